@@ -6,15 +6,20 @@ at 1/2/4/8 MI355X (BASELINE.json: configs[1] at N=1, the same per-GPU work under
 for N>1 -- weak scaling).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full   # + parity, roofline, per-kernel table, CPU baseline, bf16 run
     python bench.py --gpus 8 --steps 20 --warmup 5          # no launcher: spawns its own 8 ranks (one per GPU, RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints TWO lines on stdout:
+A plain run sets up, warms up, times the K steps and prints ONE line on stdout: the compact object of the driver's
+contract (metric, value, unit, ms_per_step, dtype, config, loss, ...).  `--dump-outputs DIR` also writes what the last
+timed step returned (loss, projection statistics) and the parameters it left behind as DIR/*.npy.
+
+With `--full`, rank 0 prints TWO lines on stdout:
   `BENCH_DETAILS {...}`  first: the full record -- the per-kernel table ("kernels": HIP-event average, algorithmic
                          bytes / flops, fraction of the roof of the kernel that ran, for every hand-written launch tag),
-                         the long-form cpu_baseline / config / dist objects.  Also written to
-                         gpurun_out/bench_details.json (or $PECLR_BENCH_DETAILS) when that directory exists;
+                         the long-form cpu_baseline / config / dist objects.  Also written to $PECLR_BENCH_DETAILS,
+                         or to bench_details.json in the scratch output folder emit() looks for, when it exists;
   `{...}`                LAST: the compact line of the driver's contract (< 4 KB) with
       "roofline"     the dominant hand-written kernel (by time): algorithmic bytes/flops per launch
                      / its average launch duration measured with HIP events on the launch stream
@@ -40,11 +45,39 @@ if ROOT not in sys.path:
 # MIOpen JIT-compiles every convolution kernel on first use (~70 s for ResNet-50 on a fresh box: the
 # PyTorch wheel ships no gfx950 kernel database).  Keep its user find-db / kernel cache in-tree so a
 # populated cache travels with the repo snapshot; an empty or stale one only costs the JIT again.
-_MIOPEN_DIR = os.path.join(ROOT, ".miopen")
-os.environ.setdefault("MIOPEN_USER_DB_PATH", os.path.join(_MIOPEN_DIR, "db"))
-os.environ.setdefault("MIOPEN_CUSTOM_CACHE_DIR", os.path.join(_MIOPEN_DIR, "cache"))
-for _d in (os.environ["MIOPEN_USER_DB_PATH"], os.environ["MIOPEN_CUSTOM_CACHE_DIR"]):
-    os.makedirs(_d, exist_ok=True)
+
+
+def miopen_dirs(root):
+    """(user find-db, kernel cache) for MIOpen: `root`/.miopen/{db,cache} when the checkout is writable; otherwise a
+    per-user directory under the system temp directory, its find-db seeded with the committed records (so MIOpen picks
+    the same solvers), because MIOpen has to write to both and a read-only checkout is no reason to fail."""
+    import glob
+    import shutil
+    import tempfile
+
+    db, cache = os.path.join(root, ".miopen", "db"), os.path.join(root, ".miopen", "cache")
+    try:
+        for d in (db, cache):
+            os.makedirs(d, exist_ok=True)
+        if os.access(db, os.W_OK | os.X_OK) and os.access(cache, os.W_OK | os.X_OK):
+            return db, cache
+    except OSError:
+        pass
+    alt = os.path.join(tempfile.gettempdir(), f"peclr-miopen-{os.getuid()}")
+    alt_db, alt_cache = os.path.join(alt, "db"), os.path.join(alt, "cache")
+    for d in (alt_db, alt_cache):
+        os.makedirs(d, exist_ok=True)
+    for src in glob.glob(os.path.join(db, "*.txt")):
+        dst = os.path.join(alt_db, os.path.basename(src))
+        if not os.path.exists(dst):
+            shutil.copyfile(src, dst)
+    return alt_db, alt_cache
+
+
+if "MIOPEN_USER_DB_PATH" not in os.environ or "MIOPEN_CUSTOM_CACHE_DIR" not in os.environ:
+    _db, _cache = miopen_dirs(ROOT)
+    os.environ.setdefault("MIOPEN_USER_DB_PATH", _db)
+    os.environ.setdefault("MIOPEN_CUSTOM_CACHE_DIR", _cache)
 
 import torch  # noqa: E402
 
@@ -114,6 +147,15 @@ def parse():
     ap.add_argument("--cpu-budget", type=float, default=400.0,
                     help="seconds of CPU work the whole-workload baseline may be predicted to take (the default configuration, "
                          "ResNet-50 2 x 128 @224, needs ~100 s on the MI355X hosts)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the oracle parity line and the fp32 GEMM accuracy check "
+                         "before the timed steps, the per-kernel HIP-event table / roofline / backbone figures (an extra eager "
+                         "pass of the K steps after graph replays), the CPU baseline, the bf16 companion run, and the "
+                         "BENCH_DETAILS line; a plain run measures and prints the compact line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (its output dict: loss, projection "
+                         "statistics) and the parameters it left behind (a fixed, seeded sample of at most 4 Mi values) as "
+                         "DIR/<name>.npy in float32 / float64")
     return ap.parse_args()
 
 
@@ -382,6 +424,14 @@ def parity_line(model, batch, autocast):
                               "loss_hip", "loss_oracle", "rows") if k in d}
 
 
+def parity_forward(model, batch, autocast):
+    """What parity_line does to the model, without the oracle (runs without --full): the same untimed training-mode forward
+    to the projections under no_grad.  It moves the BatchNorm running statistics once, and the fused BatchNorm kernels centre
+    their sums on them, so without it the timed steps would round differently from those of a --full run."""
+    with torch.no_grad(), (autocast if autocast is not None else torch.autocast("cuda", enabled=False)):
+        model._project(batch)
+
+
 def committed_profile(name, args):
     """Per-kernel figures that cannot be taken from inside the timed run (rocprofv3 kernel-trace durations,
     SQ MFMA-busy counters): read from the committed summaries under profiles/, default workload only."""
@@ -615,9 +665,9 @@ def bf16_companion():
     for a in sys.argv[1:]:
         if skip:
             skip = False
-        elif a in ("--dtype", "--graph", "--bf16-companion"):
+        elif a in ("--dtype", "--graph", "--bf16-companion", "--dump-outputs"):
             skip = True
-        elif not a.startswith(("--dtype=", "--graph=", "--bf16-companion=")):
+        elif not a.startswith(("--dtype=", "--graph=", "--bf16-companion=", "--dump-outputs=")):
             argv.append(a)
     cmd = [sys.executable, os.path.abspath(__file__), *argv, "--dtype", "bf16", "--no-cpu-baseline", "--bf16-companion", "0"]
     env = {k: v for k, v in os.environ.items() if k not in ("PECLR_BENCH_CHILD", "PECLR_BENCH_DETAILS", "PECLR_LAUNCH_MANIFEST")}
@@ -634,9 +684,10 @@ def bf16_companion():
 
 
 def wants_companion(args):
-    # (--no-cpu-baseline = "only the measurement itself": profiling / A-B commands carry it, and get no companion either)
-    return bool(args.bf16_companion and not args.no_cpu_baseline and args.dtype == "fp32" and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1
-                and not os.environ.get("PECLR_BENCH_CHILD"))
+    # (--no-cpu-baseline = "only the measurement itself": profiling / A-B commands carry it, and get no companion either;
+    # a plain run, without --full, measures its own precision only)
+    return bool(args.full and args.bf16_companion and not args.no_cpu_baseline and args.dtype == "fp32" and args.gpus == 1
+                and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not os.environ.get("PECLR_BENCH_CHILD"))
 
 
 def fp32_gemm_check(device):
@@ -677,6 +728,36 @@ def amp_steps_taken(trainer):
     overflowed); read outside the timed region."""
     scaler = getattr(trainer, "_scaler", None)
     return scaler.good_steps() if hasattr(scaler, "good_steps") else None
+
+
+DUMP_PARAM_SAMPLE = 1 << 22     # parameter values written by --dump-outputs at most (16 MB as float32)
+
+
+def dump_outputs(path, out, params, sample=DUMP_PARAM_SAMPLE):
+    """--dump-outputs: what the last timed step computed, as `path`/<name>.npy -- every entry of the step's output dict
+    (`out_<key>.npy`: the loss and the projection statistics) and the parameters the step's optimiser update left behind
+    (`params.npy`: all of them flattened in `params` order, or a fixed, seeded sample of `sample` of them in index order
+    when there are more).  Floating values keep float64 or become float32, everything else float64.  Returns
+    {name: shape}."""
+    import numpy as np
+
+    def host(t):
+        t = t.detach()
+        return t.cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy() if t.is_floating_point() \
+            else t.double().cpu().numpy()
+
+    arrays = {f"out_{k}": host(v) for k, v in out.items() if torch.is_tensor(v)}
+    params = [p.detach().reshape(-1) for p in params]
+    total = sum(p.numel() for p in params)
+    flat = torch.cat([p.float() for p in params]) if params else torch.zeros(0)
+    if total > sample:
+        idx = np.sort(np.random.default_rng(20240605).choice(total, size=sample, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    arrays["params"] = host(flat)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def main():
@@ -771,9 +852,13 @@ def main():
     parity = None
     with torch.cuda.stream(stream):
         if rank == 0 or world > 1:   # forward-only, untimed; every rank runs it (BatchNorm state stays in step)
-            parity = parity_line(model, batch, trainer._autocast() if args.dtype != "fp32" else None)
-        x6_check = (fp32_gemm_check(device) if (rank == 0 and args.dtype == "fp32" and os.environ.get("PECLR_GEMM_X6", "1") != "0")
-                    else None)
+            autocast = trainer._autocast() if args.dtype != "fp32" else None
+            if args.full:
+                parity = parity_line(model, batch, autocast)
+            else:
+                parity_forward(model, batch, autocast)
+        x6_check = (fp32_gemm_check(device) if (args.full and rank == 0 and args.dtype == "fp32"
+                                                and os.environ.get("PECLR_GEMM_X6", "1") != "0") else None)
         if split:
             # every rank must take the same path: agree on whether all captures succeeded
             ok = 1
@@ -817,16 +902,20 @@ def main():
             dt = time.perf_counter() - t0
             amp_after = amp_steps_taken(trainer)
             loss = float(out["loss"])
-            # per-kernel HIP events cannot sit inside a graph: the SAME K steps once more, eagerly, with an
-            # event pair around every hand-written launch (same kernels, same shapes, same stream)
-            _capi.EVENT_LOG, _capi.LAUNCH_ORDER, _capi.TAG_BOUND_SUFFIX = {}, [], True
-            for i in range(args.steps):
-                one_step(args.warmup + args.steps + i)
-            torch.cuda.synchronize()
+            if args.dump_outputs and rank == 0:      # before anything else runs a step
+                dump_outputs(args.dump_outputs, out, model.parameters())
+            if args.full:
+                # per-kernel HIP events cannot sit inside a graph: the SAME K steps once more, eagerly, with an
+                # event pair around every hand-written launch (same kernels, same shapes, same stream)
+                _capi.EVENT_LOG, _capi.LAUNCH_ORDER, _capi.TAG_BOUND_SUFFIX = {}, [], True
+                for i in range(args.steps):
+                    one_step(args.warmup + args.steps + i)
+                torch.cuda.synchronize()
         else:
             for i in range(args.warmup):
                 out = one_step(i)
-            _capi.EVENT_LOG, _capi.LAUNCH_ORDER, _capi.TAG_BOUND_SUFFIX = {}, [], True
+            if args.full:    # eager launches: the event pairs sit inside the timed steps themselves
+                _capi.EVENT_LOG, _capi.LAUNCH_ORDER, _capi.TAG_BOUND_SUFFIX = {}, [], True
             if world > 1:
                 torch.distributed.barrier()
             torch.cuda.synchronize()
@@ -840,10 +929,12 @@ def main():
             dt = time.perf_counter() - t0
             amp_after = amp_steps_taken(trainer)
             loss = float(out["loss"])
+            if args.dump_outputs and rank == 0:
+                dump_outputs(args.dump_outputs, out, model.parameters())
     table_steps = args.steps
     event_log, _capi.EVENT_LOG = _capi.EVENT_LOG, None
     launch_order, _capi.LAUNCH_ORDER = _capi.LAUNCH_ORDER, None
-    if rank == 0 and os.environ.get("PECLR_LAUNCH_MANIFEST"):
+    if rank == 0 and args.full and os.environ.get("PECLR_LAUNCH_MANIFEST"):
         # names of the hand-written launches of the measured pass, in order: the LAST len(order) peclr:: dispatches
         # of a rocprofv3 trace of this process are exactly these (tools/pmc_mfma.py aligns on that)
         with open(os.environ["PECLR_LAUNCH_MANIFEST"], "w") as f:
@@ -887,34 +978,6 @@ def main():
                              "are the driver's"}
     if rank == 0:
         images = world * 2 * args.pairs * args.accum * args.steps
-        n_params = sum(p.numel() for n, p in model.named_parameters() if "final_layer" not in n)
-        din = model.config.projection_head_input_dim
-        kernels = kernel_table(event_log, 2 * args.pairs, world * 2 * args.pairs, din, 512, n_params)
-        # dominant kernel = the kernel FAMILY with the largest share of the step's hand-written GPU time (avg duration x
-        # launches, summed over the tags it runs under: one GEMM kernel serves several convolution roles, and its
-        # MFMA-bound and HBM-bound shapes are logged apart); the roofline object is that family's biggest tag
-        spent = lambda k: kernels[k]["avg_us"] * kernels[k]["launches"]      # noqa: E731
-        family = lambda k: kernels[k]["kernel"] if isinstance(kernels[k].get("kernel"), str) else k   # noqa: E731
-        by_family = {}
-        for k in kernels:
-            by_family[family(k)] = by_family.get(family(k), 0.0) + spent(k)
-        top_family = max(by_family, key=by_family.get)
-        dominant = max((k for k in kernels if family(k) == top_family), key=spent)
-        roof = {k: kernels[dominant][k] for k in ("bound", "achieved", "peak", "unit", "frac")}
-        roof["kernel_family"] = {"name": top_family, "share_of_handwritten_time": round(by_family[top_family] / sum(by_family.values()), 4),
-                                 "tags": {k: {"bound": kernels[k]["bound"], "frac": kernels[k]["frac"],
-                                              "ms_per_step": round(spent(k) / (table_steps * args.accum) / 1e3, 3)}
-                                          for k in sorted(kernels, key=spent, reverse=True) if family(k) == top_family}}
-        if use_graph:
-            roof["events"] = "eager pass of the same K steps right after the timed graph replays"
-        roof.update(kernel=dominant, avg_us=kernels[dominant]["avg_us"],
-                    launches_per_step=kernels[dominant]["launches"] // (table_steps * args.accum),
-                    traffic=pmc_traffic(dominant, args),
-                    algorithmic_bytes=kernels[dominant]["bytes"], algorithmic_flops=kernels[dominant]["flops"])
-        flops_img = conv_flops_per_image(model.encoder.features, (args.size, args.size))
-        step_flops = 3 * flops_img * 2 * args.pairs * args.accum
-        peak_tf = MFMA_F32_PEAK_TF if args.dtype == "fp32" else MFMA_BF16_PEAK_TF   # fp16 dense peak = the bf16 one
-        ach_tf = step_flops * args.steps / dt / 1e12
         result = {
             "metric": "images/sec (2-view) ResNet-50 bs128 @1/2/4/8 MI355X; NT-Xent loss Δ vs ref",
             "value": round(images / dt, 2), "unit": "images/sec", "n_gpus": world, "steps": args.steps,
@@ -963,70 +1026,104 @@ def main():
                        "bn": "global-batch statistics (synchronised)" if (args.sync_bn and world > 1)
                        else "per-rank batch statistics"},
             "loss": round(loss, 6),
-            "fp32_gemm_check": x6_check,
-            "roofline": roof,
-            "kernels": kernels,
-            # fp32: the step's GEMM work runs in pair arithmetic (three fp16 products: own roof = the dense fp16 peak / 3 = 833
-            # TFLOP/s fp32-equivalent) or, with PECLR_X6_PAIR=0, on the six-product kernels (dense bf16 peak / 6 = 417); `frac` is
-            # priced against the roof of the kernels that run, frac_vs_v_mfma_f32 against the 157.3 TFLOP/s of the v_mfma_f32
-            # instructions they no longer use
-            "backbone": {"note": "whole encoder, 3x forward conv FLOPs over the step time; fp32: every 1x1 and 3x3 convolution of the "
-                                 "residual blocks (stride 1 and 2; forward, input gradient, weight gradient) and the 7x7 stem run on the "
-                                 "in-tree split-operand kernels (config.fp32_gemm); 16-bit: see config.conv16",
-                         "flops_per_step_per_gpu": step_flops, "achieved": round(ach_tf, 2), "unit": "TFLOP/s",
-                         **({"peak": round(MFMA_BF16_PEAK_TF / X6_PRODUCTS, 1), "frac": round(ach_tf / (MFMA_BF16_PEAK_TF / X6_PRODUCTS), 4),
-                             "frac_vs_x6_roof": round(ach_tf / (MFMA_BF16_PEAK_TF / 6.0), 4),
-                             "frac_vs_v_mfma_f32": round(ach_tf / MFMA_F32_PEAK_TF, 4)}
-                            if (args.dtype == "fp32" and os.environ.get("PECLR_GEMM_X6", "1") != "0") else
-                            {"peak": peak_tf, "frac": round(ach_tf / peak_tf, 4),
-                             **({"frac_vs_bf16_mfma": round(ach_tf / peak_tf, 4)} if args.dtype != "fp32" else
-                                {"frac_vs_v_mfma_f32": round(ach_tf / peak_tf, 4)})})},
-            "hand_written_us_per_step": round(sum(k["avg_us"] * k["launches"] / table_steps
-                                                  for k in kernels.values()), 1),
-            # launch-count reduction of the head / alignment / loss (reference: ~100 stock-op
-            # launches forward incl. a CPU round trip, ~60 backward through autograd)
-            "head_launches_per_step": {name: kernels[name]["launches"] // (table_steps * args.accum) for name in
-                                       ("gemm_k1_fwd", "bn_relu_fwd", "gemm_k2_fwd", "align_fwd", "ntxent_fwd", "ntxent_finalize",
-                                        "ntxent_bwd", "slab_reduce", "align_bwd", "gemm_dw2", "gemm_da", "bn_relu_bwd",
-                                        "gemm_dw1", "gemm_dh") if name in kernels},
         }
-        if parity is not None:
-            result["parity"] = parity
-            result["loss_delta_vs_oracle"] = parity["loss_delta_vs_oracle"]
-            result["sim_max_abs_delta"] = parity["sim_max_abs_delta"]
-        # figures a run cannot take of itself: rocprofv3 kernel-trace durations (HIP-event pairs add ~4 us, which
-        # matters for the us-scale head kernels) and SQ counters, from the committed profiles of this command
-        prof_file = "r03_bench_mfma.json"
-        prof = committed_profile(prof_file, args)   # tools/profile_passes.sh + tools/pmc_mfma.py
-        for name, k in kernels.items():
-            p = prof.get(name)
-            if not p:
-                continue
-            # NOT measured by this run: figures of the committed rocprofv3 passes of this command (their own build, their
-            # own box), kept apart from the live numbers
-            cp = {"source": f"profiles/{prof_file}", "rocprof_avg_us": p["avg_us"], "symbol": p.get("symbol")}
-            if min(k["avg_us"], p["avg_us"]) < 30.0:
-                work = k["flops"] / 1e12 if k["bound"] == "mfma" else k["bytes"] / 1e9
-                cp["achieved_rocprof"] = round(work / (p["avg_us"] * 1e-6), 3)
-                cp["frac_rocprof"] = round(cp["achieved_rocprof"] / k["peak"], 5)
-            for key in ("mfma_util", "mfma_busy_of_sq_busy", "lds_conflict_share", "occupancy"):
-                if key in p and (k["bound"] == "mfma" or not key.startswith("mfma")):
-                    cp[key] = p[key]
-            k["committed_profile"] = cp
         if world > 1:
             result["dist"] = dist_info
-        if world == 1 and not args.no_cpu_baseline:
-            result["cpu_baseline"] = cpu_baseline(args)
-        # launches that are latency-bound by construction (a few KB of partial sums): counted, because each costs a
-        # launch slot of the graph whatever its bytes
-        small = ("bn2d_finalize", "bn2d_bwd_finalize", "wgrad_slab_reduce", "bn2d_combine")
-        result["latency_bound_launches_per_step"] = {
-            "count": sum(k["launches"] for t, k in kernels.items() if t.split("~")[0] in small) // (table_steps * args.accum),
-            "ms": round(sum(k["launches"] * k["avg_us"] for t, k in kernels.items() if t.split("~")[0] in small)
-                        / (table_steps * args.accum) / 1e3, 3)}
-        if wants_companion(args):           # (eager fallback of the default run: the child-process route above did not print)
-            result["bf16_companion"] = bf16_companion()
-        emit(result)
+        if args.full:      # per-kernel table, roofline, backbone, parity, CPU baseline, bf16 companion
+            n_params = sum(p.numel() for n, p in model.named_parameters() if "final_layer" not in n)
+            din = model.config.projection_head_input_dim
+            kernels = kernel_table(event_log, 2 * args.pairs, world * 2 * args.pairs, din, 512, n_params)
+            # dominant kernel = the kernel FAMILY with the largest share of the step's hand-written GPU time (avg duration x
+            # launches, summed over the tags it runs under: one GEMM kernel serves several convolution roles, and its
+            # MFMA-bound and HBM-bound shapes are logged apart); the roofline object is that family's biggest tag
+            spent = lambda k: kernels[k]["avg_us"] * kernels[k]["launches"]      # noqa: E731
+            family = lambda k: kernels[k]["kernel"] if isinstance(kernels[k].get("kernel"), str) else k   # noqa: E731
+            by_family = {}
+            for k in kernels:
+                by_family[family(k)] = by_family.get(family(k), 0.0) + spent(k)
+            top_family = max(by_family, key=by_family.get)
+            dominant = max((k for k in kernels if family(k) == top_family), key=spent)
+            roof = {k: kernels[dominant][k] for k in ("bound", "achieved", "peak", "unit", "frac")}
+            roof["kernel_family"] = {"name": top_family, "share_of_handwritten_time": round(by_family[top_family] / sum(by_family.values()), 4),
+                                     "tags": {k: {"bound": kernels[k]["bound"], "frac": kernels[k]["frac"],
+                                                  "ms_per_step": round(spent(k) / (table_steps * args.accum) / 1e3, 3)}
+                                              for k in sorted(kernels, key=spent, reverse=True) if family(k) == top_family}}
+            if use_graph:
+                roof["events"] = "eager pass of the same K steps right after the timed graph replays"
+            roof.update(kernel=dominant, avg_us=kernels[dominant]["avg_us"],
+                        launches_per_step=kernels[dominant]["launches"] // (table_steps * args.accum),
+                        traffic=pmc_traffic(dominant, args),
+                        algorithmic_bytes=kernels[dominant]["bytes"], algorithmic_flops=kernels[dominant]["flops"])
+            flops_img = conv_flops_per_image(model.encoder.features, (args.size, args.size))
+            step_flops = 3 * flops_img * 2 * args.pairs * args.accum
+            peak_tf = MFMA_F32_PEAK_TF if args.dtype == "fp32" else MFMA_BF16_PEAK_TF   # fp16 dense peak = the bf16 one
+            ach_tf = step_flops * args.steps / dt / 1e12
+            result.update({
+                "fp32_gemm_check": x6_check,
+                "roofline": roof,
+                "kernels": kernels,
+                # fp32: the step's GEMM work runs in pair arithmetic (three fp16 products: own roof = the dense fp16 peak / 3 = 833
+                # TFLOP/s fp32-equivalent) or, with PECLR_X6_PAIR=0, on the six-product kernels (dense bf16 peak / 6 = 417); `frac` is
+                # priced against the roof of the kernels that run, frac_vs_v_mfma_f32 against the 157.3 TFLOP/s of the v_mfma_f32
+                # instructions they no longer use
+                "backbone": {"note": "whole encoder, 3x forward conv FLOPs over the step time; fp32: every 1x1 and 3x3 convolution of the "
+                                     "residual blocks (stride 1 and 2; forward, input gradient, weight gradient) and the 7x7 stem run on the "
+                                     "in-tree split-operand kernels (config.fp32_gemm); 16-bit: see config.conv16",
+                             "flops_per_step_per_gpu": step_flops, "achieved": round(ach_tf, 2), "unit": "TFLOP/s",
+                             **({"peak": round(MFMA_BF16_PEAK_TF / X6_PRODUCTS, 1), "frac": round(ach_tf / (MFMA_BF16_PEAK_TF / X6_PRODUCTS), 4),
+                                 "frac_vs_x6_roof": round(ach_tf / (MFMA_BF16_PEAK_TF / 6.0), 4),
+                                 "frac_vs_v_mfma_f32": round(ach_tf / MFMA_F32_PEAK_TF, 4)}
+                                if (args.dtype == "fp32" and os.environ.get("PECLR_GEMM_X6", "1") != "0") else
+                                {"peak": peak_tf, "frac": round(ach_tf / peak_tf, 4),
+                                 **({"frac_vs_bf16_mfma": round(ach_tf / peak_tf, 4)} if args.dtype != "fp32" else
+                                    {"frac_vs_v_mfma_f32": round(ach_tf / peak_tf, 4)})})},
+                "hand_written_us_per_step": round(sum(k["avg_us"] * k["launches"] / table_steps
+                                                      for k in kernels.values()), 1),
+                # launch-count reduction of the head / alignment / loss (reference: ~100 stock-op
+                # launches forward incl. a CPU round trip, ~60 backward through autograd)
+                "head_launches_per_step": {name: kernels[name]["launches"] // (table_steps * args.accum) for name in
+                                           ("gemm_k1_fwd", "bn_relu_fwd", "gemm_k2_fwd", "align_fwd", "ntxent_fwd", "ntxent_finalize",
+                                            "ntxent_bwd", "slab_reduce", "align_bwd", "gemm_dw2", "gemm_da", "bn_relu_bwd",
+                                            "gemm_dw1", "gemm_dh") if name in kernels},
+            })
+            if parity is not None:
+                result["parity"] = parity
+                result["loss_delta_vs_oracle"] = parity["loss_delta_vs_oracle"]
+                result["sim_max_abs_delta"] = parity["sim_max_abs_delta"]
+            # figures a run cannot take of itself: rocprofv3 kernel-trace durations (HIP-event pairs add ~4 us, which
+            # matters for the us-scale head kernels) and SQ counters, from the committed profiles of this command
+            prof_file = "r03_bench_mfma.json"
+            prof = committed_profile(prof_file, args)   # tools/profile_passes.sh + tools/pmc_mfma.py
+            for name, k in kernels.items():
+                p = prof.get(name)
+                if not p:
+                    continue
+                # NOT measured by this run: figures of the committed rocprofv3 passes of this command (their own build, their
+                # own box), kept apart from the live numbers
+                cp = {"source": f"profiles/{prof_file}", "rocprof_avg_us": p["avg_us"], "symbol": p.get("symbol")}
+                if min(k["avg_us"], p["avg_us"]) < 30.0:
+                    work = k["flops"] / 1e12 if k["bound"] == "mfma" else k["bytes"] / 1e9
+                    cp["achieved_rocprof"] = round(work / (p["avg_us"] * 1e-6), 3)
+                    cp["frac_rocprof"] = round(cp["achieved_rocprof"] / k["peak"], 5)
+                for key in ("mfma_util", "mfma_busy_of_sq_busy", "lds_conflict_share", "occupancy"):
+                    if key in p and (k["bound"] == "mfma" or not key.startswith("mfma")):
+                        cp[key] = p[key]
+                k["committed_profile"] = cp
+            if world == 1 and not args.no_cpu_baseline:
+                result["cpu_baseline"] = cpu_baseline(args)
+            # launches that are latency-bound by construction (a few KB of partial sums): counted, because each costs a
+            # launch slot of the graph whatever its bytes
+            small = ("bn2d_finalize", "bn2d_bwd_finalize", "wgrad_slab_reduce", "bn2d_combine")
+            result["latency_bound_launches_per_step"] = {
+                "count": sum(k["launches"] for t, k in kernels.items() if t.split("~")[0] in small) // (table_steps * args.accum),
+                "ms": round(sum(k["launches"] * k["avg_us"] for t, k in kernels.items() if t.split("~")[0] in small)
+                            / (table_steps * args.accum) / 1e3, 3)}
+            if wants_companion(args):           # (eager fallback of the default run: the child-process route above did not print)
+                result["bf16_companion"] = bf16_companion()
+            emit(result)
+        else:
+            result["details"] = "per-kernel table, roofline, parity, CPU baseline: bench.py --full"
+            print(compact_line(result), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()
 

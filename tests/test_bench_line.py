@@ -71,11 +71,11 @@ def test_bf16_companion_rides_in_the_compact_line():
     assert {"bound", "kernel", "achieved", "peak", "unit", "frac", "avg_us"} <= set(roof)
     assert roof["frac"] == pytest.approx(roof["achieved"] / roof["peak"], rel=1e-3)
     assert out["dtype"] == "fp32" and out["ms_per_step"] == full["ms_per_step"]         # the judged numbers stay the fp32 run's
-    # which runs get one: the default fp32 single-GPU command only
+    # which runs get one: the default fp32 single-GPU command with --full only (a plain run measures its own precision)
     argv = sys.argv
     try:
-        for extra, want in (([], True), (["--dtype", "bf16"], False), (["--no-cpu-baseline"], False), (["--bf16-companion", "0"], False),
-                            (["--gpus", "2"], False)):
+        for extra, want in ((["--full"], True), (["--full", "--dtype", "bf16"], False), (["--full", "--no-cpu-baseline"], False),
+                            (["--full", "--bf16-companion", "0"], False), (["--full", "--gpus", "2"], False), ([], False)):
             sys.argv = ["bench.py", *extra]
             assert bench.wants_companion(bench.parse()) == want, extra
     finally:
@@ -89,6 +89,50 @@ def test_emit_prints_details_first_and_the_compact_line_last(capsys, tmp_path, m
     assert len(lines) == 2 and lines[0].startswith("BENCH_DETAILS {") and lines[1].startswith("{")
     assert "kernels" in json.loads(lines[0][len("BENCH_DETAILS "):]) and len(lines[1]) < bench.COMPACT_LIMIT
     assert "kernels" in json.load(open(tmp_path / "d.json"))
+
+
+def test_plain_run_options_and_its_compact_line():
+    """A plain run (no --full) carries the contract keys and nothing that needs a pass of its own."""
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        args = bench.parse()
+        assert not args.full and args.dump_outputs is None and args.steps == 7 and args.warmup == 2
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "out_dir"]
+        args = bench.parse()
+        assert args.full and args.dump_outputs == "out_dir"
+    finally:
+        sys.argv = argv
+    full = recorded_full_line()
+    plain = {k: full[k] for k in CONTRACT | {"loss"}}
+    plain["details"] = "per-kernel table, roofline, parity, CPU baseline: bench.py --full"
+    out = json.loads(bench.compact_line(plain))
+    assert CONTRACT <= set(out) and out["ms_per_step"] == full["ms_per_step"] and out["value"] == full["value"]
+    assert not {"roofline", "backbone", "cpu_baseline", "parity", "fp32_gemm_check", "bf16_companion"} & set(out)
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_parameter_sample(tmp_path):
+    import numpy as np
+    import torch
+
+    g = torch.Generator().manual_seed(3)
+    params = [torch.randn(40, 30, generator=g), torch.randn(7, generator=g, dtype=torch.float64), torch.randn(5, generator=g).half()]
+    out = {"loss": torch.tensor(2.5), "stat": torch.tensor([1.0, 2.0], dtype=torch.float64), "count": torch.tensor(3)}
+    shapes = bench.dump_outputs(str(tmp_path / "a"), out, params)
+    assert shapes == {"out_loss": [], "out_stat": [2], "out_count": [], "params": [1212]}
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in shapes}
+    assert {n: list(v.shape) for n, v in a.items()} == shapes
+    assert a["out_loss"].dtype == np.float32 and a["out_stat"].dtype == np.float64 and a["out_count"].dtype == np.float64
+    assert float(a["out_loss"]) == 2.5 and float(a["out_count"]) == 3.0
+    flat = torch.cat([p.reshape(-1).float() for p in params]).numpy()
+    assert a["params"].dtype == np.float32 and np.array_equal(a["params"], flat)
+    # more parameters than the cap: a seeded sample in index order, the same from run to run
+    bench.dump_outputs(str(tmp_path / "b"), out, params, sample=100)
+    bench.dump_outputs(str(tmp_path / "c"), out, params, sample=100)
+    b, c = np.load(tmp_path / "b" / "params.npy"), np.load(tmp_path / "c" / "params.npy")
+    assert b.shape == (100,) and np.array_equal(b, c) and np.isin(b, flat).all()
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert total < 64 << 20 and bench.DUMP_PARAM_SAMPLE * 4 < 64 << 20
 
 
 @pytest.mark.timeout(300)
@@ -132,3 +176,32 @@ def test_a_rank_that_dies_takes_the_whole_launch_down_instead_of_hanging_it():
     assert p.returncode != 0 and "rank 1 exited with code 3" in p.stderr, p.stderr[-2000:]
     assert time.monotonic() - t0 < 120
     assert not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_plain_run_prints_the_contract_line_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (small shape): one stdout line, K timed steps, no per-kernel
+    pass or checker output, and the last timed step's outputs as float .npy files within 64 MB."""
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    out_dir = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--resnet", "18", "--pairs", "8", "--size", "64", "--dump-outputs", str(out_dir)],
+                       env=env, capture_output=True, text=True, timeout=560, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = p.stdout.strip().splitlines()
+    assert len(lines) == 1 and lines[0].startswith("{") and "BENCH_DETAILS" not in p.stdout
+    r = json.loads(lines[0])
+    assert CONTRACT <= set(r) and r["steps"] == 3 and r["warmup"] == 1 and r["dtype"] == "fp32" and r["unit"] == "images/sec"
+    assert r["value"] == pytest.approx(2 * 8 * 3 / (r["ms_per_step"] * 3e-3), rel=1e-3)
+    assert not {"roofline", "kernels", "cpu_baseline", "parity", "fp32_gemm_check", "bf16_companion"} & set(r)
+    files = sorted(os.listdir(out_dir))
+    assert "out_loss.npy" in files and "params.npy" in files
+    assert sum(os.path.getsize(out_dir / f) for f in files) <= 64 << 20
+    for f in files:
+        a = np.load(out_dir / f)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), f
+    assert float(np.load(out_dir / "out_loss.npy")) == pytest.approx(r["loss"], abs=1e-6)
+    assert np.load(out_dir / "params.npy").shape == (bench.DUMP_PARAM_SAMPLE,)      # ResNet-18 + head: more than the cap

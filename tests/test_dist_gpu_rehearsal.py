@@ -222,7 +222,7 @@ def test_bench_two_ranks_on_one_gpu_emits_a_valid_line(graph, dtype):
     # the literal command form the driver runs for SCALE (`python bench.py --gpus N ...`, no launcher, no WORLD_SIZE):
     # bench.py spawns its own ranks; the two test-only variables put both on cuda:0 over gloo (RCCL refuses that)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--resnet", "18",
-           "--pairs", "8", "--size", "64", "--graph", graph, "--dtype", dtype]
+           "--pairs", "8", "--size", "64", "--graph", graph, "--dtype", dtype, "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(PECLR_DIST_BACKEND="gloo", PECLR_SHARE_DEVICE="1")
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=800, cwd=ROOT)

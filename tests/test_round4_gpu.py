@@ -55,13 +55,14 @@ def _errors(got, want):
     return e
 
 
-def _check(got, want, stock, floors, what):
+def _check(got, want, stock, floors, what, stock_want=None):
     """In-tree fp32 against float64, CALIBRATED by stock fp32 ops (MIOpen + ATen) against the same float64 run: train-mode
     BatchNorm over few rows amplifies fp32 round-off (and a ReLU decision within round-off of zero flips a whole gradient
     element) by an amount that depends on depth and batch, so the bar is 6 x what the stock fp32 path shows on the same
     data, with a floor.  A dropped term -- a shortcut gradient missing from a reduction, a parity class, stale weight
-    planes -- is O(0.1 ... 1) and two to three orders above either."""
-    mine, theirs = _errors(got, want), _errors(stock, want)
+    planes -- is O(0.1 ... 1) and two to three orders above either.  stock_want: the float64 run the stock arm is measured
+    against, when `want` is not it (a float64 run that takes the in-tree arm's rectifier decisions at its ties)."""
+    mine, theirs = _errors(got, want), _errors(stock, want if stock_want is None else stock_want)
     for k, floor in floors.items():
         assert mine[k] <= max(6 * theirs[k], floor), (what, k, mine, theirs)
     return mine, theirs
@@ -133,6 +134,38 @@ def _rectifier_ties(pre64, act32, tol=1e-5):
     return wrong, ties, near
 
 
+def _run_with_decisions(ref64, x64, gy64, act32, tol=1e-5):
+    """`_run` of the float64 stock network, except that where a fused BatchNorm's pre-activation is within tol (relative) of
+    zero the ReLU takes the decision of the in-tree arm (`act32`: `_in_tree_activations` of the same weights and input)
+    instead of its own: the gradients then differ from the in-tree arm's by arithmetic alone, not by a rectifier tie of the
+    in-tree forward (counted and bounded by `_rectifier_ties`) that falls the other way than float64's."""
+    from peclr_amd import bn2d as B
+
+    names = {m: n for n, m in ref64.named_modules()}
+    hooks = []
+
+    def hook(mod, args, out):
+        xin = args[0]
+        res = args[1] if len(args) > 1 else None
+        relu = args[2] if len(args) > 2 else mod.default_relu
+        a32 = act32.get(names[mod])
+        if not relu or a32 is None or a32.shape != out.shape:
+            return None
+        a = torch.nn.functional.batch_norm(xin, None, None, mod.weight, mod.bias, True, 0.0, mod.eps)
+        pre = a + res if res is not None else a
+        close = pre.detach().abs() <= tol * float(pre.detach().abs().max())
+        return pre * torch.where(close, a32 > 0, pre.detach() > 0)
+
+    for m in ref64.modules():
+        if isinstance(m, B.FusedBatchNormAct2d):
+            hooks.append(m.register_forward_hook(hook))
+    try:
+        return _run(ref64, x64, gy64)
+    finally:
+        for h in hooks:
+            h.remove()
+
+
 def _basicblock_arm():
     """Three BasicBlocks at routed sizes (identity, identity, stride 2 + downsample; 32 768 rows), fresh from fixed seeds."""
     from peclr_amd import bn2d as B
@@ -175,12 +208,19 @@ def test_basicblock_input_with_two_consumers_gets_the_whole_batchnorm_reduction(
     # 1e-5 (relative) of zero -- a handful of the 1.1e7 decisions, each of which moves one element's gradient (2e-4 .. 5e-4
     # norm-wise here, for ANY fp32 evaluation: the stock arm has its own)
     fresh, _, _ = _basicblock_arm()
+    ref_tied = _f64_copy(fresh)              # (before any forward moves the running statistics)
     B.enable_hip_batchnorm(fresh)
-    wrong, ties, near = _rectifier_ties(_rectifier_margins(_f64_copy(fresh), x.double()), _in_tree_activations(fresh, x))
+    pre64 = _rectifier_margins(_f64_copy(fresh), x.double())
+    act32 = _in_tree_activations(fresh, x)
+    wrong, ties, near = _rectifier_ties(pre64, act32)
     print(f"rectifier decisions that differ from float64's: {wrong} away from zero, {ties} of the {near} within 1e-5 of it")
     assert wrong == 0 and ties <= 8
+    # those ties are measured against float64 that decides them as the in-tree arm did; whether the stock arm's own ties
+    # lift its calibration depends on the algorithms MIOpen picks, so it is held to the plain float64 run as before
+    want_tied = _run_with_decisions(ref_tied, x.double(), gy.double(), act32)
     # sums that miss the shortcut's contribution -- what this test is for -- are off by tens of per cent
-    print(_check(got, want, _run(stock, x, gy), {"y": 2e-5, "dx": 1e-4, "grad": 2e-4, "stat": 1e-5}, "BasicBlock x 3"))
+    print(_check(got, want_tied, _run(stock, x, gy), {"y": 2e-5, "dx": 1e-4, "grad": 2e-4, "stat": 1e-5}, "BasicBlock x 3",
+                 stock_want=want))
 
 
 def test_in_tree_basicblock_arm_gives_the_same_bits_every_time():

@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: ab.sh "<bench args>" TAG1,TAG2 ENVSET1 ENVSET2 ...   (an ENVSET is "A=1,B=2" or "-" for none): alternating same-box runs
-ARGS=$1; TAGS=${2//,/ }; shift 2
+ARGS="$1 --full"; TAGS=${2//,/ }; shift 2
 mkdir -p gpurun_out/ab
 for rep in 1 2; do
   for set in "$@"; do

@@ -22,7 +22,7 @@ run() {  # name, pmc ("" = trace only), command...
   fi
   echo "$name rc=$? $(ls "$d" | tr '\n' ' ')"
 }
-BENCH="python $ROOT/bench.py --graph 0 --steps 2 --warmup 2 --no-cpu-baseline"
+BENCH="python $ROOT/bench.py --graph 0 --steps 2 --warmup 2 --no-cpu-baseline --full"
 run probe_trace "" python "$ROOT/tools/mfma_probe.py"
 run probe_pmc_a "$PMC_A" python "$ROOT/tools/mfma_probe.py"
 run probe_pmc_b "$PMC_B" python "$ROOT/tools/mfma_probe.py"

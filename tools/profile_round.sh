@@ -22,7 +22,7 @@ run() {  # name, pmc ("" = trace only), command...
   echo "$name rc=$? $(ls "$d" | tr '\n' ' ')"
 }
 for DT in $DTYPES; do
-  BENCH="python $ROOT/bench.py --graph 0 --steps 2 --warmup 2 --no-cpu-baseline --dtype $DT"
+  BENCH="python $ROOT/bench.py --graph 0 --steps 2 --warmup 2 --no-cpu-baseline --full --dtype $DT"
   run ${DT}_trace "" $BENCH
   run ${DT}_pmc_a "$PMC_A" $BENCH
   run ${DT}_pmc_b "$PMC_B" $BENCH
