@@ -530,6 +530,45 @@ int peclr_augment_resize_color_norm(const uint8_t* crops, int B, int H, int W, i
                                     const float* stdv, int channels_last, float* out,
                                     peclr_stream_t stream);
 
+/* The reference's other five augmentations (sample_augmenter.py:67-84 sobel_filter / cut_out /
+ * gaussian_blur before the rotation, :113-125 gaussian_noise / color_drop after the colour jitter),
+ * TwoViewAugmenter(extended=True).  Used only for batches that draw one of them; the parameters
+ * (decisions, cut-out box, blur taps, noise table) come from peclr_amd/augment.py.
+ *
+ * ext : [n_views][B][PECLR_AUG_EXT_INTS] ints per (view, sample):
+ *         [0]     PECLR_AUG_EXT_* bits       [1..4] cut-out rows [r0, r1), columns [c0, c1)
+ *         [5]     cut-out fill (0..254)       [6]    offset into `coefs` of the view's blur taps (-1: none)
+ *         [7]     reserved (0)
+ * coefs: Q8 Gaussian taps (sum 256) per blurred view: kx horizontal taps, then ky vertical ones
+ *
+ * peclr_augment_pre_u8 (stage 0, two launches when blur_tmp != NULL): images -> srcs
+ *   [n_views][B][H][W][3] u8, in the reference's order Sobel (3x3 dx + dy of BGR2GRAY, reflect-101,
+ *   low byte into all three channels), cut-out, Gaussian blur (separable, reflect-101; rows u8 x Q8
+ *   into blur_tmp [n_views][B][H][W][3] u16, columns (sum + 2^15) >> 16).  Samples without a pre-op
+ *   are copied.  kx, ky: the batch's odd kernel lengths, at most PECLR_AUG_MAX_BLUR_KSIZE.
+ *   blur_tmp may be NULL only if no record has the blur bit (blur is then skipped).
+ *   peclr_augment_warp_crop_u8 then runs once per view on srcs (n_views = 1).
+ * peclr_augment_resize_color_norm_ext: peclr_augment_resize_color_norm, then per pixel and channel
+ *   n = #{k < n_table : noise_table[k] <= u} with u from Philox4x32-10 (key = noise_seed, counter =
+ *   (out pixel index, sample, view, call), output word = channel), pixel = (pixel + n) mod 256;
+ *   then colour drop (BGR2GRAY into all three channels). */
+#define PECLR_AUG_EXT_INTS 8
+#define PECLR_AUG_EXT_SOBEL 1
+#define PECLR_AUG_EXT_CUT_OUT 2
+#define PECLR_AUG_EXT_BLUR 4
+#define PECLR_AUG_EXT_NOISE 8
+#define PECLR_AUG_EXT_COLOR_DROP 16
+#define PECLR_AUG_MAX_BLUR_KSIZE 257
+int peclr_augment_pre_u8(const uint8_t* images, int B, int H, int W, int n_views, const int* ext,
+                         const int* coefs, int kx, int ky, uint8_t* srcs, uint16_t* blur_tmp,
+                         peclr_stream_t stream);
+int peclr_augment_resize_color_norm_ext(const uint8_t* crops, int B, int H, int W, int n_views,
+                                        const double* params, const int* ext,
+                                        const uint32_t* noise_table, int n_table, uint64_t noise_seed,
+                                        uint32_t call, int out_h, int out_w, const float* mean,
+                                        const float* stdv, int channels_last, float* out,
+                                        peclr_stream_t stream);
+
 /* ---- 16-bit convolutions of the residual blocks (bf16 / fp16 autocast: BASELINE configs C3 / C5 and the reference's own
  * `precision: 16`, training_config.json:9, peclr_training.py:78-79), csrc/conv_h.hip.  They replace MIOpen's 16-bit
  * convolution kernels behind torchvision's Bottleneck / BasicBlock (resnet_model.py:15) -- forward and input gradient of the

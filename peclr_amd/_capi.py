@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_uint32, c_uint64, c_void_p
 from typing import Optional
 
 import torch  # must be imported BEFORE the CDLL: the .so binds to torch's libamdhip64.so.7
@@ -74,6 +74,9 @@ SIGNATURES = {
     "peclr_augment_warp_crop_u8": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "peclr_augment_resize_color_norm": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P, _P, c_int, _P,
                                                 _P]),
+    "peclr_augment_pre_u8": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P]),
+    "peclr_augment_resize_color_norm_ext": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, c_uint64,
+                                                    c_uint32, c_int, c_int, _P, _P, c_int, _P, _P]),
     "peclr_gemm_x6_f32": (c_int, [c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P]),
     "peclr_gemm_x6_tn_slabs": (c_int, [c_int, c_int, c_int]),
     "peclr_gemm_x6_tn_f32": (c_int, [c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, _P]),
@@ -1395,3 +1398,75 @@ def augment_views(images: torch.Tensor, params: torch.Tensor, out_hw, mean, std,
                                                    int(channels_last), out.data_ptr(), _stream())
     _check(rc, "peclr_augment_resize_color_norm")
     return out, crops
+
+
+AUG_EXT_INTS = 8
+AUG_EXT_BLUR = 4
+AUG_EXT_PRE, AUG_EXT_POST = 1 | 2 | 4, 8 | 16  # sobel, cut-out, blur | noise, colour drop
+
+
+def augment_views_ext(images: torch.Tensor, params: torch.Tensor, ext: torch.Tensor, coefs: torch.Tensor, ksize,
+                      noise_table: torch.Tensor, n_table: int, noise_seed: int, call: int, ops: int, out_hw, mean, std,
+                      channels_last: bool = True):
+    """augment_views plus the reference's other five augmentations (peclr_amd/augment.py builds the inputs):
+    ext [V,B,8] int32 records, coefs int32 Q8 blur taps, ksize (horizontal, vertical) blur lengths of the batch,
+    noise_table int32 storage of n_table uint32 thresholds, the Philox key and call index, and `ops`, the OR of
+    all records' bits (the stages it names are the only ones launched).  Stage 0 (sobel / cut-out / blur) writes
+    per-view sources, the warp then runs once per view on them.
+    Returns (out, srcs or None, crops)."""
+    if not images.is_cuda or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+        raise PeclrHipError(f"augment: images must be a [B,H,W,3] uint8 HIP tensor, got {images.dtype} "
+                            f"{tuple(images.shape)} on {images.device} (peclr_amd has no CPU path)")
+    if not images.is_contiguous():
+        raise PeclrHipError("augment: images must be contiguous")
+    b, h, w, _ = images.shape
+    if (params.dtype != torch.float64 or params.dim() != 3 or params.shape[1] != b
+            or params.shape[2] != AUG_PARAM_DOUBLES or not params.is_cuda or not params.is_contiguous()):
+        raise PeclrHipError(f"augment: params must be a contiguous [V,{b},{AUG_PARAM_DOUBLES}] float64 HIP tensor")
+    v = params.shape[0]
+    if ext.dtype != torch.int32 or tuple(ext.shape) != (v, b, AUG_EXT_INTS) or not ext.is_cuda or not ext.is_contiguous():
+        raise PeclrHipError(f"augment: ext must be a contiguous [{v},{b},{AUG_EXT_INTS}] int32 HIP tensor")
+    for name, t in (("coefs", coefs), ("noise_table", noise_table)):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_cuda or not t.is_contiguous():
+            raise PeclrHipError(f"augment: {name} must be a contiguous 1-D int32 HIP tensor")
+    if not 0 <= n_table <= noise_table.numel():
+        raise PeclrHipError(f"augment: n_table {n_table} exceeds the table's {noise_table.numel()} entries")
+    oh, ow = out_hw
+    kx, ky = ksize
+    dev, stream = images.device, _stream()
+    crops = torch.empty((v, b, h, w, 3), device=dev, dtype=torch.uint8)
+    out = torch.empty((v * b, 3, oh, ow), device=dev, dtype=torch.float32,
+                      memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    mean_arr, std_arr = (c_float * 3)(*mean), (c_float * 3)(*std)
+    srcs = None
+    if ops & AUG_EXT_PRE:
+        srcs = torch.empty((v, b, h, w, 3), device=dev, dtype=torch.uint8)
+        tmp = torch.empty((v, b, h, w, 3), device=dev, dtype=torch.int16) if ops & AUG_EXT_BLUR else None
+        blur_bytes = (kx + ky) * 3 if tmp is not None else 0
+        with _timed("augment_pre", v * b * h * w * (3 + 3 + 4 * (3 if tmp is not None else 0)), v * b * h * w * blur_bytes):
+            rc = lib().peclr_augment_pre_u8(images.data_ptr(), b, h, w, v, ext.data_ptr(), coefs.data_ptr(), kx, ky,
+                                            srcs.data_ptr(), None if tmp is None else tmp.data_ptr(), stream)
+        _check(rc, "peclr_augment_pre_u8")
+        for i in range(v):
+            with _timed("augment_warp_crop", 2 * b * h * w * 3):
+                rc = lib().peclr_augment_warp_crop_u8(srcs[i].data_ptr(), b, h, w, 1, params[i].data_ptr(),
+                                                      crops[i].data_ptr(), stream)
+            _check(rc, "peclr_augment_warp_crop_u8")
+    else:
+        with _timed("augment_warp_crop", 2 * v * b * h * w * 3):
+            rc = lib().peclr_augment_warp_crop_u8(images.data_ptr(), b, h, w, v, params.data_ptr(), crops.data_ptr(), stream)
+        _check(rc, "peclr_augment_warp_crop_u8")
+    mp, sp = ctypes.cast(mean_arr, c_void_p), ctypes.cast(std_arr, c_void_p)
+    if ops & AUG_EXT_POST:
+        with _timed("augment_resize_color_norm_ext", v * b * (h * w * 3 + oh * ow * 12)):
+            rc = lib().peclr_augment_resize_color_norm_ext(crops.data_ptr(), b, h, w, v, params.data_ptr(), ext.data_ptr(),
+                                                           noise_table.data_ptr(), n_table, noise_seed & (2 ** 64 - 1),
+                                                           call & 0xFFFFFFFF, oh, ow, mp, sp, int(channels_last),
+                                                           out.data_ptr(), stream)
+        _check(rc, "peclr_augment_resize_color_norm_ext")
+    else:
+        with _timed("augment_resize_color_norm", v * b * (h * w * 3 + oh * ow * 12)):
+            rc = lib().peclr_augment_resize_color_norm(crops.data_ptr(), b, h, w, v, params.data_ptr(), oh, ow, mp, sp,
+                                                       int(channels_last), out.data_ptr(), stream)
+        _check(rc, "peclr_augment_resize_color_norm")
+    return out, srcs, crops

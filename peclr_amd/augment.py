@@ -17,9 +17,11 @@ The emitted dict is what torch's default collate makes of the reference's per-sa
 (only with rotate); `h/s/a/b_{1,2}` float64 [B] (only with colour jitter); `crop_margin_scale_{1,2}`
 float64 [B]; `blur_flag_{1,2}` bool [B].
 
-Flags outside the recipe (sobel_filter, cut_out, gaussian_blur, gaussian_noise, color_drop) raise
-NotImplementedError; `resize` is required (without it the reference's crops have per-sample sizes
-and cannot be collated either).
+The other five flags of the reference (sobel_filter, cut_out, gaussian_blur, gaussian_noise,
+color_drop) are opt-in: `TwoViewAugmenter(..., extended=True)`.  Without it they raise
+NotImplementedError.  With it their draws join the reference's order and their pixels run in two
+more device stages (see `TwoViewAugmenter.__init__`).  `resize` is required either way (without it
+the reference's crops have per-sample sizes and cannot be collated either).
 """
 from __future__ import annotations
 
@@ -27,6 +29,7 @@ import math
 import random as _random
 from typing import Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 from torch import Tensor
 
@@ -36,11 +39,18 @@ IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
 PARENT_JOINT, CHILD_JOINT = 0, 2  # wrist, index_mcp (reference data_loader/utils.py:15-16)
 _UNSUPPORTED = ("sobel_filter", "cut_out", "gaussian_blur", "gaussian_noise", "color_drop")
+# per-(view, sample) extension record, include/peclr_hip.h PECLR_AUG_EXT_INTS
+EXT_INTS = 8
+EXT_SOBEL, EXT_CUT_OUT, EXT_BLUR, EXT_NOISE, EXT_COLOR_DROP = 1, 2, 4, 8, 16
+EXT_PRE = EXT_SOBEL | EXT_CUT_OUT | EXT_BLUR
+EXT_POST = EXT_NOISE | EXT_COLOR_DROP
+MAX_BLUR_KSIZE = 257  # csrc/augment.hip's stage-0 limit: radius 128, enough for images up to 2048 on a side
 
 DEFAULT_PARAMS = {  # reference src/experiments/config/training_config.json
     "crop_margin": 1.25, "crop_margin_range": [0.9, 1.5], "hue_factor_range": [0.01, 1.0], "max_angle": 45,
     "min_angle": -45, "resize_shape": [128, 128], "sat_factor_range": [0.01, 1.0],
     "value_factor_alpha_range": [0.5, 1], "value_factor_beta_range": [5, 20], "crop_box_jitter": [0.0, 15.0],
+    "cut_out_fraction": [0.0, 0.16], "sobel_kernel": 3, "noise_std": 25,
 }
 RECIPE_FLAGS = {"color_jitter": True, "random_crop": True, "rotate": True, "crop": True, "resize": True}
 
@@ -72,22 +82,100 @@ def _invert_affine(m: List[List[float]]) -> List[float]:
     return [m0, m1, b1, m3, m4, b2]
 
 
+def blur_ksize(image_hw: Tuple[int, int]) -> Tuple[int, int]:
+    """gaussian_blur_sample's kernel size from the FULL source shape: int(0.1 * side), made odd.  cv2 reads
+    the tuple as (width, height), so the HORIZONTAL length comes from H and the vertical one from W (the
+    reference's swap, visible on non-square images).  Returns (horizontal, vertical)."""
+    kx, ky = int(image_hw[0] * 0.1), int(image_hw[1] * 0.1)
+    return kx + 1 if kx % 2 == 0 else kx, ky + 1 if ky % 2 == 0 else ky
+
+
+def gaussian_kernel_q8(n: int, sigma: float) -> List[int]:
+    """The 8-bit fixed-point Gaussian taps (8 fractional bits, summing to 256) of cv2.GaussianBlur's bit-exact
+    8U path.  Restated from memory of OpenCV 4.4's getGaussianKernelBitExact + getGaussianKernelFixedPoint_ED
+    (imgproc/src/smooth.dispatch.cpp); no OpenCV source, wheel or cv2 is available to check it, so like the
+    warp / resize / HSV restatements it is unpinned.  float64 Gaussian normalised to 1 (OpenCV uses a
+    software double, which may differ from libm's exp in the last bit); error-diffused round-half-even from
+    the outer taps inwards; the centre tap takes what is left of 256."""
+    if n < 1 or n % 2 == 0:
+        raise ValueError(f"Gaussian kernel size must be odd and positive, got {n}")
+    if n == 1:
+        return [256]
+    scale2x = -0.125 / (sigma * sigma)
+    half = (n - 1) // 2
+    values = [math.exp(float((1 - n + 2 * i) ** 2) * scale2x) for i in range(half)]
+    total = 0.0
+    for t in values:
+        total += t
+    total = total * 2.0 + 1.0
+    mul = 1.0 / total
+    taps, err, acc = [0] * n, 0.0, 0
+    for i in range(half):
+        adj = values[i] * mul * 256.0 + err
+        v = round(adj)  # Python's round: half to even, as cvRound
+        err = adj - v
+        taps[i] = taps[n - 1 - i] = v
+        acc += v
+    taps[half] = 256 - 2 * acc
+    return taps
+
+
+def noise_cdf_table(std: float) -> List[int]:
+    """uint32 thresholds T[k] = round(2^32 * P(n <= k)) of n = clamp(rint(N(0, std)), 0, 255), the per-channel
+    value cv2.randn writes into a uint8 matrix; only the entries below 2^32 are kept.  A uniform uint32 u
+    maps to n = #{k : T[k] <= u}, so each n has probability (T[n] - T[n-1]) / 2^32, within 2^-32 of the exact
+    discrete probability."""
+    if not std >= 0:
+        raise ValueError(f"noise_std must be >= 0, got {std}")
+    table = []
+    for k in range(255):
+        cdf = 1.0 if std == 0 else 1.0 - 0.5 * math.erfc((k + 0.5) / (std * math.sqrt(2.0)))
+        t = int(round(cdf * 2.0 ** 32))
+        if t >= 2 ** 32:
+            break
+        table.append(t)
+    return table
+
+
 class TwoViewAugmenter:
     def __init__(self, flags: Optional[Dict[str, bool]] = None, params: Optional[Dict] = None, rng=None,
-                 channels_last: bool = True):
+                 channels_last: bool = True, extended: bool = False, np_rng=None, noise_seed: Optional[int] = None):
         """flags / params: the reference's `augmentation_flags` / `augmentation_params` (missing flags
         are off, missing params take training_config.json's values).  rng: object with `.uniform`
-        (default: Python's global `random`, the generator the reference draws from)."""
+        and `.getrandbits` (default: Python's global `random`, the generator the reference draws from).
+
+        extended=True accepts the reference's other five flags (sobel_filter, cut_out, gaussian_blur,
+        gaussian_noise, color_drop); their draws are interleaved in the reference's order and cut-out's
+        joint index and fill come from `np_rng` (default: the `np.random` module, the global legacy state
+        the reference draws them from).  They are opt-in because two of them cannot match the reference
+        pixel for pixel by construction:
+          * gaussian_noise: the reference draws with cv2.randn from OpenCV's global RNG, a stream this
+            project cannot reproduce.  The noise here has the same distribution (a clamped, rounded normal
+            of std `noise_std`, added with uint8 wrap-around) from a counter-based Philox4x32-10 generator
+            keyed by `noise_seed` (default: torch.initial_seed()) and advanced on every call; it consumes
+            nothing from `rng` or `np_rng`.
+          * sobel_filter: the reference stores the float64 Sobel sum into uint8, which follows x86 NumPy's
+            float-to-uint8 conversion (the value modulo 256); that is what is done here.
+        Blur's 8-bit fixed-point path is a restatement of OpenCV's (see `gaussian_kernel_q8`)."""
         self.flags = dict(RECIPE_FLAGS if flags is None else flags)
         self.params = dict(DEFAULT_PARAMS, **(params or {}))
-        for k in _UNSUPPORTED:
-            if self.flags.get(k):
-                raise NotImplementedError(f"augmentation '{k}' is not part of the GPU recipe "
-                                          "(rotate, crop, random_crop, resize, color_jitter)")
+        self.extended = extended
+        if not extended:
+            for k in _UNSUPPORTED:
+                if self.flags.get(k):
+                    raise NotImplementedError(f"augmentation '{k}' is not part of the GPU recipe "
+                                              "(rotate, crop, random_crop, resize, color_jitter)")
+        elif self.flags.get("sobel_filter") and self.params["sobel_kernel"] != 3:
+            raise ValueError(f"sobel_filter supports sobel_kernel=3 only (the reference config's value), "
+                             f"got {self.params['sobel_kernel']}")
         if not self.flags.get("resize"):
             raise NotImplementedError("the GPU augmenter needs resize=True: crops have per-sample sizes otherwise")
         self.rng = rng if rng is not None else _random
+        self.np_rng = np_rng if np_rng is not None else np.random
         self.channels_last = channels_last
+        self.noise_seed = (torch.initial_seed() if noise_seed is None else int(noise_seed)) & (2 ** 64 - 1)
+        self.noise_call = 0  # Philox counter word: advances on every __call__
+        self._noise_table = None
 
     # ---- host: parameters of one view (sample_augmenter.py:47-129, parameter side)
     def _crop_size(self, joints: Tensor, jitter: Sequence[int], crop_margin: float) -> Tuple[int, int, int, int, int]:
@@ -102,7 +190,17 @@ class TwoViewAugmenter:
         f, p, rng = self.flags, self.params, self.rng
         h_img, w_img = image_hw
         joints = joints25d.detach().to("cpu", torch.float32).clone()
-        view: Dict = {"angle": None, "h": None, "s": None, "a": None, "b": None, "blur_flag": False, "minv": None}
+        view: Dict = {"angle": None, "h": None, "s": None, "a": None, "b": None, "blur_flag": False, "minv": None,
+                      "sobel": False, "cut_out": None, "sigma": None, "ksize": None, "noise": False, "color_drop": False}
+        # augmentations the reference applies first, each decided by one bit drawn only when its flag is on
+        if f.get("sobel_filter") and rng.getrandbits(1):
+            view["sobel"] = True
+        if f.get("cut_out") and rng.getrandbits(1):
+            view["cut_out"] = self._cut_out_box(joints, h_img, w_img)
+        if f.get("gaussian_blur") and rng.getrandbits(1):
+            view["blur_flag"] = True
+            view["sigma"] = rng.uniform(0.1, 2.0)
+            view["ksize"] = blur_ksize(image_hw)
         if f.get("rotate"):
             ox, oy, side, _, _ = self._crop_size(joints, (0, 0), 0.0)
             center = (int(ox + side / 2), int(oy + side / 2))
@@ -133,7 +231,60 @@ class TwoViewAugmenter:
             view["s"] = rng.uniform(*p["sat_factor_range"])
             view["a"] = rng.uniform(*p["value_factor_alpha_range"])
             view["b"] = rng.uniform(*p["value_factor_beta_range"])
+        # ... and last
+        if f.get("gaussian_noise") and rng.getrandbits(1):
+            view["noise"] = True
+        if f.get("color_drop") and rng.getrandbits(1):
+            view["color_drop"] = True
         return view
+
+    def _cut_out_box(self, joints: Tensor, h_img: int, w_img: int) -> Dict:
+        """cut_out_sample + get_random_cut_out_box (sample_augmenter.py:314-373) on the unrotated joints.  The
+        reference centres the ROWS on the joint's x and the COLUMNS on its y; kept.  `a` is a float32 tensor,
+        as there, and `uniform(a, a)` only consumes a draw."""
+        joint = int(self.np_rng.randint(0, 20, 1)[0])  # joint 20 is never picked
+        ratio = self.rng.uniform(*self.params["cut_out_fraction"])
+        d0, d1 = int(h_img * ratio), int(w_img * ratio)
+        a0 = joints[joint, 0] - d0 / 2
+        a1 = joints[joint, 1] - d1 / 2
+        t0 = int(self.rng.uniform(a0, a0))
+        t1 = int(self.rng.uniform(a1, a1))
+        fill = int(np.uint8(self.np_rng.randint(0, 255, 1))[0])
+        r0, r1 = (int(v) for v in np.clip([t0, t0 + d0], 0, h_img))
+        c0, c1 = (int(v) for v in np.clip([t1, t1 + d1], 0, w_img))
+        return {"joint": joint, "ratio": ratio, "rows": (r0, r1), "cols": (c0, c1), "fill": fill}
+
+    @staticmethod
+    def ext_flags(view: Dict) -> int:
+        return ((EXT_SOBEL if view["sobel"] else 0) | (EXT_CUT_OUT if view["cut_out"] is not None else 0)
+                | (EXT_BLUR if view["sigma"] is not None else 0) | (EXT_NOISE if view["noise"] else 0)
+                | (EXT_COLOR_DROP if view["color_drop"] else 0))
+
+    @classmethod
+    def pack_ext(cls, views: List[List[Dict]]):
+        """include/peclr_hip.h's `ext` records [V][B][PECLR_AUG_EXT_INTS] and the Q8 blur taps they point at
+        (per blurred view: the horizontal taps, then the vertical ones)."""
+        recs, coefs = [], []
+        for vs in views:
+            rows = []
+            for w in vs:
+                cut = w["cut_out"]
+                rec = [cls.ext_flags(w), *(cut["rows"] if cut else (0, 0)), *(cut["cols"] if cut else (0, 0)),
+                       cut["fill"] if cut else 0, -1, 0]
+                if w["sigma"] is not None:
+                    rec[6] = len(coefs)
+                    coefs += gaussian_kernel_q8(w["ksize"][0], w["sigma"]) + gaussian_kernel_q8(w["ksize"][1], w["sigma"])
+                rows.append(rec)
+            recs.append(rows)
+        return torch.tensor(recs, dtype=torch.int32), torch.tensor(coefs or [0], dtype=torch.int32)
+
+    def noise_table(self) -> Tuple[Tensor, int]:
+        """`noise_cdf_table` as int32 storage of the uint32 thresholds (at least one element) and its length."""
+        if self._noise_table is None:
+            table = noise_cdf_table(float(self.params["noise_std"]))
+            t = np.array(table or [0], dtype=np.uint32).view(np.int32)
+            self._noise_table = (torch.from_numpy(t.copy()), len(table))
+        return self._noise_table
 
     @staticmethod
     def pack(view: Dict) -> List[float]:
@@ -176,8 +327,26 @@ class TwoViewAugmenter:
         b, h, w, _ = images.shape
         params, views = self.sample_batch(joints25d, (h, w))
         rw, rh = self.params["resize_shape"]
-        out, _ = _capi.augment_views(images, params.to(images.device, non_blocking=True), (rh, rw), IMAGENET_MEAN,
-                                     IMAGENET_STD, self.channels_last)
+        call = self.noise_call
+        self.noise_call += 1
+        ops = 0
+        for vs in views:
+            for view in vs:
+                ops |= self.ext_flags(view)
+        if not ops:  # none of the five drawn anywhere in the batch: exactly the recipe's two launches
+            out, _ = _capi.augment_views(images, params.to(images.device, non_blocking=True), (rh, rw), IMAGENET_MEAN,
+                                         IMAGENET_STD, self.channels_last)
+        else:
+            if ops & EXT_BLUR and max(blur_ksize((h, w))) > MAX_BLUR_KSIZE:
+                raise ValueError(f"gaussian_blur: a {h}x{w} image needs kernels {blur_ksize((h, w))}, "
+                                 f"longer than the device's {MAX_BLUR_KSIZE}")
+            ext, coefs = self.pack_ext(views)
+            table, n_table = self.noise_table()
+            dev = images.device
+            out = _capi.augment_views_ext(images, params.to(dev, non_blocking=True), ext.to(dev, non_blocking=True),
+                                          coefs.to(dev, non_blocking=True), blur_ksize((h, w)),
+                                          table.to(dev, non_blocking=True), n_table, self.noise_seed, call, ops,
+                                          (rh, rw), IMAGENET_MEAN, IMAGENET_STD, self.channels_last)[0]
         # both views are the halves of ONE buffer; `transformed_images` lets the model skip its cat(view1, view2)
         # (hybrid2_model.py:30-32) -- an extra "image" entry, which the reference's consumers of the dict ignore
         batch = {"transformed_images": out, "transformed_image1": out[:b], "transformed_image2": out[b:]}

@@ -14,6 +14,16 @@
 //                             chosen per sample like cv::resize does) -> HSV jitter -> normalised
 //                             float32, NCHW or NHWC
 //
+// The reference's other five augmentations (TwoViewAugmenter(extended=True)) add, only for batches that
+// draw them:
+//   pre_rows_kernel    stage 0: source -> Sobel (low byte of dx + dy) -> cut-out -> [horizontal pass of
+//                      the 8-bit fixed-point Gaussian blur into a 16-bit scratch], per-view sources
+//                      [V][B][H][W][3] u8; samples without a pre-op are copied unchanged
+//   pre_cols_kernel    stage 0: vertical blur pass of the blurred samples, 16-bit scratch -> u8
+//   resize_color_norm_kernel<., true>  stage 2 plus Gaussian noise (Philox4x32-10, integer CDF table,
+//                      uint8 wrap-around add) and colour drop (BGR2GRAY to all three channels)
+// warp_crop_kernel then reads the per-view sources, one launch per view.
+//
 // Work per batch is tiny (B=128: ~40 MB read, ~50 MB written): these kernels exist to take the
 // cv2-on-CPU producer off the critical path, not to approach a roofline.  One thread per pixel,
 // consecutive lanes = consecutive x, so the float32 NHWC / NCHW stores coalesce.
@@ -48,6 +58,154 @@ __device__ __forceinline__ ViewParam load_param(const double* __restrict__ param
 }
 
 __device__ __forceinline__ long long round_ll(double x) { return (long long)rint(x); }  // half to even
+
+// ---- extension record (include/peclr_hip.h PECLR_AUG_EXT_INTS)
+constexpr int NE = PECLR_AUG_EXT_INTS;
+constexpr int PRE_RMAX = (PECLR_AUG_MAX_BLUR_KSIZE - 1) / 2;
+
+struct ExtParam {
+    int flags;
+    int r0, r1, c0, c1;  // cut-out rows [r0, r1), columns [c0, c1)
+    int fill;
+    int coef;            // offset of this view's horizontal then vertical Q8 blur taps
+};
+
+__device__ __forceinline__ ExtParam load_ext(const int* __restrict__ ext, int n) {
+    const int* p = ext + (size_t)n * NE;
+    return ExtParam{p[0], p[1], p[2], p[3], p[4], p[5], p[6]};
+}
+
+// cv::borderInterpolate(BORDER_REFLECT_101) for any offset
+__device__ __forceinline__ int reflect101(int i, int n) {
+    if (n == 1) return 0;
+    const int period = 2 * n - 2;
+    i = abs(i) % period;
+    return i < n ? i : period - i;
+}
+
+// cvtColor(COLOR_BGR2GRAY) on 8-bit data: channel 0 is taken as blue, 14-bit fixed point
+__device__ __forceinline__ int gray_u8(int c0, int c1, int c2) { return (1868 * c0 + 9617 * c1 + 4899 * c2 + 8192) >> 14; }
+
+__device__ __forceinline__ int gray_at(const uint8_t* __restrict__ src, int W, int y, int x) {
+    const uint8_t* s = src + ((size_t)y * W + x) * 3;
+    return gray_u8(s[0], s[1], s[2]);
+}
+
+constexpr int SEG = BX + 2 * PRE_RMAX;  // row positions a block of pre_rows_kernel covers, halo included
+constexpr int COL_ROWS = 8;               // output rows per thread of pre_cols_kernel (sliding window)
+
+// pixel after Sobel and cut-out at image (y, c), packed c0 | c1 << 8 | c2 << 16.  gt: the block's gray tile
+// (rows y-1 .. y+1 at gt[0..2], image column c at gt[.][gi + 1]).
+__device__ __forceinline__ uint32_t pre_packed(const uint8_t* __restrict__ src, int W, int y, int c, const ExtParam& e,
+                                               const uint8_t (*gt)[SEG + 2], int gi) {
+    int v0, v1, v2;
+    if (e.flags & PECLR_AUG_EXT_SOBEL) {
+        // 3x3 Sobel dx + dy of the gray image (BORDER_REFLECT_101), stored as its low byte
+        const int g00 = gt[0][gi], g01 = gt[0][gi + 1], g02 = gt[0][gi + 2];
+        const int g10 = gt[1][gi], g12 = gt[1][gi + 2];
+        const int g20 = gt[2][gi], g21 = gt[2][gi + 1], g22 = gt[2][gi + 2];
+        const int sx = (g02 - g00) + 2 * (g12 - g10) + (g22 - g20);
+        const int sy = (g20 + 2 * g21 + g22) - (g00 + 2 * g01 + g02);
+        v0 = v1 = v2 = (sx + sy) & 255;
+    } else {
+        const uint8_t* s = src + ((size_t)y * W + c) * 3;
+        v0 = s[0], v1 = s[1], v2 = s[2];
+    }
+    if ((e.flags & PECLR_AUG_EXT_CUT_OUT) && y >= e.r0 && y < e.r1 && c >= e.c0 && c < e.c1) v0 = v1 = v2 = e.fill;
+    return (uint32_t)v0 | ((uint32_t)v1 << 8) | ((uint32_t)v2 << 16);
+}
+
+// ---- stage 0, rows: Sobel -> cut-out -> [horizontal blur pass (u8 x Q8, exact in 16 bits)]
+// A block covers BX columns x BY rows.  Row positions x in [x0 - rx, min(x0 + BX, W) + rx) are evaluated at
+// their reflect-101 image column, which always lies in [lo, hi); the gray tile covers [lo - 1, hi + 1).
+__global__ __launch_bounds__(BX* BY) void pre_rows_kernel(const uint8_t* __restrict__ images, int B, int H, int W,
+                                                           const int* __restrict__ ext, const int* __restrict__ coefs,
+                                                           int kx, uint8_t* __restrict__ srcs, uint16_t* __restrict__ tmp) {
+    __shared__ uint8_t gray[BY + 2][SEG + 2];
+    __shared__ uint32_t seg[BY][SEG];
+    __shared__ int taps[2 * PRE_RMAX + 1];
+    const int n = blockIdx.z;  // view * B + sample
+    const ExtParam e = load_ext(ext, n);
+    const uint8_t* src = images + (size_t)(n % B) * H * W * 3;
+    const bool blur = (e.flags & PECLR_AUG_EXT_BLUR) && tmp;  // block-uniform
+    const int rx = blur ? kx >> 1 : 0;
+    const int x0 = blockIdx.x * BX, y0 = blockIdx.y * BY, tid = threadIdx.y * BX + threadIdx.x;
+    const int lo = max(x0 - rx, 0), hi = min(x0 + BX + rx, W);
+    if (blur)
+        for (int i = tid; i < kx; i += BX * BY) taps[i] = coefs[e.coef + i];
+    if (e.flags & PECLR_AUG_EXT_SOBEL) {
+        const int gw = hi - lo + 2;
+        for (int i = tid; i < (BY + 2) * gw; i += BX * BY) {
+            const int j = i / gw, c = i - j * gw;
+            gray[j][c] = (uint8_t)gray_at(src, W, reflect101(y0 - 1 + j, H), reflect101(lo - 1 + c, W));
+        }
+        __syncthreads();
+    }
+    const int y = y0 + threadIdx.y;
+    const int npos = min(BX, W - x0) + 2 * rx;
+    if (y < H) {
+        for (int i = threadIdx.x; i < npos; i += BX) {
+            const int c = reflect101(x0 - rx + i, W);
+            const int gi = min(max(c - lo, 0), hi - lo - 1);  // == c - lo (see above); the clamp only bounds LDS
+            seg[threadIdx.y][i] = pre_packed(src, W, y, c, e, (const uint8_t(*)[SEG + 2])gray[threadIdx.y], gi);
+        }
+    }
+    __syncthreads();
+    const int x = x0 + threadIdx.x;
+    if (x >= W || y >= H) return;
+    if (!blur) {
+        const uint32_t p = seg[threadIdx.y][threadIdx.x];
+        uint8_t* d = srcs + ((size_t)n * H * W + (size_t)y * W + x) * 3;
+        d[0] = (uint8_t)p, d[1] = (uint8_t)(p >> 8), d[2] = (uint8_t)(p >> 16);
+        return;
+    }
+    // channels 0 and 2 share one 32-bit accumulator: each sum is at most 255 * 256 < 2^16
+    uint32_t a02 = 0u, a1 = 0u;
+    for (int k = 0; k < kx; ++k) {
+        const uint32_t t = (uint32_t)taps[k], p = seg[threadIdx.y][threadIdx.x + k];
+        a02 += t * (p & 0x00FF00FFu);
+        a1 += t * ((p >> 8) & 0xFFu);
+    }
+    uint16_t* d = tmp + ((size_t)n * H * W + (size_t)y * W + x) * 3;
+    d[0] = (uint16_t)a02, d[1] = (uint16_t)a1, d[2] = (uint16_t)(a02 >> 16);
+}
+
+// ---- stage 0, columns: vertical blur pass (16-bit x Q8, (acc + 2^15) >> 16) of the blurred samples.
+// Each thread produces COL_ROWS consecutive rows from one pass over the COL_ROWS + ky - 1 input rows.
+__global__ __launch_bounds__(BX* BY) void pre_cols_kernel(int H, int W, const int* __restrict__ ext,
+                                                           const int* __restrict__ coefs, int kx, int ky,
+                                                           const uint16_t* __restrict__ tmp, uint8_t* __restrict__ srcs) {
+    __shared__ int taps[2 * PRE_RMAX + 1];
+    const int n = blockIdx.z;
+    const ExtParam e = load_ext(ext, n);
+    if (!(e.flags & PECLR_AUG_EXT_BLUR)) return;  // block-uniform; pre_rows_kernel wrote this sample already
+    for (int i = threadIdx.y * BX + threadIdx.x; i < ky; i += BX * BY) taps[i] = coefs[e.coef + kx + i];
+    __syncthreads();
+    const int x = blockIdx.x * BX + threadIdx.x, y0 = (blockIdx.y * BY + threadIdx.y) * COL_ROWS;
+    if (x >= W || y0 >= H) return;
+    const int ry = ky >> 1;
+    const uint16_t* t = tmp + (size_t)n * H * W * 3 + (size_t)x * 3;
+    uint32_t acc[COL_ROWS][3] = {};
+    for (int r = 0; r < COL_ROWS + ky - 1; ++r) {
+        const uint16_t* s = t + (size_t)reflect101(y0 - ry + r, H) * W * 3;
+        const uint32_t v0 = s[0], v1 = s[1], v2 = s[2];
+#pragma unroll
+        for (int j = 0; j < COL_ROWS; ++j) {
+            const int k = r - j;
+            if (k >= 0 && k < ky) {
+                const uint32_t c = (uint32_t)taps[k];
+                acc[j][0] += c * v0, acc[j][1] += c * v1, acc[j][2] += c * v2;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < COL_ROWS; ++j) {
+        if (y0 + j >= H) break;
+        uint8_t* d = srcs + ((size_t)n * H * W + (size_t)(y0 + j) * W + x) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) d[c] = (uint8_t)((acc[j][c] + (1u << 15)) >> 16);
+    }
+}
 
 // ---- stage 1: rotation (8-bit warpAffine, bilinear, zero border), evaluated on the crop window only
 __global__ __launch_bounds__(BX* BY) void warp_crop_kernel(const uint8_t* __restrict__ images, int B, int H, int W,
@@ -214,11 +372,56 @@ struct Norm {
     float mean[3], stdv[3];
 };
 
+// ---- stage 2 extension: Gaussian noise and colour drop
+struct PostExt {
+    const int* ext;
+    const uint32_t* table;  // noise CDF thresholds: n = #{k : table[k] <= u}
+    int n_table;
+    uint32_t key0, key1, call;
+};
+
+// Philox4x32-10 (Salmon et al., SC'11)
+__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        if (r) k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
+        c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
+    }
+    return c;
+}
+
+__device__ __forceinline__ int noise_value(const uint32_t* __restrict__ table, int n_table, uint32_t u) {
+    int lo = 0, hi = n_table;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (table[mid] <= u)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// image += clamp(rint(N(0, std)), 0, 255) with uint8 wrap-around, then colour drop
+__device__ __forceinline__ void post_ops(int px[3], const PostExt& pe, int n, int B, int pixel) {
+    const int flags = pe.ext[(size_t)n * NE];
+    if (flags & PECLR_AUG_EXT_NOISE) {
+        // counter (pixel, sample, view, call); output word c is channel c
+        const uint4 r = philox4x32_10(make_uint4((uint32_t)pixel, (uint32_t)(n % B), (uint32_t)(n / B), pe.call), pe.key0, pe.key1);
+        px[0] = (px[0] + noise_value(pe.table, pe.n_table, r.x)) & 255;
+        px[1] = (px[1] + noise_value(pe.table, pe.n_table, r.y)) & 255;
+        px[2] = (px[2] + noise_value(pe.table, pe.n_table, r.z)) & 255;
+    }
+    if (flags & PECLR_AUG_EXT_COLOR_DROP) px[0] = px[1] = px[2] = gray_u8(px[0], px[1], px[2]);
+}
+
 // ---- stage 2: resize -> colour jitter -> ToTensor/Normalize
-template <bool NHWC>
+template <bool NHWC, bool EXT>
 __global__ __launch_bounds__(BX* BY) void resize_color_norm_kernel(const uint8_t* __restrict__ crops, int B, int H, int W,
                                                                     const double* __restrict__ params, int out_h, int out_w,
-                                                                    Norm norm, float* __restrict__ out) {
+                                                                    Norm norm, float* __restrict__ out, PostExt pe) {
     const int n = blockIdx.z;
     const int dx = blockIdx.x * BX + threadIdx.x, dy = blockIdx.y * BY + threadIdx.y;
     if (dx >= out_w || dy >= out_h) return;
@@ -288,6 +491,7 @@ __global__ __launch_bounds__(BX* BY) void resize_color_norm_kernel(const uint8_t
         }
     }
     if (v.color) color_jitter(px, v);
+    if (EXT) post_ops(px, pe, n, B, dy * out_w + dx);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float t = ((float)px[c] / 255.f - norm.mean[c]) / norm.stdv[c];
@@ -326,9 +530,52 @@ extern "C" int peclr_augment_resize_color_norm(const uint8_t* crops, int B, int 
     }
     dim3 grid((out_w + BX - 1) / BX, (out_h + BY - 1) / BY, B * n_views);
     hipStream_t s = static_cast<hipStream_t>(stream);
+    const PostExt none{};
     if (channels_last)
-        hipLaunchKernelGGL((resize_color_norm_kernel<true>), grid, dim3(BX, BY), 0, s, crops, B, H, W, params, out_h, out_w, norm, out);
+        hipLaunchKernelGGL((resize_color_norm_kernel<true, false>), grid, dim3(BX, BY), 0, s, crops, B, H, W, params, out_h, out_w, norm, out, none);
     else
-        hipLaunchKernelGGL((resize_color_norm_kernel<false>), grid, dim3(BX, BY), 0, s, crops, B, H, W, params, out_h, out_w, norm, out);
+        hipLaunchKernelGGL((resize_color_norm_kernel<false, false>), grid, dim3(BX, BY), 0, s, crops, B, H, W, params, out_h, out_w, norm, out, none);
+    return launch_status();
+}
+
+extern "C" int peclr_augment_pre_u8(const uint8_t* images, int B, int H, int W, int n_views, const int* ext,
+                                    const int* coefs, int kx, int ky, uint8_t* srcs, uint16_t* blur_tmp,
+                                    peclr_stream_t stream) {
+    if (!images || !ext || !coefs || !srcs) return PECLR_ERR_NULL;
+    if (B <= 0 || H <= 0 || W <= 0 || n_views <= 0 || (long long)B * n_views > 65535) return PECLR_ERR_SHAPE;
+    if (kx < 1 || ky < 1 || !(kx & 1) || !(ky & 1) || kx > PECLR_AUG_MAX_BLUR_KSIZE || ky > PECLR_AUG_MAX_BLUR_KSIZE)
+        return PECLR_ERR_SHAPE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    dim3 grid((W + BX - 1) / BX, (H + BY - 1) / BY, B * n_views);
+    hipLaunchKernelGGL(pre_rows_kernel, grid, dim3(BX, BY), 0, s, images, B, H, W, ext, coefs, kx, srcs, blur_tmp);
+    if (blur_tmp) {
+        dim3 gcol((W + BX - 1) / BX, (H + BY * COL_ROWS - 1) / (BY * COL_ROWS), B * n_views);
+        hipLaunchKernelGGL(pre_cols_kernel, gcol, dim3(BX, BY), 0, s, H, W, ext, coefs, kx, ky, blur_tmp, srcs);
+    }
+    return launch_status();
+}
+
+extern "C" int peclr_augment_resize_color_norm_ext(const uint8_t* crops, int B, int H, int W, int n_views,
+                                                   const double* params, const int* ext, const uint32_t* noise_table,
+                                                   int n_table, uint64_t noise_seed, uint32_t call, int out_h, int out_w,
+                                                   const float* mean, const float* stdv, int channels_last, float* out,
+                                                   peclr_stream_t stream) {
+    if (!crops || !params || !ext || !noise_table || !mean || !stdv || !out) return PECLR_ERR_NULL;
+    if (B <= 0 || H <= 0 || W <= 0 || n_views <= 0 || out_h <= 0 || out_w <= 0 || (long long)B * n_views > 65535 ||
+        n_table < 0 || n_table > 255)
+        return PECLR_ERR_SHAPE;
+    Norm norm;
+    for (int c = 0; c < 3; ++c) {
+        norm.mean[c] = mean[c];
+        norm.stdv[c] = stdv[c];
+        if (!(norm.stdv[c] > 0.f)) return PECLR_ERR_SHAPE;
+    }
+    const PostExt pe{ext, noise_table, n_table, (uint32_t)noise_seed, (uint32_t)(noise_seed >> 32), call};
+    dim3 grid((out_w + BX - 1) / BX, (out_h + BY - 1) / BY, B * n_views);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (channels_last)
+        hipLaunchKernelGGL((resize_color_norm_kernel<true, true>), grid, dim3(BX, BY), 0, s, crops, B, H, W, params, out_h, out_w, norm, out, pe);
+    else
+        hipLaunchKernelGGL((resize_color_norm_kernel<false, true>), grid, dim3(BX, BY), 0, s, crops, B, H, W, params, out_h, out_w, norm, out, pe);
     return launch_status();
 }
