@@ -652,6 +652,33 @@ int peclr_stem_wgrad_slabs(int N, int Hin, int Win, int fmt);
 int peclr_stem_wgrad(const float* x, const void* dY, int N, int Hin, int Win, int fmt, float* slabs, int n_slabs,
                      peclr_stream_t stream);
 
+/* The fine-tuned 2.5D hand-pose model at evaluation time (reference src/models/rn_25D_wMLPref.py and testing/pred_fh.py):
+ * the crop and the head of the two-pass crop -> predict -> re-crop loop.  Host side: peclr_amd/pose.py.
+ *
+ * peclr_pose_crop_u8: fh_utils.preprocess for a batch.  images [B][H][W][3] u8 RGB, T [B][3][3] float64 forward matrices:
+ *   out [B][S][S][3] float32 (the [B,3,S,S] channels_last tensor the stem reads) = table[c][warpAffine(img, T[:2], (S, S))],
+ *   8-bit INTER_LINEAR with BORDER_CONSTANT 0 (the reference's borderValue saturates to 0 on u8).  table [3][256] float32:
+ *   the normalisation of each channel value.  K [B][3][3] float64 (may be NULL): k_out [B][3][3] float32 = float32(T @ K).
+ * peclr_pose_head_f32: pooled features feat [B][n_feat = 2048] -> the model's head, one launch.  fc_w [64][2048], fc_b [64];
+ *   mlp: host array of PECLR_POSE_MLP_TENSORS device pointers -- zroot_ref.zroot_ref.{0.weight, 0.bias, 1.weight, 1.bias,
+ *   1.running_mean, 1.running_var, 3.weight, 3.bias, 4.weight, 4.bias, 4.running_mean, 4.running_var, 6.weight, 6.bias};
+ *   bn_eps1 / bn_eps2: the eps of the two BatchNorm1d.  K [B or 1][3][3] float32 (k_per_sample 0: one matrix broadcast).
+ *   Out: out64 [B][64] (the fc output with the root's zrel zeroed: kp25d = out64[:, :63]), kp3d [B][21][3].
+ *   Pass 1 (T1 != NULL): T2 [B][3][3] float64 = the re-crop matrix of pred() from kp2d and T1 [B][3][3], crop size S;
+ *     status[b] = PECLR_POSE_STATUS_NO_BBOX (T2 NaN) when every x or every y of kp2d is NaN, else 0.
+ *   Pass 2 (scale != NULL): fh [B][21][3] float64 = FreiHAND joints (palm -> wrist, joint order) times scale[b];
+ *     PECLR_POSE_STATUS_NAN is OR-ed into status[b] when one is NaN, status[b] is left as it is otherwise.
+ *   At most one of the two epilogues per launch; without either, status is not touched. */
+#define PECLR_POSE_MLP_TENSORS 14
+#define PECLR_POSE_STATUS_NO_BBOX 1
+#define PECLR_POSE_STATUS_NAN 2
+int peclr_pose_crop_u8(const uint8_t* images, int B, int H, int W, const double* T, const double* K, const float* table, int S,
+                       float* out, float* k_out, peclr_stream_t stream);
+int peclr_pose_head_f32(const float* feat, int B, int n_feat, const float* fc_w, const float* fc_b, const float* const* mlp,
+                        float bn_eps1, float bn_eps2, const float* K, int k_per_sample, float eps, float* out64, float* kp3d,
+                        const double* T1, double* T2, int S, const double* scale, double* fh, int* status,
+                        peclr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,9 @@ SIGNATURES = {
     "peclr_lars_adam_update_amp_f32": (c_int, [_P, _P, c_int, _P, _P, _P, _P, c_int, _P, _P, _P, _P, c_int, c_double,
                                                c_double, c_float, c_int, c_float, c_float, c_int, _P, _P]),
     "peclr_amp_update": (c_int, [_P, c_float, c_float, c_int, _P]),
+    "peclr_pose_crop_u8": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P]),
+    "peclr_pose_head_f32": (c_int, [_P, c_int, c_int, _P, _P, _P, c_float, c_float, _P, c_int, c_float, _P, _P, _P, _P, c_int,
+                                    _P, _P, _P, _P]),
 }
 
 
@@ -1470,3 +1473,74 @@ def augment_views_ext(images: torch.Tensor, params: torch.Tensor, ext: torch.Ten
                                                        int(channels_last), out.data_ptr(), stream)
         _check(rc, "peclr_augment_resize_color_norm")
     return out, srcs, crops
+
+
+# ------------------------------------------------------------------ 2.5D hand-pose model at evaluation time (peclr_amd/pose.py)
+POSE_MLP_TENSORS = 14
+POSE_STATUS_NO_BBOX, POSE_STATUS_NAN = 1, 2
+
+
+def _mat_ptr(t, b, dtype, what, broadcast=False):
+    if t is None:
+        return None
+    ok = t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.dim() == 3 and tuple(t.shape[1:]) == (3, 3)
+    if not ok or not (t.shape[0] == b or (broadcast and t.shape[0] == 1)):
+        raise PeclrHipError(f"pose: {what} must be a contiguous [{b},3,3] {dtype} HIP tensor, got {t.dtype} {tuple(t.shape)} "
+                            f"on {t.device} (peclr_amd has no CPU path)")
+    return t.data_ptr()
+
+
+def pose_crop(images: torch.Tensor, T: torch.Tensor, K: Optional[torch.Tensor], table: torch.Tensor, size: int):
+    """images [B,H,W,3] uint8, T [B,3,3] float64 forward matrices, K [B,3,3] float64 or None, table [3,256] float32 ->
+    (float32 [B,3,size,size] channels_last, float32 K' = T @ K [B,3,3] or None).  One launch."""
+    if not images.is_cuda or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3 or not images.is_contiguous():
+        raise PeclrHipError(f"pose_crop: images must be a contiguous [B,H,W,3] uint8 HIP tensor, got {images.dtype} "
+                            f"{tuple(images.shape)} on {images.device} (peclr_amd has no CPU path)")
+    b, h, w, _ = images.shape
+    tp, kp = _mat_ptr(T, b, torch.float64, "T"), _mat_ptr(K, b, torch.float64, "K")
+    if tuple(table.shape) != (3, 256):
+        raise PeclrHipError("pose_crop: table must be [3,256] float32")
+    out = torch.empty((b, 3, size, size), device=images.device, dtype=torch.float32, memory_format=torch.channels_last)
+    k_out = torch.empty((b, 3, 3), device=images.device, dtype=torch.float32) if K is not None else None
+    with _timed("pose_crop", b * h * w * 3 + b * size * size * 12):
+        rc = lib().peclr_pose_crop_u8(images.data_ptr(), b, h, w, tp, kp, _ptr(table, what="pose_crop table"), size,
+                                      out.data_ptr(), k_out.data_ptr() if k_out is not None else None, _stream())
+    _check(rc, "peclr_pose_crop_u8")
+    return out, k_out
+
+
+def pose_head(feat: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, mlp, bn_eps, K: torch.Tensor, eps: float,
+              T1: Optional[torch.Tensor] = None, size: int = 0, scale: Optional[torch.Tensor] = None,
+              status: Optional[torch.Tensor] = None):
+    """Pooled features [B,2048] -> (out64 [B,64], kp3d [B,21,3], T2 [B,3,3] float64 or None, fh [B,21,3] float64 or None,
+    status [B] int32).  mlp: the 14 tensors of zroot_ref.zroot_ref in the order of include/peclr_hip.h; K [B or 1,3,3]
+    float32.  Pass 1: T1 given (T2 out, status written); pass 2: scale [B] float64 given (fh out, NaN bit OR-ed into
+    `status`, zeros when not given).  One launch."""
+    if feat.dim() != 2:
+        raise PeclrHipError(f"pose_head: features must be [B,2048], got {tuple(feat.shape)}")
+    b, nf = feat.shape
+    fp = _ptr(feat, what="pose_head features")
+    kp = _mat_ptr(K, b, torch.float32, "K", broadcast=True)
+    if len(mlp) != POSE_MLP_TENSORS:
+        raise PeclrHipError(f"pose_head: {POSE_MLP_TENSORS} MLP tensors expected, got {len(mlp)}")
+    mlp_arr = (c_void_p * POSE_MLP_TENSORS)(*[_ptr(t, what="pose_head MLP tensor") for t in mlp])
+    dev = feat.device
+    out64 = torch.empty((b, 64), device=dev, dtype=torch.float32)
+    kp3d = torch.empty((b, 21, 3), device=dev, dtype=torch.float32)
+    T2 = torch.empty((b, 3, 3), device=dev, dtype=torch.float64) if T1 is not None else None
+    fh = torch.empty((b, 21, 3), device=dev, dtype=torch.float64) if scale is not None else None
+    if status is None:
+        status = torch.zeros((b,), device=dev, dtype=torch.int32)
+    if scale is not None and (tuple(scale.shape) != (b,)):
+        raise PeclrHipError(f"pose_head: scale must be [{b}] float64")
+    if tuple(status.shape) != (b,):
+        raise PeclrHipError(f"pose_head: status must be [{b}] int32")
+    with _timed("pose_head", 4 * b * (nf + 64 + 63 + 64) + 4 * 64 * nf):
+        rc = lib().peclr_pose_head_f32(fp, b, nf, _ptr(fc_w, what="pose_head fc weight"), _ptr(fc_b, what="pose_head fc bias"),
+                                       ctypes.cast(mlp_arr, c_void_p), float(bn_eps[0]), float(bn_eps[1]), kp,
+                                       int(K.shape[0] != 1 or b == 1), float(eps), out64.data_ptr(), kp3d.data_ptr(),
+                                       _mat_ptr(T1, b, torch.float64, "T1"), T2.data_ptr() if T2 is not None else None, int(size),
+                                       _ptr(scale, torch.float64, "pose_head scale"), fh.data_ptr() if fh is not None else None,
+                                       _ptr(status, torch.int32, "pose_head status"), _stream())
+    _check(rc, "peclr_pose_head_f32")
+    return out64, kp3d, T2, fh, status

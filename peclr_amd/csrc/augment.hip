@@ -28,6 +28,7 @@
 // cv2-on-CPU producer off the critical path, not to approach a roofline.  One thread per pixel,
 // consecutive lanes = consecutive x, so the float32 NHWC / NCHW stores coalesce.
 #include "common.hpp"
+#include "warp_u8.hpp"
 
 #pragma clang fp contract(off)  // products and sums round separately, as in the scalar restatement
 
@@ -223,33 +224,10 @@ __global__ __launch_bounds__(BX* BY) void warp_crop_kernel(const uint8_t* __rest
         dst[0] = s[0], dst[1] = s[1], dst[2] = s[2];
         return;
     }
-    // 10-bit fixed-point source coordinates, rounded to 1/32 pixel
-    const long long xf = (round_ll((v.minv[1] * y + v.minv[2]) * 1024.0) + 16 + round_ll(v.minv[0] * x * 1024.0)) >> 5;
-    const long long yf = (round_ll((v.minv[4] * y + v.minv[5]) * 1024.0) + 16 + round_ll(v.minv[3] * x * 1024.0)) >> 5;
-    const long long sx = xf >> 5, sy = yf >> 5;
-    const int fx = (int)(xf & 31), fy = (int)(yf & 31);
-    const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
-    const bool x0ok = sx >= 0 && sx < W, x1ok = sx + 1 >= 0 && sx + 1 < W;
-    const bool y0ok = sy >= 0 && sy < H, y1ok = sy + 1 >= 0 && sy + 1 < H;
-    int acc[3] = {0, 0, 0};
-    if (y0ok && x0ok) {
-        const uint8_t* s = src + ((size_t)sy * W + sx) * 3;
-        acc[0] += s[0] * w00, acc[1] += s[1] * w00, acc[2] += s[2] * w00;
-    }
-    if (y0ok && x1ok) {
-        const uint8_t* s = src + ((size_t)sy * W + sx + 1) * 3;
-        acc[0] += s[0] * w01, acc[1] += s[1] * w01, acc[2] += s[2] * w01;
-    }
-    if (y1ok && x0ok) {
-        const uint8_t* s = src + ((size_t)(sy + 1) * W + sx) * 3;
-        acc[0] += s[0] * w10, acc[1] += s[1] * w10, acc[2] += s[2] * w10;
-    }
-    if (y1ok && x1ok) {
-        const uint8_t* s = src + ((size_t)(sy + 1) * W + sx + 1) * 3;
-        acc[0] += s[0] * w11, acc[1] += s[1] * w11, acc[2] += s[2] * w11;
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) dst[c] = (uint8_t)((acc[c] + (1 << 14)) >> 15);
+    // 10-bit fixed-point source coordinates, rounded to 1/32 pixel (warp_u8.hpp)
+    int px[3];
+    warp_bilinear_u8(src, H, W, v.minv, x, y, px);
+    dst[0] = (uint8_t)px[0], dst[1] = (uint8_t)px[1], dst[2] = (uint8_t)px[2];
 }
 
 // ---- stage 2 helpers: cv::resize(INTER_AREA) paths
