@@ -453,17 +453,34 @@ class _BnBwdFuse(ctypes.Structure):
                 ("relu", c_int), ("partial", c_void_p)]
 
 
-def _bn_bwd_fuse(bn_bwd, m: int, n: int, tile_rows: int, groups: int = 1, dtype=torch.float32, row_blocks: int = 0):
-    """bn_bwd = (x [.., n] NHWC/2-D fp32 of m rows, save [2, n], ss [2, n], mask or None, relu) of the BatchNorm layer whose
-    incoming gradient this GEMM produces -> (struct, partial [2 * n_split, n], n_split); keeps the tensors alive."""
+def _byref(struct):
+    return ctypes.byref(struct) if struct is not None else None
+
+
+def _epilogue(who: str, m: int, n: int, tile_rows: int, stat_shift, bn_bwd, device, groups: int = 1, dtype=torch.float32,
+              row_blocks: int = 0):
+    """The fused epilogue of a packed-operand GEMM / convolution `who` whose [m, n] output is computed in blocks of `tile_rows` rows
+    -> (partial, n_split, fuse).  n_split: `row_blocks` where the kernel reports its own count, else the row blocks of each of
+    `groups` equal row sets.
+    stat_shift (fp32 [n]): the output's BatchNorm statistics -- partial [2 n_split + 1, n] in peclr_bn2d_stats' layout (the shift in
+    the last row), fuse None;
+    else bn_bwd = (x, save [2, n], ss [2, n], mask or None, relu) of the BatchNorm layer whose incoming gradient the output is (x:
+    that layer's input, m * n elements of `dtype`) -- partial [2 n_split, n] in peclr_bn2d_bwd_reduce's layout, fuse the
+    peclr_bn_bwd_fuse to pass by reference (`_byref`);
+    neither: (None, 0, None)."""
+    if stat_shift is None and bn_bwd is None:
+        return None, 0, None
+    ns = row_blocks or groups * ((m // groups + tile_rows - 1) // tile_rows)
+    if stat_shift is not None:
+        if stat_shift.numel() != n:
+            raise PeclrHipError(f"{who}: stat_shift has {stat_shift.numel()} entries for {n} columns")
+        return torch.empty((2 * ns + 1, n), device=device, dtype=torch.float32), ns, None
     x, save, ss, mask, relu = bn_bwd
     if x.dtype != dtype or x.numel() != m * n or not x.is_cuda:
         raise PeclrHipError(f"bn backward fusion: layer input of {x.numel()} {x.dtype} elements for a {dtype} [{m}, {n}] gradient")
-    ns = row_blocks or groups * ((m // groups + tile_rows - 1) // tile_rows)       # (groups: row blocks of each of several equal row sets)
-    partial = torch.empty((2 * ns, n), device=x.device, dtype=torch.float32)
-    st = _BnBwdFuse(x.data_ptr(), save[0].data_ptr(), save[1].data_ptr(), _ptr(ss), _ptr(mask, torch.int32, "relu mask"), int(relu),
-                    partial.data_ptr())
-    return st, partial, ns
+    partial = torch.empty((2 * ns, n), device=device, dtype=torch.float32)
+    return partial, ns, _BnBwdFuse(x.data_ptr(), save[0].data_ptr(), save[1].data_ptr(), _ptr(ss), _ptr(mask, torch.int32, "relu mask"),
+                                   int(relu), partial.data_ptr())
 
 
 class X6Planes:
@@ -547,7 +564,7 @@ def gemm_x6p(a: torch.Tensor, planes: torch.Tensor, n: int, addend: Optional[tor
     bf16 matrix cores, the weight operand split once per step (peclr_gemm_x6p_f32).
     stat_shift (fp32 [n]): also return the training-mode BatchNorm statistics of C as `(partial, n_split)` in the layout
     of peclr_bn2d_stats (sums of (C - shift) and its square per row block; the shift in the last row) -> (C, partial, n_split).
-    bn_bwd (see `_bn_bwd_fuse`): C is the gradient arriving at that BatchNorm layer; also return its backward reduction
+    bn_bwd (see `_epilogue`): C is the gradient arriving at that BatchNorm layer; also return its backward reduction
     `(partial, n_split)` in peclr_bn2d_bwd_reduce's layout -> (C, partial, n_split).
     addend_s2 = (H, W): the rows are the pixels of H x W images and `addend` [M / 4, n] holds every second pixel only (the
     compact input gradient of a 1x1 / stride-2 convolution): added at the even (h, w) rows (peclr_gemm_x6p_s2add_f32).
@@ -557,7 +574,6 @@ def gemm_x6p(a: torch.Tensor, planes: torch.Tensor, n: int, addend: Optional[tor
     m, k = a.shape
     add_rows = m if addend_s2 is None else m // 4
     pst, wb = _pair_arg(pair, "gemm_x6p")
-    pref = ctypes.byref(pst) if pst is not None else None
     if planes.dtype != torch.uint8 or planes.numel() != wb * ((n + 127) // 128 * 128) * k or (addend is not None and tuple(addend.shape) != (add_rows, n)):
         raise PeclrHipError(f"gemm_x6p: A {tuple(a.shape)}, planes of {planes.numel()} bytes for B_t[{n}, {k}]")
     if addend_s2 is not None and (addend is None or stat_shift is not None or addend_mask is not None):
@@ -566,32 +582,23 @@ def gemm_x6p(a: torch.Tensor, planes: torch.Tensor, n: int, addend: Optional[tor
                                     or addend_mask.numel() != m * (n // 32) or not addend_mask.is_contiguous()):
         raise PeclrHipError("gemm_x6p: addend_mask is the int32 [M, n / 32] bit mask of a dense addend (no statistics output)")
     out = torch.empty((m, n), device=a.device, dtype=torch.float32)
-    partial, ns, fuse = None, 0, None
     tile_rows = tile_rows or _X6P_TILE_ROWS
     if stat_shift is not None or bn_bwd is not None:
         tile_rows = tile_rows or lib().peclr_gemm_x6p_tile_rows(m, n, k)
-    if stat_shift is not None:
-        if stat_shift.numel() != n:
-            raise PeclrHipError(f"gemm_x6p: stat_shift has {stat_shift.numel()} entries for {n} columns")
-        ns = (m + tile_rows - 1) // tile_rows
-        partial = torch.empty((2 * ns + 1, n), device=a.device, dtype=torch.float32)
-    elif bn_bwd is not None:
-        fuse, partial, ns = _bn_bwd_fuse(bn_bwd, m, n, tile_rows)
+    partial, ns, fuse = _epilogue("gemm_x6p", m, n, tile_rows, stat_shift, bn_bwd, a.device)
     add_elems = 0 if addend is None else addend.numel() + (0 if addend_mask is None else addend_mask.numel())
     with _timed(tag, 4 * (m * k + m * n + add_elems + (m * n if fuse is not None else 0)) + wb * k * n, 2 * m * n * k,
                 kernel="gemm_x6p_kernel" if pst is None else "gemm_x6p_kernel<pair>"):
         if addend_mask is not None:
             rc = lib().peclr_gemm_x6p_maskadd_f32(m, n, k, _ptr(a), k, _ptr(planes, torch.uint8), out.data_ptr(), n, _ptr(addend), n,
-                                                  _ptr(addend_mask, torch.int32), tile_rows,
-                                                  ctypes.byref(fuse) if fuse is not None else None, pref, _stream())
+                                                  _ptr(addend_mask, torch.int32), tile_rows, _byref(fuse), _byref(pst), _stream())
         elif addend_s2 is not None:
             rc = lib().peclr_gemm_x6p_s2add_f32(m, n, k, _ptr(a), k, _ptr(planes, torch.uint8), out.data_ptr(), n, _ptr(addend), n,
-                                                int(addend_s2[0]), int(addend_s2[1]), tile_rows,
-                                                ctypes.byref(fuse) if fuse is not None else None, pref, _stream())
+                                                int(addend_s2[0]), int(addend_s2[1]), tile_rows, _byref(fuse), _byref(pst), _stream())
         else:
             rc = lib().peclr_gemm_x6p_f32(m, n, k, _ptr(a), k, _ptr(planes, torch.uint8), out.data_ptr(), n, _ptr(addend), n,
                                           tile_rows, _ptr(stat_shift), partial.data_ptr() if stat_shift is not None else None,
-                                          ctypes.byref(fuse) if fuse is not None else None, pref, _stream())
+                                          _byref(fuse), _byref(pst), _stream())
     _check(rc, "peclr_gemm_x6p_maskadd_f32" if addend_mask is not None else "peclr_gemm_x6p_s2add_f32" if addend_s2 is not None
            else "peclr_gemm_x6p_f32")
     return out if partial is None else (out, partial, ns)
@@ -622,22 +629,15 @@ def conv3x3_x6p(x: torch.Tensor, planes: torch.Tensor, cout: int, flip: bool = F
         raise PeclrHipError(f"conv3x3_x6p: planes of {planes.numel()} bytes for [{cout}, 9 * {cin}]")
     y = torch.empty((nb, cout, h, w), device=x.device, dtype=torch.float32, memory_format=torch.channels_last)
     m = nb * h * w
-    partial, ns, fuse = None, 0, None
     if stat_shift is not None or bn_bwd is not None:
         tile_rows = tile_rows or lib().peclr_gemm_x6p_tile_rows(m, cout, 9 * cin)
-    if stat_shift is not None:
-        ns = (m + tile_rows - 1) // tile_rows
-        partial = torch.empty((2 * ns + 1, cout), device=x.device, dtype=torch.float32)
-    elif bn_bwd is not None:
-        fuse, partial, ns = _bn_bwd_fuse(bn_bwd, m, cout, tile_rows)
+    partial, ns, fuse = _epilogue("conv3x3_x6p", m, cout, tile_rows, stat_shift, bn_bwd, x.device)
     ap = _nhwc_ptr(addend, "conv3x3 addend", torch.float32) if addend is not None else None
     with _timed(tag, 4 * (m * cin + (2 if addend is not None else 1) * m * cout + (m * cout if fuse is not None else 0)) + 9 * wb * cin * cout,
                 18 * m * cin * cout, kernel="gemm_x6p_kernel (3x3)" if pst is None else "gemm_x6p_kernel<pair> (3x3)"):
         rc = lib().peclr_conv3x3_x6p_f32(nb, h, w, cin, cout, xp, _ptr(planes, torch.uint8), y.data_ptr(), ap, int(flip), tile_rows,
                                          _CONV3X3_VARIANT if variant is None else int(variant), _zeros(x.device).data_ptr(), _ptr(stat_shift),
-                                         partial.data_ptr() if stat_shift is not None else None,
-                                         ctypes.byref(fuse) if fuse is not None else None,
-                                         ctypes.byref(pst) if pst is not None else None, _stream())
+                                         partial.data_ptr() if stat_shift is not None else None, _byref(fuse), _byref(pst), _stream())
     _check(rc, "peclr_conv3x3_x6p_f32")
     return y if partial is None else (y, partial, ns)
 
@@ -655,15 +655,13 @@ def conv3x3_s2_dgrad_x6p(gy: torch.Tensor, planes: torch.Tensor, cin: int, tag: 
         raise PeclrHipError(f"conv3x3_s2_dgrad_x6p: planes of {planes.numel()} bytes for [{cin}, 9 * {cout}]")
     dx = torch.empty((nb, cin, 2 * ho, 2 * wo), device=gy.device, dtype=torch.float32, memory_format=torch.channels_last)
     mc = nb * ho * wo
-    partial, ns, fuse = None, 0, None
     if bn_bwd is not None:
         tile_rows = tile_rows or lib().peclr_gemm_x6p_tile_rows(mc, cin, 4 * cout)
-        fuse, partial, ns = _bn_bwd_fuse(bn_bwd, 4 * mc, cin, tile_rows, groups=4)
+    partial, ns, fuse = _epilogue("conv3x3_s2_dgrad_x6p", 4 * mc, cin, tile_rows, None, bn_bwd, gy.device, groups=4)
     with _timed(tag, 4 * (mc * cout + 4 * mc * cin * (2 if fuse is not None else 1)) + 9 * wb * cin * cout, 18 * mc * cin * cout,
                 kernel="gemm_x6p_kernel (3x3)" if pst is None else "gemm_x6p_kernel<pair> (3x3)"):
         rc = lib().peclr_conv3x3_s2_dgrad_x6p_f32(nb, ho, wo, cout, cin, gp, _ptr(planes, torch.uint8), dx.data_ptr(), tile_rows,
-                                                  _zeros(gy.device).data_ptr(), ctypes.byref(fuse) if fuse is not None else None,
-                                                  ctypes.byref(pst) if pst is not None else None, _stream())
+                                                  _zeros(gy.device).data_ptr(), _byref(fuse), _byref(pst), _stream())
     _check(rc, "peclr_conv3x3_s2_dgrad_x6p_f32")
     return dx if partial is None else (dx, partial, ns)
 
@@ -680,18 +678,15 @@ def conv_s2_x6p(x: torch.Tensor, planes: torch.Tensor, cout: int, taps: int, tag
         raise PeclrHipError(f"conv_s2_x6p: planes of {planes.numel()} bytes for [{cout}, {taps} * {cin}], input {h} x {w}")
     y = torch.empty((nb, cout, h // 2, w // 2), device=x.device, dtype=torch.float32, memory_format=torch.channels_last)
     m = nb * (h // 2) * (w // 2)
-    partial, ns = None, 0
     if stat_shift is not None:
         tile_rows = tile_rows or lib().peclr_gemm_x6p_tile_rows(m, cout, taps * cin)
-        ns = (m + tile_rows - 1) // tile_rows
-        partial = torch.empty((2 * ns + 1, cout), device=x.device, dtype=torch.float32)
+    partial, ns, _ = _epilogue("conv_s2_x6p", m, cout, tile_rows, stat_shift, None, x.device)
     with _timed(tag, 4 * (nb * h * w * cin + m * cout) + wb * taps * cin * cout, 2 * m * taps * cin * cout,
                 kernel="gemm_x6p_kernel (stride 2)" if pst is None else "gemm_x6p_kernel<pair> (stride 2)"):
         rc = lib().peclr_conv_s2_x6p_f32(nb, h, w, cin, cout, taps, xp, _ptr(planes, torch.uint8), y.data_ptr(), tile_rows,
-                                         _zeros(x.device).data_ptr(), _ptr(stat_shift), _ptr(partial),
-                                         ctypes.byref(pst) if pst is not None else None, _stream())
+                                         _zeros(x.device).data_ptr(), _ptr(stat_shift), _ptr(partial), _byref(pst), _stream())
     _check(rc, "peclr_conv_s2_x6p_f32")
-    return y if stat_shift is None else (y, partial, ns)
+    return y if partial is None else (y, partial, ns)
 
 
 def gemm_x6_tn(a: torch.Tensor, b: torch.Tensor, tag: str = "gemm_x6_tn") -> torch.Tensor:
@@ -838,16 +833,9 @@ def gemm_h(a: torch.Tensor, planes: torch.Tensor, n: int, addend: Optional[torch
                                     or addend_mask.numel() != m * (n // 32) or not addend_mask.is_contiguous()):
         raise PeclrHipError("gemm_h: addend_mask is the int32 [M, n / 32] bit mask of a dense addend (no statistics output)")
     out = torch.empty((m, n), device=a.device, dtype=a.dtype)
-    partial, ns, fuse = None, 0, None
     if stat_shift is not None or bn_bwd is not None:
         tile_rows = tile_rows or lib().peclr_conv_h_tile_rows(m, n)
-    if stat_shift is not None:
-        if stat_shift.numel() != n:
-            raise PeclrHipError(f"gemm_h: stat_shift has {stat_shift.numel()} entries for {n} columns")
-        ns = (m + tile_rows - 1) // tile_rows
-        partial = torch.empty((2 * ns + 1, n), device=a.device, dtype=torch.float32)
-    elif bn_bwd is not None:
-        fuse, partial, ns = _bn_bwd_fuse(bn_bwd, m, n, tile_rows, dtype=a.dtype)
+    partial, ns, fuse = _epilogue("gemm_h", m, n, tile_rows, stat_shift, bn_bwd, a.device, dtype=a.dtype)
     add_elems = 0 if addend is None else addend.numel()
     mask_bytes = 0 if addend_mask is None else 4 * addend_mask.numel()
     with _timed(tag, 2 * (m * k + m * n + add_elems + (m * n if fuse is not None else 0) + k * n) + mask_bytes, 2 * m * n * k,
@@ -856,8 +844,7 @@ def gemm_h(a: torch.Tensor, planes: torch.Tensor, n: int, addend: Optional[torch
                                 addend.data_ptr() if addend is not None else None, n,
                                 int(addend_s2[0]) if addend_s2 is not None else 0, int(addend_s2[1]) if addend_s2 is not None else 0,
                                 _ptr(addend_mask, torch.int32), tile_rows, _ptr(stat_shift),
-                                partial.data_ptr() if stat_shift is not None else None,
-                                ctypes.byref(fuse) if fuse is not None else None, _stream())
+                                partial.data_ptr() if stat_shift is not None else None, _byref(fuse), _stream())
     _check(rc, "peclr_gemm_h")
     return out if partial is None else (out, partial, ns)
 
@@ -876,21 +863,17 @@ def conv_h(x: torch.Tensor, planes: torch.Tensor, cout: int, taps: int = 9, stri
     ho, wo = h // stride, w // stride
     y = torch.empty((nb, cout, ho, wo), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
     m = nb * ho * wo
-    partial, ns, fuse = None, 0, None
+    ns = 0
     if stat_shift is not None or bn_bwd is not None:
         ns = lib().peclr_conv_h_row_blocks(nb, h, w, cout, taps, stride, tile_rows)     # (tile_rows 0: the library's choice)
         if ns <= 0:
             raise PeclrHipError(f"conv_h: no launch for tile_rows = {tile_rows} at {h} x {w}, taps {taps}, stride {stride}")
-    if stat_shift is not None:
-        partial = torch.empty((2 * ns + 1, cout), device=x.device, dtype=torch.float32)
-    elif bn_bwd is not None:
-        fuse, partial, ns = _bn_bwd_fuse(bn_bwd, m, cout, tile_rows, dtype=x.dtype, row_blocks=ns)
+    partial, ns, fuse = _epilogue("conv_h", m, cout, tile_rows, stat_shift, bn_bwd, x.device, dtype=x.dtype, row_blocks=ns)
     with _timed(tag, 2 * (nb * h * w * cin + m * cout * (2 if fuse is not None else 1) + taps * cin * cout), 2 * m * taps * cin * cout,
                 kernel="conv_h_kernel (3x3)" if taps == 9 else "conv_h_kernel (stride 2)"):
         rc = lib().peclr_conv_h(io, nb, h, w, cin, cout, taps, stride, xp, _ptr(planes, torch.uint8), y.data_ptr(), int(flip), tile_rows,
                                 _hzeros(x.device, x.dtype).data_ptr(), _ptr(stat_shift),
-                                partial.data_ptr() if stat_shift is not None else None,
-                                ctypes.byref(fuse) if fuse is not None else None, _stream())
+                                partial.data_ptr() if stat_shift is not None else None, _byref(fuse), _stream())
     _check(rc, "peclr_conv_h")
     return y if partial is None else (y, partial, ns)
 
@@ -948,18 +931,15 @@ def conv3x3_s2_dgrad_h(gy: torch.Tensor, planes: torch.Tensor, cin: int, tag: st
     _h_planes_ok(planes, cin, 9 * cout, "conv3x3_s2_dgrad_h")
     dx = torch.empty((nb, cin, 2 * ho, 2 * wo), device=gy.device, dtype=gy.dtype, memory_format=torch.channels_last)
     mc = nb * ho * wo
-    partial, ns, fuse = None, 0, None
     if bn_bwd is not None:
         tile_rows = tile_rows or lib().peclr_conv_h_tile_rows(mc, cin)
-        fuse, partial, ns = _bn_bwd_fuse(bn_bwd, 4 * mc, cin, tile_rows, groups=4, dtype=gy.dtype)
+    partial, ns, fuse = _epilogue("conv3x3_s2_dgrad_h", 4 * mc, cin, tile_rows, None, bn_bwd, gy.device, groups=4, dtype=gy.dtype)
     with _timed(tag, 2 * (mc * cout + 4 * mc * cin * (2 if fuse is not None else 1) + 9 * cin * cout), 18 * mc * cin * cout,
                 kernel="conv_h_kernel (3x3)"):
         rc = lib().peclr_conv3x3_s2_dgrad_h(io, nb, ho, wo, cout, cin, gp, _ptr(planes, torch.uint8), dx.data_ptr(), tile_rows,
-                                            _hzeros(gy.device, gy.dtype).data_ptr(), ctypes.byref(fuse) if fuse is not None else None,
-                                            _stream())
+                                            _hzeros(gy.device, gy.dtype).data_ptr(), _byref(fuse), _stream())
     _check(rc, "peclr_conv3x3_s2_dgrad_h")
     return dx if partial is None else (dx, partial, ns)
-
 
 
 # ------------------------------------------------------------------ backbone glue: BN2d (+add) (+ReLU), NHWC
@@ -1002,11 +982,7 @@ def stem_conv(x: torch.Tensor, planes: "StemPlanes", stat_shift: Optional[torch.
     out_dtype = {v: k for k, v in STEM_FMT.items()}[planes.fmt]
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     y = torch.empty((n, 64, ho, wo), device=x.device, dtype=out_dtype, memory_format=torch.channels_last)
-    partial = None
-    if stat_shift is not None:
-        if stat_shift.numel() != 64:
-            raise PeclrHipError("stem_conv: stat_shift has 64 entries")
-        partial = torch.empty((2 * ns + 1, 64), device=x.device, dtype=torch.float32)
+    partial, ns, _ = _epilogue("stem_conv", n * ho * wo, 64, 0, stat_shift, None, x.device, row_blocks=ns)     # (one block per workgroup)
     e = y.element_size()
     k_mfma = 14 * 16                                        # the contraction the matrix cores run (147 padded to 224)
     with _timed(tag, 4 * x.numel() + e * y.numel() + planes.planes.numel(), 2 * n * ho * wo * 64 * 147,

@@ -102,8 +102,6 @@ def checkpoint_block(run, x: Tensor) -> Tensor:
     return run(x)
 
 
-
-
 # gradient tensors whose producer (an input-gradient GEMM) already reduced them against the BatchNorm layer they arrive at:
 # data_ptr -> (token of that layer's forward, partial sums, n_split); popped by the layer's backward
 _BN_BWD_STATS: dict = {}
@@ -189,20 +187,73 @@ def routing(**overrides):
             setattr(ROUTING, k, v)
 
 
+def _rows(x: Tensor) -> Tensor:
+    """The NHWC storage of a channels_last [N, C, H, W] tensor seen as [N H W, C] (a view)."""
+    n, c, h, w = x.shape
+    return x.permute(0, 2, 3, 1).reshape(n * h * w, c)
+
+
+def _nchw(y2: Tensor, n: int, h: int, w: int) -> Tensor:
+    """... and back: [N H W, C] rows as the channels_last [N, C, H, W] tensor they are (a view)."""
+    return y2.view(n, h, w, y2.shape[1]).permute(0, 3, 1, 2)
+
+
+class _PackedOnce:
+    """Freshness of ONE set of packed weight planes (a plane set of an `X6PackGroup`, the stem filter of one precision): the
+    planes object is (re-)packed when the weight asked about changed since the last pack (in-place update: `_version`; fused
+    optimiser step, which writes through raw pointers: `_capi.WEIGHTS_EPOCH`; new storage: `data_ptr`) and by the FIRST request
+    of every hipGraph capture, whatever the stamps say (the host-side stamps describe the moment of recording, a replay must
+    re-split the weights it is about to use); it is built when there is none for the weights' present storage -- never while
+    capturing: building uploads a pointer table (a host-to-device copy) and allocates the planes, and neither may be recorded
+    into a hipGraph (`missing`: the error raised then)."""
+
+    __slots__ = ("planes", "ptrs", "stamps", "capture")
+
+    def __init__(self):
+        self.planes, self.ptrs, self.stamps, self.capture = None, None, None, 0     # (capture: the one that already holds a pack launch)
+
+    @staticmethod
+    def stamp(w):
+        return (w.data_ptr(), w._version, _capi.WEIGHTS_EPOCH)
+
+    def pack(self, weights, build, missing: str):
+        """Pack now; `build()` makes the planes object (one `.pack()` launch for all of `weights`)."""
+        ptrs = [w.data_ptr() for w in weights]
+        if self.planes is None or ptrs != self.ptrs:
+            if _capi.capture_id() != 0:
+                raise _capi.PeclrHipError(missing)
+            self.planes, self.ptrs = build(), ptrs
+        self.planes.pack()
+        self.stamps = [self.stamp(w) for w in weights]
+
+    def fresh(self, w, at: int, repack):
+        """The planes object, after `repack()` (the owner's call of `pack`) if `w`, weight number `at` of the set, moved since the
+        last pack or this capture has no pack launch yet."""
+        stale = self.stamps is None or self.stamps[at] != self.stamp(w)
+        cap = _capi.capture_id()
+        if cap != self.capture:          # a new capture (or back to eager launches): this capture has no pack launch yet
+            stale = stale or cap != 0
+            self.capture = cap
+        if stale:
+            repack()
+        return self.planes
+
+
 class X6PackGroup:
     """The 1x1-convolution weights of one encoder that run as peclr_gemm_x6p_f32 GEMMs, split into fragment-ordered
     bf16 planes by ONE launch per optimiser step (peclr_x6_pack_f32): W[Cout][Cin] for the forward GEMM, W^T for the
     input-gradient GEMMs.  A member convolution asks `planes(conv)` right before it launches; the group re-packs
-    everything when that convolution's weight changed since the last pack (in-place update: `_version`; fused optimiser
-    step, which writes through raw pointers: `_capi.WEIGHTS_EPOCH`; new storage: `data_ptr`).  While a hipGraph is
-    being captured, the FIRST `planes()` call of that capture (whichever member makes it, whatever the stamps say) packs:
-    the host-side stamps describe the moment of recording, a replay must re-split the weights it is about to use."""
+    everything when that convolution's weight changed since the last pack, and on the first `planes()` call of a hipGraph
+    capture, whichever member makes it (`_PackedOnce`)."""
+
+    MISSING = ("X6PackGroup: the weight planes of this precision do not exist yet and cannot be created "
+               "while a hipGraph is being captured -- run one eager forward pass (same autocast dtype) first")
 
     def __init__(self, convs):
         self.convs = [c for c in convs if self.member(c)]
-        # one plane set per operand format: None = the three bf16 planes of the fp32 six-product kernels (peclr_x6_pack_f32);
-        # torch.bfloat16 / torch.float16 = the single 16-bit plane of the autocast kernels (peclr_h_pack), packed from the same
-        # fp32 master weights.  Each: [planes object, parameter addresses, stamps, capture that already holds a pack launch]
+        # one plane set (`_PackedOnce`) per operand format: None = the three bf16 planes of the fp32 six-product kernels
+        # (peclr_x6_pack_f32); "pair" = their fp16-pair format; torch.bfloat16 / torch.float16 = the single 16-bit plane of the
+        # autocast kernels (peclr_h_pack), packed from the same fp32 master weights
         self._sets = {}
         for i, c in enumerate(self.convs):   # (position kept on the module: a deep copy of the model keeps group and members consistent)
             c.x6_group, c.x6_index = self, i
@@ -216,9 +267,6 @@ class X6PackGroup:
             return cout >= 64 and cin >= 64 and cout % 64 == 0 and cin % 64 == 0        # 64-column tiles for layer1
         return (conv.kernel_size == (1, 1) and conv.padding == (0, 0) and cout >= 64 and cin >= 64
                 and cout % 64 == 0 and cin % 64 == 0)
-
-    def _key(self, conv):
-        return (conv.weight.data_ptr(), conv.weight._version, _capi.WEIGHTS_EPOCH)
 
     def _specs(self):
         specs = []
@@ -235,20 +283,12 @@ class X6PackGroup:
                 specs += [(w2, False), (w2, True)]
         return specs
 
+    def _build(self, dtype):
+        return (_capi.X6Planes(self._specs()) if dtype is None else _capi.X6Planes(self._specs(), pair=True) if dtype == "pair"
+                else _capi.HPlanes(self._specs(), dtype))
+
     def pack(self, dtype=None):
-        st = self._sets.setdefault(dtype, [None, None, [None] * len(self.convs), 0])
-        ptrs = [c.weight.data_ptr() for c in self.convs]
-        if st[0] is None or ptrs != st[1]:
-            if _capi.capture_id() != 0:
-                # building the plane set uploads its pointer table (a host-to-device copy) and allocates the planes: neither
-                # may be recorded into a hipGraph
-                raise _capi.PeclrHipError("X6PackGroup: the weight planes of this precision do not exist yet and cannot be created "
-                                          "while a hipGraph is being captured -- run one eager forward pass (same autocast dtype) first")
-            st[0] = (_capi.X6Planes(self._specs()) if dtype is None else _capi.X6Planes(self._specs(), pair=True) if dtype == "pair"
-                     else _capi.HPlanes(self._specs(), dtype))
-            st[1] = ptrs
-        st[0].pack()
-        st[2] = [self._key(c) for c in self.convs]
+        self._sets.setdefault(dtype, _PackedOnce()).pack([c.weight for c in self.convs], lambda: self._build(dtype), self.MISSING)
 
     def planes(self, conv, dtype=None):
         """(forward planes of W [Cout, Cin], input-gradient planes of W^T), fresh; dtype None: the fp32 kernels' three-plane
@@ -257,19 +297,13 @@ class X6PackGroup:
         at = conv.x6_index
         if at >= len(self.convs) or self.convs[at] is not conv:
             raise _capi.PeclrHipError("X6PackGroup: convolution is not a member of its group (call enable_hip_batchnorm again)")
-        st = self._sets.setdefault(dtype, [None, None, [None] * len(self.convs), 0])
-        stale = st[2][at] != self._key(conv)
-        cap = _capi.capture_id()
-        if cap != st[3]:          # a new capture (or back to eager launches): this capture has no pack launch yet
-            stale = stale or cap != 0
-            st[3] = cap
-        if stale:
-            self.pack(dtype)
-        return st[0].planes[2 * at], st[0].planes[2 * at + 1]
+        st = self._sets.setdefault(dtype, _PackedOnce())
+        planes = st.fresh(conv.weight, at, lambda: self.pack(dtype)).planes
+        return planes[2 * at], planes[2 * at + 1]
 
     def pair_scales(self, conv):
         """The device floats holding the powers of two of `conv`'s two pair-format matrices (after `planes(conv, "pair")`)."""
-        st = self._sets["pair"][0]
+        st = self._sets["pair"].planes
         return st.scale(2 * conv.x6_index), st.scale(2 * conv.x6_index + 1)
 
 
@@ -350,17 +384,14 @@ class _BN2dAct(torch.autograd.Function):
         res_deferred: None, or (x_s, scale_shift_s, False) -- `residual` is the placeholder of the shortcut's BatchNorm layer (no
         ReLU), which left its apply pass to THIS pass: the residual is computed from that layer's input on the fly.
         amax: None, or an empty list that receives the device float holding max |y| (the "pair" GEMMs' operand scale)."""
-        training = bn.training or not bn.track_running_stats
+        training, sync, stat_args, stat_kw = bn._fwd_args(pre)
         # the ReLU mask can be recomputed from x unless a residual was added before it; then the
         # forward writes a 1-bit mask (or, for C % 32 != 0, the backward re-reads y)
         need_mask = relu and residual is not None
-        rm, rv, nbt, shift = bn._stat_buffers(training)
         slot = _new_absmax(x) if (amax is not None and defer is None) else None
-        y, save, ss, mask = _capi.bn2d_fwd(x, None if res_deferred is not None else residual, weight, bias, rm, rv, nbt, training, bn.eps,
-                                           bn.momentum if bn.momentum is not None else 0.1, relu, want_mask=need_mask,
-                                           sync_group=bn.sync_group if training else None, sync_shift=shift,
-                                           pre=pre if training else None, apply=defer is None,
-                                           residual_bn=res_deferred[:2] if res_deferred is not None else None, absmax=slot)
+        y, save, ss, mask = _capi.bn2d_fwd(x, None if res_deferred is not None else residual, weight, bias, *stat_args, relu,
+                                           want_mask=need_mask, apply=defer is None,
+                                           residual_bn=res_deferred[:2] if res_deferred is not None else None, absmax=slot, **stat_kw)
         if slot is not None:
             amax[:] = [slot]
         if defer is not None:
@@ -369,7 +400,7 @@ class _BN2dAct(torch.autograd.Function):
         keep = mask if mask is not None else (y if need_mask else None)
         ctx.save_for_backward(x, save, ss, *([keep] if keep is not None else []))
         ctx.cfg = (training, relu, residual is not None, keep is not None, mask is not None)
-        ctx.sync_group = bn.sync_group if training else None
+        ctx.sync_group = sync
         ctx.token = None
         # the residual's gradient is relu'(y) * dy: when its only consumer is the block's entry-gradient GEMM (which then
         # reads dy and the 1-bit mask itself), it is handed over as that pair instead of being written out
@@ -452,15 +483,11 @@ class _BN2dReluPool(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, bn: "FusedBatchNormAct2d", pre=None, amax=None):
-        training = bn.training or not bn.track_running_stats
-        sync = bn.sync_group if training else None
-        rm, rv, nbt, shift = bn._stat_buffers(training)
+        training, sync, stat_args, stat_kw = bn._fwd_args(pre)
         slot = _new_absmax(x) if amax is not None else None
         if slot is not None:
             amax[:] = [slot]
-        y, x_at_max, code, save, ss = _capi.bn2d_pool_fwd(x, weight, bias, rm, rv, nbt, training, bn.eps,
-                                                bn.momentum if bn.momentum is not None else 0.1, sync_group=sync, sync_shift=shift,
-                                                pre=pre if training else None, absmax=slot)
+        y, x_at_max, code, save, ss = _capi.bn2d_pool_fwd(x, weight, bias, *stat_args, absmax=slot, **stat_kw)
         ctx.save_for_backward(x, x_at_max, code, save, ss)
         ctx.cfg = (training, sync)
         return y
@@ -481,12 +508,8 @@ class _BN2dAddReluAvgPool(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, residual, bn: "FusedBatchNormAct2d", pre=None):
-        training = bn.training or not bn.track_running_stats
-        sync = bn.sync_group if training else None
-        rm, rv, nbt, shift = bn._stat_buffers(training)
-        pooled, mask, save, ss = _capi.bn2d_avgpool_fwd(x, residual, weight, bias, rm, rv, nbt, training, bn.eps,
-                                                        bn.momentum if bn.momentum is not None else 0.1, sync_group=sync,
-                                                        sync_shift=shift, pre=pre if training else None)
+        training, sync, stat_args, stat_kw = bn._fwd_args(pre)
+        pooled, mask, save, ss = _capi.bn2d_avgpool_fwd(x, residual, weight, bias, *stat_args, **stat_kw)
         ctx.save_for_backward(x, mask, save, ss)
         ctx.cfg = (training, sync)
         return pooled
@@ -557,23 +580,33 @@ def wgrad_join(on_joined=None):
     _WgradOverlap.parked.clear()
 
 
-def _conv_wgrad(gy: Tensor, x: Tensor, weight: Tensor, stride, padding, param=None):
-    """d(weight) of conv2d(x, weight) for output gradient gy.  Overlap off (or no parameter to park it for):
-    computed here and returned.  Overlap on: issued on the side stream, parked for `param`, returns None."""
-    def run():
-        g = torch.ops.aten.convolution_backward(gy, x, weight.to(x.dtype), None, list(stride), list(padding), [1, 1], False,
-                                                [0, 0], 1, [False, True, False])[1]
-        return g.to((param if param is not None else weight).dtype)
+def _on_side_stream(param, inputs, run, parked_as=None):
+    """A weight gradient `run()` computed from `inputs` = (gy, x).  Overlap off, no parameter to park it for, or inputs that are
+    not on the device: computed here and returned.  Overlap on: issued on the side stream (`parked_as(g)`, there too, gives it the
+    form `wgrad_join` hands over), parked for `param`, returns None."""
     st = _overlap_stream()
-    if st is None or param is None or not gy.is_cuda:
+    if st is None or param is None or not inputs[0].is_cuda:
         return run()
     st.wait_stream(torch.cuda.current_stream())          # gy (and x) are ready where the side stream picks up
     with torch.cuda.stream(st):
         g = run()
-        if g.stride() != param.stride():                 # the parameter's layout (channels_last weights)
-            g = torch.empty_like(param).copy_(g)
-    _WgradOverlap.parked.append((param, g, (gy, x)))     # inputs stay referenced until the join
+        if parked_as is not None:
+            g = parked_as(g)
+    _WgradOverlap.parked.append((param, g, inputs))      # inputs stay referenced until the join
     return None
+
+
+def _conv_wgrad(gy: Tensor, x: Tensor, weight: Tensor, stride, padding, param=None):
+    """d(weight) of conv2d(x, weight) for output gradient gy, from MIOpen; parked for `param` (in the parameter's layout) on the
+    side stream when that mode is on."""
+    def run():
+        g = torch.ops.aten.convolution_backward(gy, x, weight.to(x.dtype), None, list(stride), list(padding), [1, 1], False,
+                                                [0, 0], 1, [False, True, False])[1]
+        return g.to((param if param is not None else weight).dtype)
+
+    def as_param(g):                                     # channels_last weights
+        return g if g.stride() == param.stride() else torch.empty_like(param).copy_(g)
+    return _on_side_stream(param, (gy, x), run, parked_as=as_param)
 
 
 class _Conv2dSplitBackward(torch.autograd.Function):
@@ -618,8 +651,6 @@ def _x6_pays(rows: int, n_out: int, k: int) -> bool:
             and n_out >= 64 and n_out % 64 == 0)
 
 
-
-
 def _x6_wgrad_pays(rows: int, cout: int, cin: int) -> bool:
     """peclr_gemm_x6t_f32 against MIOpen's fp32 1x1 weight gradient (tools/exp/conv1x1_probe.py, wgrad_probe.py): 150-205 us
     against 208-267 from layer2 on; the 64-wide gradients of layer1 (HBM-bound: 8e5 rows of 64 + 256 channels) on 64 x 256 /
@@ -631,24 +662,14 @@ def _x6_wgrad_pays(rows: int, cout: int, cin: int) -> bool:
 def _wgrad_1x1_x6(gy: Tensor, x: Tensor, weight: Tensor, param=None):
     """d(weight) of a 1x1 / stride-1 convolution as dY^T X on the bf16 matrix cores (fp32 accuracy, deterministic
     split-K), shaped and strided like the weight; parked for `param` on the side stream when that mode is on."""
-    n, cin, h, w = x.shape
-    cout = gy.shape[1]
-
     def run():
-        gy2, x2 = gy.permute(0, 2, 3, 1).reshape(n * h * w, cout), x.permute(0, 2, 3, 1).reshape(n * h * w, cin)
+        gy2, x2 = _rows(gy), _rows(x)
         dw = (_capi.gemm_x6t(gy2, x2, tag="conv1x1_wgrad") if ROUTING.gemm_x6t
               else _capi.gemm_x6_tn(gy2, x2, tag="conv1x1_wgrad"))
         ref = param if param is not None else weight
         return dw.as_strided(ref.shape, ref.stride())       # same memory, the parameter's (channels_last) strides
 
-    st = _overlap_stream()
-    if st is None or param is None:
-        return run()
-    st.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(st):
-        g = run()
-    _WgradOverlap.parked.append((param, g, (gy, x)))
-    return None
+    return _on_side_stream(param, (gy, x), run)
 
 
 def _stat_shift_for(bn, cout: int):
@@ -667,30 +688,65 @@ def _stat_shift_for(bn, cout: int):
     return kept if kept is not None else bn.running_mean
 
 
+def _with_stats(stats, cout: int, launch) -> Tensor:
+    """Statistics in the GEMM epilogue: the output of a forward `launch(**kw)` of `cout` channels.  stats: None, or [bn] -- the
+    BatchNorm2d that consumes the output; where that layer can take its statistics from its producer (`_stat_shift_for`) the
+    launch gets `stat_shift` (and returns (y, partial, n_split)) and the list comes back as [partial, n_split, shift, bn] for
+    `_attach_stats`; otherwise the launch is plain and the list is left untouched."""
+    shift = _stat_shift_for(stats[0], cout) if (stats and ROUTING.bn_stats_in_gemm) else None
+    if shift is None:
+        return launch()
+    y, partial, ns = launch(stat_shift=shift)
+    stats[:] = [partial, ns, shift, stats[0]]
+    return y
+
+
+def _with_bn_bwd(link, x: Tensor, launch, same_dtype: bool = False) -> Tensor:
+    """BatchNorm backward reduction in the input-gradient epilogue: dx of a convolution of input `x` from `launch(**kw)`.
+    link: None, or `_bn_link_of(x)` -- x is the output of a fused BatchNorm layer and dx THE gradient arriving at it; where the
+    epilogue takes that layer (same shape, whole 32-channel mask words; same_dtype: the 16-bit kernels also want the layer's
+    input in the gradient's dtype) the launch gets `bn_bwd` (and returns (dx, partial, n_split)) and the sums are parked for
+    the layer's backward (`_note_bn_bwd`); otherwise the launch is plain."""
+    if (link is not None and link[0].shape == x.shape and x.shape[1] % 32 == 0
+            and (not same_dtype or link[0].dtype == x.dtype)):
+        dx, partial, ns = launch(bn_bwd=link[:5])
+        _note_bn_bwd(dx, link, partial, ns)
+        return dx
+    return launch()
+
+
 def _wgrad_3x3_x6(gy: Tensor, x: Tensor, weight: Tensor, param=None, stride: int = 1, taps: int = 9):
     """d(weight) of a 3x3 / padding-1 convolution (stride 1 or 2): nine dY^T X products with X read at the pixel each tap
     points at, all in one launch that splits dY once for the nine taps (peclr_gemm_x6t_f32, taps = 9; fp32 accuracy,
     fixed-order split-K: deterministic), written in the weight's own channels_last storage order [Cout][3][3][Cin].
     taps = 1 with stride 2: the 1x1 / stride-2 shortcut convolution (X read at every second pixel)."""
-    n, cin, h, w = x.shape
+    cin = x.shape[1]
     cout, ho, wo = gy.shape[1:]
 
     def run():
-        gy2, x2 = gy.permute(0, 2, 3, 1).reshape(n * ho * wo, cout), x.permute(0, 2, 3, 1).reshape(n * h * w, cin)
-        dw = _capi.gemm_x6t(gy2, x2, taps=taps, hw=(ho, wo), stride=stride, tag="conv3x3_wgrad" if taps == 9 else "conv1x1_wgrad")
+        dw = _capi.gemm_x6t(_rows(gy), _rows(x), taps=taps, hw=(ho, wo), stride=stride, tag="conv3x3_wgrad" if taps == 9 else "conv1x1_wgrad")
         if taps == 9:
             return dw.view(cout, 3, 3, cin).permute(0, 3, 1, 2)      # = a channels_last [Cout, Cin, 3, 3] tensor
         ref = param if param is not None else weight
         return dw.as_strided(ref.shape, ref.stride())               # [Cout][Cin] in memory either way
 
-    st = _overlap_stream()
-    if st is None or param is None:
-        return run()
-    st.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(st):
-        g = run()
-    _WgradOverlap.parked.append((param, g, (gy, x)))
-    return None
+    return _on_side_stream(param, (gy, x), run)
+
+
+def _conv1x1_fwd(x: Tensor, weight: Tensor, conv, planes, stats, amax) -> Tensor:
+    """y = x . W^T of a 1x1 / stride-1 convolution of an NHWC fp32 tensor (`_Conv1x1Gemm`, `_ForkConv1x1`): on the weight planes
+    packed once per step with the consuming BatchNorm's statistics in the epilogue (stats, amax: see `_Conv1x1Gemm.forward`), or
+    -- planes None: the convolution is in no pack group -- on peclr_gemm_x6_f32, which has no such epilogue."""
+    n, _, h, w = x.shape
+    cout, cin = weight.shape[:2]
+    x2 = _rows(x)
+    if planes is None:
+        return _nchw(_capi.gemm_x6(x2, weight.detach().reshape(cout, cin), tag="conv1x1_fwd"), n, h, w)
+
+    def launch(**kw):
+        pl, pkw = _pair_planes(conv, amax, 0, planes)
+        return _capi.gemm_x6p(x2, pl, cout, tag="conv1x1_fwd", **pkw, **kw)
+    return _nchw(_with_stats(stats, cout, launch), n, h, w)          # channels_last NCHW view of the NHWC result
 
 
 class _Conv1x1Gemm(torch.autograd.Function):
@@ -708,22 +764,7 @@ class _Conv1x1Gemm(torch.autograd.Function):
         planes = _x6_planes(conv) if (use_fwd or use_bwd) else None
         ctx.cfg = (conv, use_bwd, planes)
         ctx.link = link
-        if not use_fwd:
-            return F.conv2d(x, weight)
-        n, cin, h, w = x.shape
-        cout = weight.shape[0]
-        x2 = x.permute(0, 2, 3, 1).reshape(n * h * w, cin)
-        shift = _stat_shift_for(stats[0], cout) if (stats and planes is not None and ROUTING.bn_stats_in_gemm) else None
-        if planes is not None:
-            pl, kw = _pair_planes(conv, amax, 0, planes)
-        if shift is not None:
-            y, partial, ns = _capi.gemm_x6p(x2, pl, cout, tag="conv1x1_fwd", stat_shift=shift, **kw)
-            stats[:] = [partial, ns, shift, stats[0]]
-        elif planes is not None:
-            y = _capi.gemm_x6p(x2, pl, cout, tag="conv1x1_fwd", **kw)
-        else:
-            y = _capi.gemm_x6(x2, weight.detach().reshape(cout, cin), tag="conv1x1_fwd")
-        return y.view(n, h, w, cout).permute(0, 3, 1, 2)          # channels_last NCHW view of the NHWC result
+        return _conv1x1_fwd(x, weight, conv, planes, stats, amax) if use_fwd else F.conv2d(x, weight)
 
     @staticmethod
     def backward(ctx, gy):
@@ -739,26 +780,18 @@ class _Conv1x1Gemm(torch.autograd.Function):
                   else _conv_wgrad(gy, x, weight, (1, 1), (0, 0), param))
         dx = None
         if ctx.needs_input_grad[0]:
-            if use_bwd:
-                gy2 = gy.permute(0, 2, 3, 1).reshape(n * h * w, cout)
-                link = ctx.link
-                if planes is not None:
-                    pl, kw = _pair_planes(conv, _absmax_of(gy), 1, planes)
-                if planes is not None and link is not None and link[0].shape == x.shape and cin % 32 == 0:
-                    dx, partial, ns = _capi.gemm_x6p(gy2, pl, cin, tag="conv1x1_dgrad", bn_bwd=link[:5], **kw)
-                    _note_bn_bwd(dx, link, partial, ns)
-                elif planes is not None:
-                    dx = _capi.gemm_x6p(gy2, pl, cin, tag="conv1x1_dgrad", **kw)
-                else:
-                    wt = weight.detach().reshape(cout, cin).t().contiguous()          # [Cin][Cout]: K-contiguous B operand
-                    dx = _capi.gemm_x6(gy2, wt, tag="conv1x1_dgrad")
-                dx = dx.view(n, h, w, cin).permute(0, 3, 1, 2)
+            if use_bwd and planes is not None:
+                def launch(**kw):
+                    pl, pkw = _pair_planes(conv, _absmax_of(gy), 1, planes)
+                    return _capi.gemm_x6p(_rows(gy), pl, cin, tag="conv1x1_dgrad", **pkw, **kw)
+                dx = _nchw(_with_bn_bwd(ctx.link, x, launch), n, h, w)
+            elif use_bwd:
+                wt = weight.detach().reshape(cout, cin).t().contiguous()          # [Cin][Cout]: K-contiguous B operand
+                dx = _nchw(_capi.gemm_x6(_rows(gy), wt, tag="conv1x1_dgrad"), n, h, w)
             else:
                 dx = torch.ops.aten.convolution_backward(gy, x, weight, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
                                                          [True, False, False])[0]
         return dx, dw, None, None, None, None, None, None
-
-
 
 
 class _Conv3x3Gemm(torch.autograd.Function):
@@ -775,14 +808,12 @@ class _Conv3x3Gemm(torch.autograd.Function):
         ctx.cfg = (conv, planes)
         ctx.link = link
         cout = weight.shape[0]
-        shift = _stat_shift_for(stats[0], cout) if (stats and ROUTING.bn_stats_in_gemm) else None
-        pl, kw = _pair_planes(conv, amax, 0, planes)
-        tile_rows = ROUTING.conv3x3_pair_tile_rows if kw else ROUTING.conv3x3_tile_rows
-        if shift is not None:
-            y, partial, ns = _capi.conv3x3_x6p(x, pl, cout, tag="conv3x3_fwd", tile_rows=tile_rows, stat_shift=shift, **kw)
-            stats[:] = [partial, ns, shift, stats[0]]
-            return y
-        return _capi.conv3x3_x6p(x, pl, cout, tag="conv3x3_fwd", tile_rows=tile_rows, **kw)
+
+        def launch(**kw):
+            pl, pkw = _pair_planes(conv, amax, 0, planes)
+            tile_rows = ROUTING.conv3x3_pair_tile_rows if pkw else ROUTING.conv3x3_tile_rows
+            return _capi.conv3x3_x6p(x, pl, cout, tag="conv3x3_fwd", tile_rows=tile_rows, **pkw, **kw)
+        return _with_stats(stats, cout, launch)
 
     @staticmethod
     def backward(ctx, gy):
@@ -797,19 +828,12 @@ class _Conv3x3Gemm(torch.autograd.Function):
             dw = _wgrad_3x3_x6(gy, x, weight, conv.weight) if in_tree else _conv_wgrad(gy, x, weight, (1, 1), (1, 1), conv.weight)
         dx = None
         if ctx.needs_input_grad[0]:
-            link = ctx.link
-            pl, kw = _pair_planes(conv, _absmax_of(gy), 1, planes)
-            tile_rows = ROUTING.conv3x3_pair_tile_rows if kw else ROUTING.conv3x3_tile_rows
-            if link is not None and link[0].shape == x.shape and x.shape[1] % 32 == 0:
-                # dx is the gradient arriving at the BatchNorm layer whose output x is: reduce it in the epilogue
-                dx, partial, ns = _capi.conv3x3_x6p(gy, pl, x.shape[1], flip=True, tag="conv3x3_dgrad", tile_rows=tile_rows,
-                                                    bn_bwd=link[:5], **kw)
-                _note_bn_bwd(dx, link, partial, ns)
-            else:
-                dx = _capi.conv3x3_x6p(gy, pl, x.shape[1], flip=True, tag="conv3x3_dgrad", tile_rows=tile_rows, **kw)
+            def launch(**kw):
+                pl, pkw = _pair_planes(conv, _absmax_of(gy), 1, planes)
+                tile_rows = ROUTING.conv3x3_pair_tile_rows if pkw else ROUTING.conv3x3_tile_rows
+                return _capi.conv3x3_x6p(gy, pl, x.shape[1], flip=True, tag="conv3x3_dgrad", tile_rows=tile_rows, **pkw, **kw)
+            dx = _with_bn_bwd(ctx.link, x, launch)
         return dx, dw, None, None, None, None
-
-
 
 
 class _ConvS2Gemm(torch.autograd.Function):
@@ -827,13 +851,11 @@ class _ConvS2Gemm(torch.autograd.Function):
         ctx.link = link
         planes = _x6_planes(conv)
         cout, taps = weight.shape[0], weight.shape[2] * weight.shape[3]
-        shift = _stat_shift_for(stats[0], cout) if (stats and ROUTING.bn_stats_in_gemm) else None
-        pl, kw = _pair_planes(conv, amax, 0, planes)
-        if shift is not None:
-            y, partial, ns = _capi.conv_s2_x6p(x, pl, cout, taps, tag="conv_s2_fwd", stat_shift=shift, tile_rows=ROUTING.s2_tile_rows if taps == 9 else 0, **kw)
-            stats[:] = [partial, ns, shift, stats[0]]
-            return y
-        return _capi.conv_s2_x6p(x, pl, cout, taps, tag="conv_s2_fwd", tile_rows=ROUTING.s2_tile_rows if taps == 9 else 0, **kw)
+
+        def launch(**kw):
+            pl, pkw = _pair_planes(conv, amax, 0, planes)
+            return _capi.conv_s2_x6p(x, pl, cout, taps, tag="conv_s2_fwd", tile_rows=ROUTING.s2_tile_rows if taps == 9 else 0, **pkw, **kw)
+        return _with_stats(stats, cout, launch)
 
     @staticmethod
     def backward(ctx, gy):
@@ -857,21 +879,17 @@ class _ConvS2Gemm(torch.autograd.Function):
                 # pixels: no 4x larger tensor); elsewhere (BasicBlock networks: the block input is a plain tensor) it is
                 # scattered into zeros here -- never MIOpen's input gradient, whose fp32 1x1 / stride-2 solver adds with float
                 # atomics (a different last bit every run: tools/exp/two_outcome.py)
-                n, cout, ho, wo = gy.shape
                 pl, kw = _pair_planes(conv, _absmax_of(gy), 1, _x6_planes(conv))
-                dc = _capi.gemm_x6p(gy.permute(0, 2, 3, 1).reshape(n * ho * wo, cout), pl, x.shape[1], tag="conv_s2_dgrad", **kw)
+                dc = _capi.gemm_x6p(_rows(gy), pl, x.shape[1], tag="conv_s2_dgrad", **kw)
                 dx = _compact_grad(dc, x.shape) if (ctx.compact and not torch.is_anomaly_enabled()) else _expand_compact(dc, x.shape)
             elif (ROUTING.conv_s2_dgrad_x6 and weight.shape[2] == 3 and x.shape[2] == 2 * gy.shape[2] and x.shape[3] == 2 * gy.shape[3]
                   and x.shape[1] % 64 == 0 and gy.shape[1] % 16 == 0):
                 # 3x3: one dense implicit GEMM per parity class of input pixels (1, 2, 2, 4 taps); dx is the gradient arriving
                 # at the BatchNorm layer whose output x is: reduced in the epilogue
-                pl, kw = _pair_planes(conv, _absmax_of(gy), 1, _x6_planes(conv))
-                link = ctx.link
-                if link is not None and link[0].shape == x.shape and x.shape[1] % 32 == 0:
-                    dx, partial, ns = _capi.conv3x3_s2_dgrad_x6p(gy, pl, x.shape[1], bn_bwd=link[:5], tile_rows=ROUTING.s2_tile_rows, **kw)
-                    _note_bn_bwd(dx, link, partial, ns)
-                else:
-                    dx = _capi.conv3x3_s2_dgrad_x6p(gy, pl, x.shape[1], tile_rows=ROUTING.s2_tile_rows, **kw)
+                def launch(**kw):
+                    pl, pkw = _pair_planes(conv, _absmax_of(gy), 1, _x6_planes(conv))
+                    return _capi.conv3x3_s2_dgrad_x6p(gy, pl, x.shape[1], tile_rows=ROUTING.s2_tile_rows, **pkw, **kw)
+                dx = _with_bn_bwd(ctx.link, x, launch)
             else:
                 dx = torch.ops.aten.convolution_backward(gy, x, weight, None, [2, 2], pad, [1, 1], False, [0, 0], 1, [True, False, False])[0]
         return dx, dw, None, None, None, None, None
@@ -928,15 +946,14 @@ def _dense_of(payload, shape) -> Tensor:
     _, dy, mask = payload
     n, c, h, w = shape
     bits = (mask.view(n * h * w, c // 32, 1) >> torch.arange(32, device=mask.device, dtype=torch.int32)) & 1
-    d = dy.permute(0, 2, 3, 1).reshape(n * h * w, c) * bits.view(n * h * w, c).to(dy.dtype)
-    return d.view(n, h, w, c).permute(0, 3, 1, 2)
+    return _nchw(_rows(dy) * bits.view(n * h * w, c).to(dy.dtype), n, h, w)
 
 
 def _expand_compact(dc: Tensor, shape) -> Tensor:
     """The dense form (fallback paths): zeros with the compact gradient at the even pixels."""
     n, c, h, w = shape
     full = torch.zeros(shape, device=dc.device, dtype=dc.dtype).contiguous(memory_format=torch.channels_last)
-    full[:, :, ::2, ::2] = dc.view(n, h // 2, w // 2, c).permute(0, 3, 1, 2)
+    full[:, :, ::2, ::2] = _nchw(dc, n, h // 2, w // 2)
     return full
 
 
@@ -1008,22 +1025,13 @@ def _wgrad_h(gy: Tensor, x: Tensor, conv, stride: int):
     (+ its cast to fp32)."""
     w = conv.weight
     taps = w.shape[2] * w.shape[3]
-    fn = getattr(_capi, "wgrad_h", None)
-    if (fn is not None and ROUTING.wgrad16 and w.is_contiguous(memory_format=torch.channels_last)
-            and _capi.wgrad_h_ok(gy, x, taps, stride)):
+    if ROUTING.wgrad16 and w.is_contiguous(memory_format=torch.channels_last) and _capi.wgrad_h_ok(gy, x, taps, stride):
         def run():
-            dw = fn(gy, x, taps, stride)                  # [Cout, taps * Cin] fp32
+            dw = _capi.wgrad_h(gy, x, taps, stride)       # [Cout, taps * Cin] fp32
             if taps == 9:
                 return dw.view(w.shape[0], 3, 3, w.shape[1]).permute(0, 3, 1, 2)    # = a channels_last [Cout, Cin, 3, 3] tensor
             return dw.as_strided(w.shape, w.stride())
-        st = _overlap_stream()
-        if st is None:
-            return run()
-        st.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(st):
-            g = run()
-        _WgradOverlap.parked.append((w, g, (gy, x)))
-        return None
+        return _on_side_stream(w, (gy, x), run)
     return _conv_wgrad(gy, x, w, conv.stride, conv.padding, w)
 
 
@@ -1040,22 +1048,11 @@ class _ConvH(torch.autograd.Function):
         planes = conv.x6_group.planes(conv, x.dtype)
         ctx.planes = planes
         cout, taps, stride = conv.out_channels, conv.kernel_size[0] * conv.kernel_size[1], conv.stride[0]
-        shift = _stat_shift_for(stats[0], cout) if (stats and ROUTING.bn_stats_in_gemm) else None
-        n, cin, h, w = x.shape
+        n, _, h, w = x.shape
         if taps == 1 and stride == 1:
-            x2 = x.permute(0, 2, 3, 1).reshape(n * h * w, cin)
-            if shift is not None:
-                y, partial, ns = _capi.gemm_h(x2, planes[0], cout, tag="conv1x1_fwd", stat_shift=shift)
-                stats[:] = [partial, ns, shift, stats[0]]
-            else:
-                y = _capi.gemm_h(x2, planes[0], cout, tag="conv1x1_fwd")
-            return y.view(n, h, w, cout).permute(0, 3, 1, 2)
+            return _nchw(_with_stats(stats, cout, lambda **kw: _capi.gemm_h(_rows(x), planes[0], cout, tag="conv1x1_fwd", **kw)), n, h, w)
         tag = "conv3x3_fwd" if stride == 1 else "conv_s2_fwd"
-        if shift is not None:
-            y, partial, ns = _capi.conv_h(x, planes[0], cout, taps=taps, stride=stride, tag=tag, stat_shift=shift)
-            stats[:] = [partial, ns, shift, stats[0]]
-            return y
-        return _capi.conv_h(x, planes[0], cout, taps=taps, stride=stride, tag=tag)
+        return _with_stats(stats, cout, lambda **kw: _capi.conv_h(x, planes[0], cout, taps=taps, stride=stride, tag=tag, **kw))
 
     @staticmethod
     def backward(ctx, gy):
@@ -1063,36 +1060,26 @@ class _ConvH(torch.autograd.Function):
         conv, planes, link = ctx.conv, ctx.planes, ctx.link
         gy = gy.to(x.dtype).contiguous(memory_format=torch.channels_last)
         n, cin, h, w = x.shape
-        cout, taps, stride = conv.out_channels, conv.kernel_size[0] * conv.kernel_size[1], conv.stride[0]
+        taps, stride = conv.kernel_size[0] * conv.kernel_size[1], conv.stride[0]
         dw = _wgrad_h(gy, x, conv, stride) if ctx.needs_input_grad[1] else None
         dx = None
         if ctx.needs_input_grad[0]:
-            fuse = link[:5] if (link is not None and link[0].shape == x.shape and link[0].dtype == x.dtype and cin % 32 == 0) else None
             if taps == 1 and stride == 1:
-                gy2 = gy.permute(0, 2, 3, 1).reshape(n * h * w, cout)
-                out = _capi.gemm_h(gy2, planes[1], cin, tag="conv1x1_dgrad", bn_bwd=fuse)
+                dx = _nchw(_with_bn_bwd(link, x, lambda **kw: _capi.gemm_h(_rows(gy), planes[1], cin, tag="conv1x1_dgrad", **kw),
+                                        same_dtype=True), n, h, w)
             elif taps == 9 and stride == 1:
-                out = _capi.conv_h(gy, planes[1], cin, flip=True, tag="conv3x3_dgrad", bn_bwd=fuse)
+                dx = _with_bn_bwd(link, x, lambda **kw: _capi.conv_h(gy, planes[1], cin, flip=True, tag="conv3x3_dgrad", **kw),
+                                  same_dtype=True)
             elif taps == 9:
-                out = _capi.conv3x3_s2_dgrad_h(gy, planes[1], cin, bn_bwd=fuse)
+                dx = _with_bn_bwd(link, x, lambda **kw: _capi.conv3x3_s2_dgrad_h(gy, planes[1], cin, **kw), same_dtype=True)
             elif h == 2 * gy.shape[2] and w == 2 * gy.shape[3]:
                 # 1x1 / stride-2 shortcut: dY . W over the OUTPUT pixels only; the block's entry-gradient GEMM adds it at the even
                 # pixels, any other consumer gets it scattered into zeros (deterministic, unlike MIOpen's atomics)
-                ho, wo = gy.shape[2:]
-                dc = _capi.gemm_h(gy.permute(0, 2, 3, 1).reshape(n * ho * wo, cout), planes[1], cin, tag="conv_s2_dgrad")
-                lazy = ctx.compact and not torch.is_anomaly_enabled()
-                return (_compact_grad(dc, x.shape) if lazy else _expand_compact(dc, x.shape)), dw, None, None, None, None
+                dc = _capi.gemm_h(_rows(gy), planes[1], cin, tag="conv_s2_dgrad")
+                dx = _compact_grad(dc, x.shape) if (ctx.compact and not torch.is_anomaly_enabled()) else _expand_compact(dc, x.shape)
             else:
-                w16 = conv.weight.detach().to(x.dtype)
-                return (torch.ops.aten.convolution_backward(gy, x, w16, None, [2, 2], [0, 0], [1, 1], False, [0, 0], 1, [True, False, False])[0],
-                        dw, None, None, None, None)
-            if fuse is not None:
-                dx, partial, ns = out
-                _note_bn_bwd(dx, link, partial, ns)
-            else:
-                dx = out
-            if taps == 1:
-                dx = dx.view(n, h, w, cin).permute(0, 3, 1, 2)
+                dx = torch.ops.aten.convolution_backward(gy, x, conv.weight.detach().to(x.dtype), None, [2, 2], [0, 0], [1, 1], False,
+                                                         [0, 0], 1, [True, False, False])[0]
         return dx, dw, None, None, None, None
 
 
@@ -1103,14 +1090,7 @@ def _stem_wgrad(gy: Tensor, x: Tensor, param):
         dw = _capi.stem_wgrad(gy, x)
         return torch.empty_like(param).copy_(dw)                   # (9 408 elements: into the parameter's own strides)
 
-    st = _overlap_stream()
-    if st is None:
-        return run()
-    st.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(st):
-        g = run()
-    _WgradOverlap.parked.append((param, g, (gy, x)))
-    return None
+    return _on_side_stream(param, (gy, x), run)
 
 
 class _StemConv(torch.autograd.Function):
@@ -1126,12 +1106,7 @@ class _StemConv(torch.autograd.Function):
         planes = conv._stem_planes(dtype)
         ctx.save_for_backward(x, weight)
         ctx.conv, ctx.dtype = conv, dtype
-        shift = _stat_shift_for(stats[0], 64) if (stats and ROUTING.bn_stats_in_gemm) else None
-        if shift is not None:
-            y, partial, ns = _capi.stem_conv(x, planes, stat_shift=shift)
-            stats[:] = [partial, ns, shift, stats[0]]
-            return y
-        return _capi.stem_conv(x, planes)
+        return _with_stats(stats, 64, lambda **kw: _capi.stem_conv(x, planes, **kw))
 
     @staticmethod
     def backward(ctx, gy):
@@ -1161,29 +1136,15 @@ class Conv2d(nn.Conv2d):
 
     hip_gemm = False   # enable_hip_batchnorm: fp32 1x1 / stride-1 convolutions as GEMMs on the bf16 matrix cores
     hip_stem = False   # enable_hip_batchnorm: this is the 7x7 / stride-2 stem of 3-channel images (csrc/stem.hip)
+    STEM_MISSING = ("stem: the filter planes of this precision do not exist yet and cannot be created while a "
+                    "hipGraph is being captured -- run one eager forward pass (same autocast dtype) first")
 
     def _stem_planes(self, dtype):
         """The stem filter packed for `dtype` (fp32: three bf16 planes; bf16 / fp16: one plane), fresh: re-packed when the weight
-        changed since the last pack (`_version`, fused optimiser epoch, storage) and once per hipGraph capture -- the protocol
-        of `X6PackGroup.planes`."""
-        sets = self.__dict__.setdefault("_stem_sets", {})
-        st = sets.get(dtype)
+        changed since the last pack and once per hipGraph capture (`_PackedOnce`, one per dtype)."""
+        st = self.__dict__.setdefault("_stem_sets", {}).setdefault(dtype, _PackedOnce())
         w = self.weight
-        key = (w.data_ptr(), w._version, _capi.WEIGHTS_EPOCH)
-        cap = _capi.capture_id()
-        if st is None or st[0].weight.data_ptr() != w.data_ptr():
-            if cap != 0:
-                raise _capi.PeclrHipError("stem: the filter planes of this precision do not exist yet and cannot be created while a "
-                                          "hipGraph is being captured -- run one eager forward pass (same autocast dtype) first")
-            st = sets[dtype] = [_capi.StemPlanes(w.detach(), dtype), None, 0]
-        stale = st[1] != key
-        if cap != st[2]:
-            stale = stale or cap != 0
-            st[2] = cap
-        if stale:
-            st[0].pack()
-            st[1] = key
-        return st[0]
+        return st.fresh(w, 0, lambda: st.pack([w], lambda: _capi.StemPlanes(w.detach(), dtype), self.STEM_MISSING))
 
     def forward(self, x: Tensor, stats_for=None, sole_consumer: bool = False) -> Tensor:
         """stats_for: the BatchNorm2d that consumes the output -- when this convolution runs as an in-tree GEMM its
@@ -1207,9 +1168,11 @@ class Conv2d(nn.Conv2d):
             compact = (ROUTING.s2_dgrad_compact and self.kernel_size == (1, 1) and self.stride == (2, 2)
                        and getattr(x, "_peclr_compact_ok", False) and grad)
             return _attach_stats(_ConvH.apply(x, self.weight, self, stats, bn_link(x) if grad else None, compact), stats)
-        if (self.hip_gemm and x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")
-                and self.kernel_size == (1, 1) and self.stride == (1, 1) and self.padding == (0, 0) and self.groups == 1
-                and self.bias is None and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)):
+        # what every fp32 in-tree arm below needs of its input: an NHWC fp32 device tensor outside autocast
+        fp32 = (self.hip_gemm and x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled("cuda") and x.dim() == 4
+                and x.is_contiguous(memory_format=torch.channels_last))
+        if (fp32 and self.kernel_size == (1, 1) and self.stride == (1, 1) and self.padding == (0, 0) and self.groups == 1
+                and self.bias is None):
             rows = x.shape[0] * x.shape[2] * x.shape[3]
             use_fwd = _x6_pays(rows, self.out_channels, self.in_channels)
             use_bwd = _x6_pays(rows, self.in_channels, self.out_channels) and torch.is_grad_enabled() and x.requires_grad
@@ -1218,19 +1181,16 @@ class Conv2d(nn.Conv2d):
             if use_fwd or use_bwd or use_wgrad:
                 stats = [stats_for] if (stats_for is not None and use_fwd) else None
                 return _attach_stats(_Conv1x1Gemm.apply(x, self.weight, self, use_fwd, use_bwd, stats, bn_link(x) if use_bwd else None, _absmax_of(x)), stats)
-        if (self.hip_gemm and ROUTING.conv_s2_x6 and ROUTING.gemm_x6p and getattr(self, "x6_group", None) is not None and self.stride == (2, 2)
-                and x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled("cuda") and x.dim() == 4
-                and x.is_contiguous(memory_format=torch.channels_last) and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
+        if (fp32 and ROUTING.conv_s2_x6 and ROUTING.gemm_x6p and getattr(self, "x6_group", None) is not None and self.stride == (2, 2)
+                and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
                 and (x.shape[0] * x.shape[2] * x.shape[3] >= 32768 or ROUTING.force)):
             stats = [stats_for] if stats_for is not None else None
             compact = (ROUTING.s2_dgrad_compact and self.kernel_size == (1, 1) and getattr(x, "_peclr_compact_ok", False)
                        and torch.is_grad_enabled() and x.requires_grad)
             link = bn_link(x) if (torch.is_grad_enabled() and x.requires_grad and self.kernel_size == (3, 3)) else None
             return _attach_stats(_ConvS2Gemm.apply(x, self.weight, self, stats, compact, link, _absmax_of(x)), stats)
-        if (self.hip_gemm and ROUTING.conv3x3_x6 and ROUTING.gemm_x6p and getattr(self, "x6_group", None) is not None and self.kernel_size == (3, 3)
+        if (fp32 and ROUTING.conv3x3_x6 and ROUTING.gemm_x6p and getattr(self, "x6_group", None) is not None and self.kernel_size == (3, 3)
                 and self.stride == (1, 1)
-                and x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled("cuda") and x.dim() == 4
-                and x.is_contiguous(memory_format=torch.channels_last)
                 and (x.shape[0] * x.shape[2] * x.shape[3] >= 8192 or ROUTING.force)):
             stats = [stats_for] if stats_for is not None else None
             return _attach_stats(_Conv3x3Gemm.apply(x, self.weight, self, stats, bn_link(x), _absmax_of(x)), stats)
@@ -1250,6 +1210,17 @@ def _entry_gemm(a: Tensor, planes: Tensor, n: int, addend=None, **kw):
     (Round 5 tried a barrier-free streaming kernel for the HBM-bound shapes here -- tools/exp/gemm_x6s.hip, bit-identical
     output -- and measured it slower: docs/history.md.)"""
     return _capi.gemm_x6p(a, planes, n, addend, tag="conv1x1_dgrad_add_x6", **kw)
+
+
+def _entry_addend(gid: Tensor, lazy, x: Tensor) -> dict:
+    """The addend keywords of a block's entry-gradient GEMM (peclr_gemm_x6p_f32 / peclr_gemm_h) for the identity branch's gradient
+    `gid` of the block input `x`: dense rows, or -- lazy = `_take_lazy(gid)` -- the compact gradient of a stride-2 shortcut (added
+    at the even pixels) / the (dy, mask) pair of an identity shortcut."""
+    if lazy is None:
+        return dict(addend=_rows(gid.to(x.dtype).contiguous(memory_format=torch.channels_last)))
+    if lazy[0] == "s2":
+        return dict(addend=lazy[1], addend_s2=tuple(x.shape[2:]))
+    return dict(addend=_rows(lazy[1].contiguous(memory_format=torch.channels_last)), addend_mask=lazy[2])
 
 
 class _ForkConv1x1(torch.autograd.Function):
@@ -1276,20 +1247,7 @@ class _ForkConv1x1(torch.autograd.Function):
         ctx.use_bwd = use_bwd
         if flags is not None:       # tells fork_conv1x1 whether the backward takes compact shortcut gradients (the x6p GEMM)
             flags.append(bool(use_bwd and ctx.planes is not None))
-        if use_fwd:
-            x2 = x.permute(0, 2, 3, 1).reshape(r, cin)
-            shift = _stat_shift_for(stats[0], cmid) if (stats and ctx.planes is not None and ROUTING.bn_stats_in_gemm) else None
-            if ctx.planes is not None:
-                pl, kw = _pair_planes(conv, amax, 0, ctx.planes)
-            if shift is not None:
-                y, partial, ns = _capi.gemm_x6p(x2, pl, cmid, tag="conv1x1_fwd", stat_shift=shift, **kw)
-                stats[:] = [partial, ns, shift, stats[0]]
-            elif ctx.planes is not None:
-                y = _capi.gemm_x6p(x2, pl, cmid, tag="conv1x1_fwd", **kw)
-            else:
-                y = _capi.gemm_x6(x2, weight.detach().reshape(cmid, cin), tag="conv1x1_fwd")
-            return y.view(n, h, w, cmid).permute(0, 3, 1, 2), x.view_as(x)
-        return F.conv2d(x, weight), x.view_as(x)
+        return (_conv1x1_fwd(x, weight, conv, ctx.planes, stats, amax) if use_fwd else F.conv2d(x, weight)), x.view_as(x)
 
     @staticmethod
     def backward(ctx, gy, gid):
@@ -1305,47 +1263,30 @@ class _ForkConv1x1(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             gy = gy.contiguous(memory_format=torch.channels_last)
-            r = n * h * w
-            a = gy.permute(0, 2, 3, 1).reshape(r, cmid)           # NHWC storage seen as [R, Cmid]: a view
+            a = _rows(gy)                   # NHWC storage seen as [R, Cmid]: a view
             lazy = _take_lazy(gid)          # the shortcut's gradient in its compact / (dy, mask) form (see `_lazy_grad`)
-            if lazy is not None and ctx.use_bwd and ctx.planes is not None and x.dtype == torch.float32:
-                if lazy[0] == "s2":
-                    kw = dict(addend=lazy[1], addend_s2=(h, w))
-                else:
-                    kw = dict(addend=lazy[1].contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1).reshape(r, cin), addend_mask=lazy[2])
-                link = ctx.link
-                pl, pkw = _pair_planes(ctx.conv, _absmax_of(gy), 1, ctx.planes)
-                kw.update(pkw)
-                if link is not None and link[0].shape == x.shape and cin % 32 == 0:
-                    out, partial, ns = _entry_gemm(a, pl, cin, bn_bwd=link[:5], **kw)
-                    _note_bn_bwd(out, link, partial, ns)
-                else:
-                    out = _entry_gemm(a, pl, cin, **kw)
-                return out.view(n, h, w, cin).permute(0, 3, 1, 2), dw, None, None, None, None, None
-            if lazy is not None:
-                gid = _dense_of(lazy, x.shape)
-            gid = gid.to(x.dtype).contiguous(memory_format=torch.channels_last)
-            d = gid.permute(0, 2, 3, 1).reshape(r, cin)
-            if x.dtype in (torch.bfloat16, torch.float16):       # autocast backbone: 16-bit MFMA, fp32 accumulate
-                wt = torch.empty((cin, cmid), device=x.device, dtype=x.dtype)
-                wt.copy_(weight.detach().reshape(cmid, cin).t())      # transpose + cast in ONE launch
-                out = _capi.gemm_add_half(a, wt, d, tag="conv1x1_dgrad_add")
-            elif ctx.use_bwd and ctx.planes is not None:
-                # fp32 on the bf16 matrix cores (exact 3-way split, six products), weight planes packed once per step;
-                # the result is the gradient arriving at the previous block's last BatchNorm: reduced in the epilogue
-                link = ctx.link
-                pl, pkw = _pair_planes(ctx.conv, _absmax_of(gy), 1, ctx.planes)
-                if link is not None and link[0].shape == x.shape and cin % 32 == 0:
-                    out, partial, ns = _entry_gemm(a, pl, cin, d, bn_bwd=link[:5], **pkw)
-                    _note_bn_bwd(out, link, partial, ns)
-                else:
-                    out = _entry_gemm(a, pl, cin, d, **pkw)
-            elif ctx.use_bwd:
-                wt = weight.detach().reshape(cmid, cin).t().contiguous()
-                out = _capi.gemm_x6(a, wt, d, tag="conv1x1_dgrad_add_x6")
+            if ctx.use_bwd and ctx.planes is not None:
+                # fp32 on the bf16 matrix cores (exact 3-way split, six products; `use_bwd`: fp32 only), weight planes packed once
+                # per step; the result is the gradient arriving at the previous block's last BatchNorm: reduced in the epilogue
+                addend = _entry_addend(gid, lazy, x)
+
+                def launch(**kw):
+                    pl, pkw = _pair_planes(ctx.conv, _absmax_of(gy), 1, ctx.planes)
+                    return _entry_gemm(a, pl, cin, **addend, **pkw, **kw)
+                out = _with_bn_bwd(ctx.link, x, launch)
             else:
-                out = _capi.gemm_add(_capi.GEMM_NN, a, weight.reshape(cmid, cin), d, tag="conv1x1_dgrad_add")
-            dx = out.view(n, h, w, cin).permute(0, 3, 1, 2)       # back to a channels_last NCHW tensor
+                dense = gid if lazy is None else _dense_of(lazy, x.shape)        # (these kernels add a dense tensor only)
+                d = _rows(dense.to(x.dtype).contiguous(memory_format=torch.channels_last))
+                if x.dtype in _HALF:             # autocast backbone: 16-bit MFMA, fp32 accumulate
+                    wt = torch.empty((cin, cmid), device=x.device, dtype=x.dtype)
+                    wt.copy_(weight.detach().reshape(cmid, cin).t())      # transpose + cast in ONE launch
+                    out = _capi.gemm_add_half(a, wt, d, tag="conv1x1_dgrad_add")
+                elif ctx.use_bwd:
+                    wt = weight.detach().reshape(cmid, cin).t().contiguous()
+                    out = _capi.gemm_x6(a, wt, d, tag="conv1x1_dgrad_add_x6")
+                else:
+                    out = _capi.gemm_add(_capi.GEMM_NN, a, weight.reshape(cmid, cin), d, tag="conv1x1_dgrad_add")
+            dx = _nchw(out, n, h, w)        # back to a channels_last NCHW tensor
         return dx, dw, None, None, None, None, None
 
 
@@ -1359,42 +1300,23 @@ class _ForkConvH(torch.autograd.Function):
         ctx.save_for_backward(x)
         ctx.conv, ctx.link = conv, link
         planes = ctx.planes = conv.x6_group.planes(conv, x.dtype)
-        n, cin, h, w = x.shape
+        n, _, h, w = x.shape
         cmid = conv.out_channels
-        x2 = x.permute(0, 2, 3, 1).reshape(n * h * w, cin)
-        shift = _stat_shift_for(stats[0], cmid) if (stats and ROUTING.bn_stats_in_gemm) else None
-        if shift is not None:
-            y, partial, ns = _capi.gemm_h(x2, planes[0], cmid, tag="conv1x1_fwd", stat_shift=shift)
-            stats[:] = [partial, ns, shift, stats[0]]
-        else:
-            y = _capi.gemm_h(x2, planes[0], cmid, tag="conv1x1_fwd")
-        return y.view(n, h, w, cmid).permute(0, 3, 1, 2), x.view_as(x)
+        y = _with_stats(stats, cmid, lambda **kw: _capi.gemm_h(_rows(x), planes[0], cmid, tag="conv1x1_fwd", **kw))
+        return _nchw(y, n, h, w), x.view_as(x)
 
     @staticmethod
     def backward(ctx, gy, gid):
         (x,) = ctx.saved_tensors
         conv, planes, link = ctx.conv, ctx.planes, ctx.link
         n, cin, h, w = x.shape
-        cmid = conv.out_channels
-        r = n * h * w
         gy = gy.to(x.dtype).contiguous(memory_format=torch.channels_last)
         dw = _wgrad_h(gy, x, conv, 1) if ctx.needs_input_grad[1] else None
         dx = None
         if ctx.needs_input_grad[0]:
-            a = gy.permute(0, 2, 3, 1).reshape(r, cmid)
-            lazy = _take_lazy(gid)
-            if lazy is None:
-                kw = dict(addend=gid.to(x.dtype).contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1).reshape(r, cin))
-            elif lazy[0] == "s2":
-                kw = dict(addend=lazy[1], addend_s2=(h, w))
-            else:
-                kw = dict(addend=lazy[1].contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1).reshape(r, cin), addend_mask=lazy[2])
-            if link is not None and link[0].shape == x.shape and link[0].dtype == x.dtype and cin % 32 == 0:
-                out, partial, ns = _capi.gemm_h(a, planes[1], cin, tag="conv1x1_dgrad_add", bn_bwd=link[:5], **kw)
-                _note_bn_bwd(out, link, partial, ns)
-            else:
-                out = _capi.gemm_h(a, planes[1], cin, tag="conv1x1_dgrad_add", **kw)
-            dx = out.view(n, h, w, cin).permute(0, 3, 1, 2)
+            addend = _entry_addend(gid, _take_lazy(gid), x)
+            dx = _nchw(_with_bn_bwd(link, x, lambda **kw: _capi.gemm_h(_rows(gy), planes[1], cin, tag="conv1x1_dgrad_add", **addend, **kw),
+                                    same_dtype=True), n, h, w)
         return dx, dw, None, None, None
 
 
@@ -1456,6 +1378,16 @@ class FusedBatchNormAct2d(nn.BatchNorm2d):
             if shift is None:
                 shift = self.running_mean.detach().clone()
         return self.running_mean, self.running_var, self.num_batches_tracked, shift
+
+    def _fwd_args(self, pre):
+        """What the three fused forwards hand their kernel about this layer: (training, sync group, the positional block
+        (running_mean, running_var, num_batches_tracked, training, eps, momentum), the keywords sync_group / sync_shift / pre);
+        `pre`: the statistics a producer's epilogue summed (training only)."""
+        training = self.training or not self.track_running_stats
+        sync = self.sync_group if training else None
+        rm, rv, nbt, shift = self._stat_buffers(training)
+        return (training, sync, (rm, rv, nbt, training, self.eps, self.momentum if self.momentum is not None else 0.1),
+                dict(sync_group=sync, sync_shift=shift, pre=pre if training else None))
 
     def _takes_deferred_residual(self, x: Tensor) -> bool:
         """Can this layer's pass compute the shortcut's BatchNorm itself (peclr_bn2d_apply_res_bn)?  The plain fused pass only

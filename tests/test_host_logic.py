@@ -864,3 +864,163 @@ def test_absmax_tag_is_dropped_when_the_tensor_is_written_after_the_pass_that_me
         assert bn2d._absmax_of(t) is slot
     with bn2d.routing(x6_pair=False):
         assert bn2d._absmax_of(t) is None
+
+
+def test_stats_hand_over_fills_the_list_only_when_the_batchnorm_takes_statistics(monkeypatch):
+    """bn2d._with_stats, the one place a forward launch is offered its consumer's BatchNorm statistics: no list, a layer that
+    cannot take them (`_stat_shift_for` -> None) or the routing switch off -> `launch()` without `stat_shift`, list untouched;
+    else `launch(stat_shift=shift)` and the list comes back as [partial, n_split, shift, bn]."""
+    from peclr_amd import bn2d as B
+
+    calls = []
+
+    def launch(**kw):
+        calls.append(kw)
+        return ("y", "partial", 7) if "stat_shift" in kw else "y"
+
+    bn = B.FusedBatchNormAct2d(8)             # not switched to the HIP kernels, CPU buffers: cannot take statistics
+    stats = [bn]
+    assert B._stat_shift_for(bn, 8) is None
+    assert B._with_stats(None, 8, launch) == "y" and B._with_stats(stats, 8, launch) == "y"
+    assert calls == [{}, {}] and stats == [bn]
+    shift = torch.zeros(8)
+    monkeypatch.setattr(B, "_stat_shift_for", lambda layer, cout: shift if (layer is bn and cout == 8) else None)
+    with B.routing(bn_stats_in_gemm=False):
+        assert B._with_stats(stats, 8, launch) == "y" and stats == [bn] and calls[-1] == {}
+    with B.routing(bn_stats_in_gemm=True):
+        assert B._with_stats(stats, 16, launch) == "y" and stats == [bn] and calls[-1] == {}      # another width: not this layer's
+        assert B._with_stats(stats, 8, launch) == "y"
+    assert calls[-1] == {"stat_shift": shift} and len(stats) == 4
+    assert stats[0] == "partial" and stats[1] == 7 and stats[2] is shift and stats[3] is bn
+    y = B._attach_stats(torch.zeros(1), stats)
+    assert y._peclr_bn_stats[3] is bn
+
+
+def test_bn_backward_hand_over_eligibility_and_what_it_parks():
+    """bn2d._with_bn_bwd, the one place an input-gradient launch is offered the backward reduction of the BatchNorm layer its
+    result arrives at: no link, another shape, a channel count that is not whole 32-bit mask words (and, for the 16-bit sites,
+    another dtype) -> `launch()` without `bn_bwd`; else `launch(bn_bwd=link[:5])` and the sums are parked under dx's address
+    with the link's token and dx's version."""
+    from peclr_amd import bn2d as B
+
+    calls = []
+    x = torch.zeros(2, 64, 3, 3)
+    dx = torch.ones(2, 64, 3, 3)
+
+    def launch(**kw):
+        calls.append(kw)
+        return (dx, "partial", 5) if "bn_bwd" in kw else dx
+
+    token = object()
+    link = (torch.zeros(2, 64, 3, 3), "save", "ss", None, True, token)
+    B.end_backward()
+    try:
+        assert B._with_bn_bwd(None, x, launch) is dx
+        assert B._with_bn_bwd((torch.zeros(2, 64, 3, 4),) + link[1:], x, launch) is dx                      # shape mismatch
+        x48 = torch.zeros(2, 48, 3, 3)
+        assert B._with_bn_bwd((x48,) + link[1:], x48, launch) is dx                                        # cin % 32 != 0
+        assert B._with_bn_bwd((link[0].half(),) + link[1:], x, launch, same_dtype=True) is dx              # 16-bit sites: dtype
+        assert calls == [{}, {}, {}, {}] and not B._BN_BWD_STATS
+        assert B._with_bn_bwd(link, x, launch, same_dtype=True) is dx
+        assert list(calls[-1]) == ["bn_bwd"] and calls[-1]["bn_bwd"] == link[:5]
+        assert B._BN_BWD_STATS == {dx.data_ptr(): (token, "partial", 5, dx._version)}
+        B._BN_BWD_STATS.clear()
+        assert B._with_bn_bwd((link[0].half(),) + link[1:], x, launch) is dx and "bn_bwd" in calls[-1]      # fp32 sites: no dtype test
+        assert B._BN_BWD_STATS[dx.data_ptr()][0] is token
+    finally:
+        B.end_backward()
+
+
+def test_side_stream_helper_runs_inline_and_parks_nothing_without_an_armed_stream():
+    """bn2d._on_side_stream: with no side stream armed (and for a gradient nobody is to be handed: param None) the weight
+    gradient is computed in place and returned, nothing is parked and the parked-form hook is not applied."""
+    from peclr_amd import bn2d as B
+
+    assert B._overlap_stream() is None and not B._WgradOverlap.parked
+    param = torch.nn.Parameter(torch.zeros(3))
+    g = torch.ones(3)
+    hooked = []
+    assert B._on_side_stream(param, (g, g), lambda: g, parked_as=hooked.append) is g
+    assert B._on_side_stream(None, (g, g), lambda: g) is g
+    assert not B._WgradOverlap.parked and not hooked
+    # the stock weight gradient goes through it: MIOpen's / the CPU's gradient, returned in the weight's dtype
+    conv = torch.nn.Conv2d(4, 6, 3, padding=1, bias=False)
+    xx = torch.randn(2, 4, 5, 5)
+    yy = conv(xx)
+    gy = torch.randn_like(yy)
+    (ref,) = torch.autograd.grad(yy, conv.weight, gy)
+    assert torch.allclose(B._conv_wgrad(gy, xx, conv.weight.detach(), (1, 1), (1, 1), conv.weight), ref, atol=1e-5)
+    assert not B._WgradOverlap.parked
+
+
+def test_packed_planes_are_repacked_when_the_weight_moved_and_not_otherwise(monkeypatch):
+    """bn2d._PackedOnce (the freshness rule of X6PackGroup's plane sets and of the stem's filter planes): built once, packed on
+    the first request, again after an in-place update of the weight (`_version`), after a fused optimiser launch
+    (`_capi.WEIGHTS_EPOCH`) and for new storage (`data_ptr`: built anew) -- and not otherwise; while a hipGraph is being captured,
+    the first request of that capture packs whatever the stamps say, and planes that do not exist cannot be created."""
+    from peclr_amd import _capi
+    from peclr_amd import bn2d as B
+
+    capture = [0]
+    monkeypatch.setattr(_capi, "capture_id", lambda: capture[0])
+    monkeypatch.setattr(_capi, "WEIGHTS_EPOCH", 0)
+    built = []
+
+    class Planes:
+        def __init__(self):
+            self.packs = 0
+            built.append(self)
+
+        def pack(self):
+            self.packs += 1
+
+    w0, w1 = torch.zeros(4), torch.zeros(4)
+    st = B._PackedOnce()
+
+    def ask(at, ws):
+        return st.fresh(ws[at], at, lambda: st.pack(ws, Planes, "cannot be created while capturing"))
+
+    ws = [w0, w1]
+    p = ask(0, ws)
+    assert p is built[0] and len(built) == 1 and p.packs == 1
+    assert ask(0, ws) is p and ask(1, ws) is p and p.packs == 1             # nothing moved: no launch
+    w1.add_(1.0)                                                            # in-place update of ONE member ...
+    assert ask(0, ws) is p and p.packs == 1                                 # ... is noticed when THAT member asks
+    assert ask(1, ws) is p and p.packs == 2 and ask(1, ws) is p and p.packs == 2
+    monkeypatch.setattr(_capi, "WEIGHTS_EPOCH", 1)                          # fused optimiser step: raw-pointer writes
+    assert ask(0, ws) is p and p.packs == 3 and ask(1, ws) is p and p.packs == 3
+    capture[0] = 11                                                         # a capture begins: its first request packs ...
+    assert ask(0, ws) is p and p.packs == 4 and ask(1, ws) is p and p.packs == 4       # ... once
+    capture[0] = 12
+    assert ask(1, ws) is p and p.packs == 5
+    ws2 = [w0, torch.zeros(4)]                                              # new storage: cannot be built while capturing
+    with pytest.raises(_capi.PeclrHipError, match="cannot be created while capturing"):
+        ask(1, ws2)
+    capture[0] = 0
+    q = ask(1, ws2)
+    assert q is built[1] and len(built) == 2 and q.packs == 1 and p.packs == 5
+    # X6PackGroup and the stem ask through it, with the messages users of capture_step_graph see
+    assert "while a hipGraph is being captured" in B.X6PackGroup.MISSING and B.X6PackGroup.MISSING.startswith("X6PackGroup: ")
+    assert "while a hipGraph is being captured" in B.Conv2d.STEM_MISSING and B.Conv2d.STEM_MISSING.startswith("stem: ")
+
+
+def test_nhwc_row_views_and_entry_addend_keywords():
+    """bn2d._rows / _nchw are views of the same storage and inverse to each other; bn2d._entry_addend turns the identity
+    branch's gradient -- dense, compact stride-2, or (dy, mask) -- into the entry GEMM's addend keywords."""
+    from peclr_amd import bn2d as B
+
+    x = torch.randn(2, 8, 3, 5).contiguous(memory_format=torch.channels_last)
+    r = B._rows(x)
+    assert tuple(r.shape) == (30, 8) and r.data_ptr() == x.data_ptr() and r.is_contiguous()
+    assert torch.equal(r, x.permute(0, 2, 3, 1).reshape(30, 8))
+    back = B._nchw(r, 2, 3, 5)
+    assert back.data_ptr() == x.data_ptr() and torch.equal(back, x) and back.is_contiguous(memory_format=torch.channels_last)
+    gid = torch.randn(2, 8, 3, 5)                                            # NCHW-contiguous: made channels_last first
+    kw = B._entry_addend(gid, None, x)
+    assert list(kw) == ["addend"] and torch.equal(kw["addend"], gid.permute(0, 2, 3, 1).reshape(30, 8))
+    dc = torch.zeros(8, 8)
+    kw = B._entry_addend(gid, ("s2", dc), x)
+    assert kw["addend"] is dc and kw["addend_s2"] == (3, 5) and len(kw) == 2
+    mask = torch.zeros(30, 1, dtype=torch.int32)
+    kw = B._entry_addend(gid, ("mask", x, mask), x)
+    assert kw["addend"].data_ptr() == x.data_ptr() and tuple(kw["addend"].shape) == (30, 8) and kw["addend_mask"] is mask
