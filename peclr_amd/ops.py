@@ -66,7 +66,10 @@ class _HeadAlign(torch.autograd.Function):
         hid, d = w1.shape[0], w2.shape[0]
         ss = None
         sync = bn.sync_group if bn.training else None
-        if m <= _REGISTER_BN_MAX_ROWS and sync is None:
+        # (the streaming kernels take the ResNet widths only -- H / 4 a divisor or a multiple of 256; any other hidden width
+        # stays on the bn_relu kernels, whose strided instance takes any number of rows)
+        streams = _capi.lib().peclr_bn2d_n_split(m, hid, _capi.DTYPE_F32) > 0
+        if (m <= _REGISTER_BN_MAX_ROWS or not streams) and sync is None:
             # K1: a = h W1^T  (split-K slabs; bias and the slab reduction are fused into the BN kernel,
             # which keeps its rows in registers)
             a_slabs = _as_slabs(_capi.gemm(_capi.GEMM_NT, h, w1, split_k=_capi.pick_split_k(m, hid, din),
