@@ -679,6 +679,39 @@ int peclr_pose_head_f32(const float* feat, int B, int n_feat, const float* fc_w,
                         const double* T1, double* T2, int S, const double* scale, double* fh, int* status,
                         peclr_stream_t stream);
 
+/* Scoring pose predictions (reference src/experiments/evaluation_utils.py: calculate_epe_statistics, calc_procrustes_transform,
+ * get_pck_curves), csrc/pose_eval.hip; host side: peclr_amd/pose_eval.py.  One launch for a batch.
+ *
+ * peclr_pose_eval: pred, gt [B][21][3], both of `dtype` (PECLR_DTYPE_F32 or PECLR_DTYPE_F64; so is every floating-point
+ *   output and thr).  dim = 3, or 2: only x and y enter the distance and the five Procrustes outputs must be NULL.
+ *   dist [B][21]: the Euclidean distance per joint, float64 arithmetic, rounded once.
+ *   Procrustes alignment of pred onto gt (calc_procrustes_transform(X = gt, Y = pred)), run when at least one of its outputs
+ *   is given, each of them nullable: aligned [B][21][3] (y_transform), rot [B][3][3], scale [B], trans [B][3],
+ *   dist_aligned [B][21] = the distance of the ROUNDED aligned cloud to gt.  float64 arithmetic whatever the dtype (one-sided
+ *   Jacobi SVD of the 3 x 3 covariance, reflection fix on the last singular pair), one rounding on output.
+ *   PCK: thr [n_thr] thresholds, counts [2][21][n_thr] 64-bit integers that are ADDED to: counts[0][j][k] += #{b : dist[b][j] <
+ *   thr[k]}, counts[1] the same for dist_aligned (only when the alignment runs); the comparison is made in `dtype` on the
+ *   values written out, NaN is never under a threshold.  n_thr = 0: no counting (thr, counts may be NULL).
+ *   status [B] int32, OR-ed into: PECLR_POSE_STATUS_NAN when a coordinate that enters the distance is NaN,
+ *   PECLR_POSE_EVAL_DEGENERATE when the alignment runs and the centred norm of gt or pred is 0 or not finite -- the sample's
+ *   Procrustes outputs are then NaN (the reference's 0 / 0), no other sample is touched.
+ *   Streaming (cursor != NULL): cursor is a DEVICE int[2] = {rows filled so far, 0}; dist, dist_aligned and status are
+ *   buffers of `capacity` rows and sample b goes to row cursor[0] + b; the launch itself advances cursor[0] by B when its
+ *   last workgroup finishes, so a hipGraph that captured the launch fills consecutive rows on every replay.  A launch whose
+ *   rows would not fit writes nothing (no counts either) and still advances: the host finds cursor[0] > capacity.
+ *   aligned / rot / scale / trans are per-launch outputs and never offset.  Every launch that shares a cursor must be
+ *   ordered on ONE stream (or one captured graph): two such launches in flight at once would read the same cursor[0] and
+ *   draw tickets from the same counter.
+ *   A sample's outputs are a pure function of that sample: the same bits alone, at any position of any batch, run to run.
+ *   Every argument error is reported as -1 before any launch: B <= 0, NULL pred / gt / dist / status, unknown dtype, dim not
+ *   2 or 3, dim = 2 with a Procrustes output, n_thr < 0, n_thr > 2^20, n_thr > 0 with NULL thr or counts, cursor with
+ *   capacity <= 0 or B > capacity.                                                                                     */
+#define PECLR_DTYPE_F64 3
+#define PECLR_POSE_EVAL_DEGENERATE 4
+int peclr_pose_eval(const void* pred, const void* gt, int B, int dtype, int dim, void* dist, void* aligned, void* rot, void* scale,
+                    void* trans, void* dist_aligned, const void* thr, int n_thr, long long* counts, int* status, int* cursor,
+                    int capacity, peclr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -116,6 +116,7 @@ SIGNATURES = {
     "peclr_pose_crop_u8": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P]),
     "peclr_pose_head_f32": (c_int, [_P, c_int, c_int, _P, _P, _P, c_float, c_float, _P, c_int, c_float, _P, _P, _P, _P, c_int,
                                     _P, _P, _P, _P]),
+    "peclr_pose_eval": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, c_int, _P]),
 }
 
 
@@ -1520,3 +1521,69 @@ def pose_head(feat: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, mlp, b
                                        _ptr(status, torch.int32, "pose_head status"), _stream())
     _check(rc, "peclr_pose_head_f32")
     return out64, kp3d, T2, fh, status
+
+
+# ------------------------------------------------------------------ scoring pose predictions (peclr_amd/pose_eval.py)
+DTYPE_F64 = 3
+POSE_EVAL_DEGENERATE = 4
+_EVAL_DTYPES = {torch.float32: DTYPE_F32, torch.float64: DTYPE_F64}
+
+
+def pose_eval(pred: torch.Tensor, gt: torch.Tensor, dim: int = 3, procrustes: bool = True, thr: Optional[torch.Tensor] = None,
+              counts: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None, dist: Optional[torch.Tensor] = None,
+              dist_aligned: Optional[torch.Tensor] = None, cursor: Optional[torch.Tensor] = None, want_transform: bool = True):
+    """pred, gt [B,21,3], both float32 or both float64 -> dict(dist [B,21], status [B] int32 and, with `procrustes`,
+    dist_aligned [B,21], aligned [B,21,3], rot [B,3,3], scale [B], trans [B,3] (the last four only with `want_transform`)).
+    thr [T] of the same dtype with counts [2,21,T] int64: PCK counts are ADDED to `counts`.  status is OR-ed into (zeros when
+    not given).  Streaming: cursor = int32 [2] device tensor {rows filled, 0}, dist / dist_aligned / status then are
+    [capacity, ...] buffers filled from row cursor[0], which the launch advances by B.  One launch."""
+    for t, what in ((pred, "pred"), (gt, "gt")):
+        if not t.is_cuda or t.dtype not in _EVAL_DTYPES or t.dim() != 3 or tuple(t.shape[1:]) != (21, 3) or not t.is_contiguous():
+            raise PeclrHipError(f"pose_eval: {what} must be a contiguous [B,21,3] float32 / float64 HIP tensor, got {t.dtype} "
+                                f"{tuple(t.shape)} on {t.device} (peclr_amd has no CPU path)")
+    if pred.dtype != gt.dtype or pred.shape != gt.shape:
+        raise PeclrHipError(f"pose_eval: pred {pred.dtype} {tuple(pred.shape)} and gt {gt.dtype} {tuple(gt.shape)} differ")
+    if dim == 2 and procrustes:
+        raise PeclrHipError("pose_eval: the Procrustes alignment needs dim = 3")
+    b, dt, dev = pred.shape[0], pred.dtype, pred.device
+    rows = b
+    if cursor is not None:
+        if dist is None or status is None or (procrustes and dist_aligned is None):
+            raise PeclrHipError("pose_eval: the streaming form needs the dist / dist_aligned / status buffers")
+        rows = dist.shape[0]
+        _ptr(cursor, torch.int32, "pose_eval cursor")
+        if tuple(cursor.shape) != (2,):
+            raise PeclrHipError("pose_eval: cursor must be int32 [2]")
+    if dist is None:
+        dist = torch.empty((rows, 21), device=dev, dtype=dt)
+    if status is None:
+        status = torch.zeros((rows,), device=dev, dtype=torch.int32)
+    if procrustes and dist_aligned is None:
+        dist_aligned = torch.empty((rows, 21), device=dev, dtype=dt)
+    for t, what in ((dist, "dist"), (dist_aligned, "dist_aligned")):
+        if t is not None and tuple(t.shape) != (rows, 21):
+            raise PeclrHipError(f"pose_eval: {what} must be [{rows},21], got {tuple(t.shape)}")
+    if tuple(status.shape) != (rows,):
+        raise PeclrHipError(f"pose_eval: status must be [{rows}] int32, got {tuple(status.shape)}")
+    n_thr = 0
+    if thr is not None:
+        n_thr = thr.numel()
+        if counts is None or tuple(counts.shape) != (2, 21, n_thr) or thr.dim() != 1:
+            raise PeclrHipError(f"pose_eval: counts must be int64 [2,21,{n_thr}] next to thr [{n_thr}]")
+    aligned = rot = scale = trans = None
+    if procrustes and want_transform:
+        aligned = torch.empty((b, 21, 3), device=dev, dtype=dt)
+        rot = torch.empty((b, 3, 3), device=dev, dtype=dt)
+        scale = torch.empty((b,), device=dev, dtype=dt)
+        trans = torch.empty((b, 3), device=dev, dtype=dt)
+    with _timed("pose_eval", 2 * pred.numel() * pred.element_size()):
+        rc = lib().peclr_pose_eval(pred.data_ptr(), gt.data_ptr(), b, _EVAL_DTYPES[dt], int(dim), _ptr(dist, dt, "pose_eval dist"),
+                                   _ptr(aligned, dt), _ptr(rot, dt), _ptr(scale, dt), _ptr(trans, dt),
+                                   _ptr(dist_aligned if procrustes else None, dt, "pose_eval dist_aligned"),
+                                   _ptr(thr, dt, "pose_eval thresholds") if n_thr else None, n_thr,
+                                   _ptr(counts, torch.int64, "pose_eval counts") if n_thr else None,
+                                   _ptr(status, torch.int32, "pose_eval status"),
+                                   cursor.data_ptr() if cursor is not None else None, rows if cursor is not None else 0, _stream())
+    _check(rc, "peclr_pose_eval")
+    return {"dist": dist, "dist_aligned": dist_aligned if procrustes else None, "aligned": aligned, "rot": rot, "scale": scale,
+            "trans": trans, "status": status}
