@@ -11,7 +11,7 @@
 //     eight 1 KiB pieces [32-column block][k-half of 16], a piece being lane l's 16 bytes at l * 16 = column n0 + (l & 31),
 //     k = k0 + 8 (l >> 5) .. + 7;
 //   * A: every wave owns 32 * WM rows x all output columns of the workgroup tile, and brings ITS rows in itself: one
-//     `global_load_lds_dwordx4` moves 16 rows x 64 bytes (32 k), four lanes per row, into a wave-private [row][4 x 16 B]
+//     `lds_dma16` moves 16 rows x 64 bytes (32 k), four lanes per row, into a wave-private [row][4 x 16 B]
 //     image whose 16-byte slots are XOR-swizzled by (row >> 2) & 3 -- the DMA writes lane-linear, so the swizzle is applied
 //     to the GLOBAL address each lane fetches -- which makes the MFMA fragment reads (ds_read_b128, row pitch 64 B)
 //     bank-conflict free.
@@ -22,46 +22,16 @@
 
 #include <type_traits>
 
-#include "common.hpp"
+#include "mfma.hpp"
 
 #include <cstddef>
 
 namespace peclr {
 namespace {
 
-typedef uint16_t h16_t;                  // storage of both 16-bit formats
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
-
 constexpr int HN = 128;                  // output columns per packed chunk
 constexpr int HK = 32;                   // k per step (two MFMA k-extents)
 constexpr int HCHUNK = 8 * 1024;         // bytes of packed W per (128 columns, 32 k)
-
-struct BF16 {
-    static constexpr int io = PECLR_DTYPE_BF16;
-    static __device__ __forceinline__ f32x16 mma(const uint4& a, const uint4& b, f32x16 acc) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-    }
-    static __device__ __forceinline__ float up(unsigned lo16) { return __uint_as_float(lo16 << 16); }
-    static __device__ __forceinline__ float lo(unsigned w) { return __uint_as_float(w << 16); }           // the two halves of a word,
-    static __device__ __forceinline__ float hi(unsigned w) { return __uint_as_float(w & 0xFFFF0000u); }   // one instruction each
-    static __device__ __forceinline__ unsigned pack2(float a, float b) { return pk_bf16(a, b); }          // round to nearest even
-};
-struct F16 {
-    static constexpr int io = PECLR_DTYPE_F16;
-    static __device__ __forceinline__ f32x16 mma(const uint4& a, const uint4& b, f32x16 acc) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
-    }
-    static __device__ __forceinline__ float up(unsigned lo16) { return (float)__builtin_bit_cast(_Float16, (unsigned short)lo16); }
-    static __device__ __forceinline__ float lo(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)w); }
-    static __device__ __forceinline__ float hi(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
-    static __device__ __forceinline__ unsigned pack2(float a, float b) {
-        const f32x2_t v = {a, b};
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2v));
-    }
-};
 
 struct HArgs {
     const h16_t* A;
@@ -89,32 +59,13 @@ struct HArgs {
     int stream_out;                      // the output (and its addend) is larger than the caches: non-temporal epilogue
 };
 
-// 16 bytes per lane, global -> LDS at (wave-uniform) dst + lane * 16 (inline assembly: see gemm_x6p.hip -- through the
-// builtin hipcc makes every later ds_read wait for the DMA; here every wait on the vm counter is written by hand)
-__device__ __forceinline__ void hdma16(const void* src, unsigned lds_byte_offset) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
-                 :: "v"(src), "s"(lds_byte_offset) : "memory", "m0");
-}
+// (H below: mfma.hpp's BF16 / F16.  Both operands arrive through its lds_dma16 family: every wait on the vm counter is written
+// by hand)
 // A/B builds: bit 0 = the activation rows of 1x1 products with ONE column tile are fetched with the non-temporal hint.  Measured
 // slower (round 5, same box, bf16: conv1x1_dgrad 74 -> 82 us, conv1x1_fwd 70 -> 72): off
 #ifndef PECLR_CONVH_NT
 #define PECLR_CONVH_NT 0
 #endif
-__device__ __forceinline__ void hdma16_nt(const void* src, unsigned lds_byte_offset) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off nt"
-                 :: "v"(src), "s"(lds_byte_offset) : "memory", "m0");
-}
-
-// ... the same with a wave-uniform 64-bit base (scalar registers) + a 32-bit lane offset + an immediate: no vector arithmetic
-// per request.  The instruction's immediate offset is added to the global address AND to the LDS address (M0 + offset +
-// lane * 16): piece k of a contiguous run is (same base, same M0, offset k * 1024)
-template <int IMM>
-__device__ __forceinline__ void hdma16s(const void* sbase, unsigned lane_off, unsigned lds_byte_offset) {
-    // (s_nop 4: the base may come straight from scalar arithmetic -- a vector memory instruction reading a scalar register the
-    // scalar unit has just written needs five wait states, and the compiler does not see into this string)
-    asm volatile("s_nop 4\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 offset:%3"
-                 :: "v"(lane_off), "s"(sbase), "s"(lds_byte_offset), "n"(IMM) : "memory", "m0");
-}
 
 // WM: 32-row MFMA tiles per wave (2 -> 256-row workgroup tile, 1 -> 128); NTL: 32-column tiles per wave (4 -> 128 output
 // columns per workgroup, 2 -> 64); TAPS = 9: 3x3 / padding 1 as an implicit GEMM, K ordered (tap, channel)
@@ -169,8 +120,10 @@ __global__ __launch_bounds__(256, (WM == 1 && RING == 0) ? ((EP & 2) ? 3 : 4) : 
 
     constexpr int PNL = 32 * NTL;
     const int nct = (g.N + PNL - 1) / PNL;
+    // XCD-aware tile order, as mfma.hpp xcd_tile -- written out: through the helper hipcc swaps the operands of one scalar multiply
+    // in the 3x3 instantiations
     const int j = blockIdx.x / 8;
-    const int row_block = 8 * (j / nct) + (int)(blockIdx.x % 8);      // all column tiles of a row block on one XCD
+    const int row_block = 8 * (j / nct) + (int)(blockIdx.x % 8);
     const int Wp = g.W + 1, Hp = g.H + 1;                             // (RING) the padded image
     if (row_block * TM >= (RING ? g.Mp : g.M)) return;
     auto ring_row = [&](int p) -> int {                               // padded pixel -> row of the NHWC tensor, -1: a zero
@@ -258,16 +211,16 @@ __global__ __launch_bounds__(256, (WM == 1 && RING == 0) ? ((EP & 2) ? 3 : 4) : 
         const unsigned char* s = bsrc + (size_t)bt_step * HCHUNK;
         const unsigned d = lds0 + B0 + (step % NSB) * BSZ;
         if constexpr (NTL == 4) {
-            hdma16(s + (2 * wave_s) * 1024, d + (2 * wave_s) * 1024);
-            hdma16(s + (2 * wave_s + 1) * 1024, d + (2 * wave_s + 1) * 1024);
+            lds_dma16(s + (2 * wave_s) * 1024, d + (2 * wave_s) * 1024);
+            lds_dma16(s + (2 * wave_s + 1) * 1024, d + (2 * wave_s + 1) * 1024);
         } else {
-            hdma16(s + wave_s * 1024, d + wave_s * 1024);
+            lds_dma16(s + wave_s * 1024, d + wave_s * 1024);
         }
     };
     auto issue_ring = [&](int chunk) {                    // RING: this wave's rows of the 32-channel chunk -> stage chunk & 1
         const unsigned st = lds0 + (chunk & 1) * ASZ;
 #pragma unroll
-        for (int c = 0; c < NA; ++c) hdma16(asrc[c] ? asrc[c] + chunk * HK : zsrc, st + 16 * (wave_s * NA + c) * 64);
+        for (int c = 0; c < NA; ++c) lds_dma16(asrc[c] ? asrc[c] + chunk * HK : zsrc, st + 16 * (wave_s * NA + c) * 64);
     };
     auto issue_a = [&](int t) {                           // this wave's rows of step t -> activation stage t % NSA
         const unsigned st = lds0 + (t % NSA) * ASZ;
@@ -290,10 +243,10 @@ __global__ __launch_bounds__(256, (WM == 1 && RING == 0) ? ((EP & 2) ? 3 : 4) : 
             const h16_t* src = asrc[c] + off;
             if constexpr (TAPS == 9) src = (tapmask[c] >> tap) & 1u ? src : zsrc;
 #if PECLR_CONVH_NT & 1
-            if (TAPS == 1 && nct == 1) hdma16_nt(src, st + (wave_s * RM + 16 * c) * 64);   // (no other workgroup reads these rows)
+            if (TAPS == 1 && nct == 1) lds_dma16_nt(src, st + (wave_s * RM + 16 * c) * 64);   // (no other workgroup reads these rows)
             else
 #endif
-            hdma16(src, st + (wave_s * RM + 16 * c) * 64);
+            lds_dma16(src, st + (wave_s * RM + 16 * c) * 64);
         }
     };
 
@@ -356,16 +309,16 @@ __global__ __launch_bounds__(256, (WM == 1 && RING == 0) ? ((EP & 2) ? 3 : 4) : 
         auto request_w = [&](int chunk, int tap, int stage) {
             const unsigned char* src = wbase + (size_t)((unsigned)tap * tap_stride) + (size_t)chunk * HCHUNK;
             const unsigned d = wlds + stage * BSZ;
-            hdma16s<0>(src, lane16, d);
-            if constexpr (NTL == 4) hdma16s<1024>(src, lane16, d);      // (the immediate moves BOTH addresses)
+            lds_dma16s<0>(src, lane16, d);
+            if constexpr (NTL == 4) lds_dma16s<1024>(src, lane16, d);      // (the immediate moves BOTH addresses)
         };
         auto step = [&](auto tapc, int chunk) {
             constexpr int tap = decltype(tapc)::value;
             const bool last_chunk = chunk + 1 == kpt;
-            if (tap + NSB - 1 > 9 && last_chunk) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (tap == 0 && chunk == 0) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N0 + NE) : "memory");
-            else if (tap >= 1 && tap <= NSB - 1 && !last_chunk) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N0 + NA) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N0) : "memory");
+            if (tap + NSB - 1 > 9 && last_chunk) wait_vmcnt<0>();
+            else if (tap == 0 && chunk == 0) wait_vmcnt<N0 + NE>();
+            else if (tap >= 1 && tap <= NSB - 1 && !last_chunk) wait_vmcnt<N0 + NA>();
+            else wait_vmcnt<N0>();
             __builtin_amdgcn_s_barrier();                 // publishes W chunk s (and the stage); every wave is done with step s - 1
             asm volatile("" ::: "memory");
             const unsigned char* sa = lds + (chunk & 1) * ASZ + aoff[tap];
@@ -411,10 +364,10 @@ __global__ __launch_bounds__(256, (WM == 1 && RING == 0) ? ((EP & 2) ? 3 : 4) : 
         // A(t), B(t) have landed: younger than them are at most the NA row DMAs of A(t + 1) -- and, in step 0, the NE
         // constant loads issued behind the first stages
         if (t == 0) {
-            if (nk > 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NA + NE) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NE) : "memory");
-        } else if (t + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NA) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (nk > 1) wait_vmcnt<NA + NE>();
+            else wait_vmcnt<NE>();
+        } else if (t + 1 < nk) wait_vmcnt<NA>();
+        else wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();                     // publishes A(t), B(t); every wave is done reading step t - 1
         asm volatile("" ::: "memory");
         if (t + 1 < nk) issue_b(t + 1, t + 1);            // into the W buffer step t - 1 read
@@ -549,7 +502,6 @@ __global__ __launch_bounds__(256, (WM == 1 && RING == 0) ? ((EP & 2) ? 3 : 4) : 
                         arow = ((size_t)img * (g.add_h >> 1) + (h >> 1)) * (g.add_w >> 1) + (w >> 1);
                     }
                     if (has) {
-                        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
                         const u32x4* asrc4 = reinterpret_cast<const u32x4*>(g.addend + arow * g.ldd + nt + ec);
                         const u32x4 tv = g.stream_out ? __builtin_nontemporal_load(asrc4) : *asrc4;
                         dv[jj] = make_uint4(tv[0], tv[1], tv[2], tv[3]);
@@ -592,7 +544,6 @@ __global__ __launch_bounds__(256, (WM == 1 && RING == 0) ? ((EP & 2) ? 3 : 4) : 
                 for (int q = 0; q < 4; ++q) ow[q] = H::pack2(c[2 * q], c[2 * q + 1]);
                 if (om[a][jj] >= 0) {
                     {
-                        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
                         u32x4* dst4 = reinterpret_cast<u32x4*>(g.out + (size_t)om[a][jj] * g.ldo + nt + ec);
                         const u32x4 tv = {ow[0], ow[1], ow[2], ow[3]};
                         if (g.stream_out) __builtin_nontemporal_store(tv, dst4);

@@ -14,14 +14,12 @@
 // addend is read and the output written exactly once.
 #include <stdlib.h>
 
-#include "common.hpp"
+#include "mfma.hpp"
 
 namespace peclr {
 namespace {
 
-typedef uint16_t bf16_t;   // storage type of BOTH 16-bit formats in this file
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef h16_t bf16_t;      // storage type of BOTH 16-bit formats in this file
 
 constexpr int BM = 64, BN = 64, BKH = 64;     // BKH: bf16 elements per K-tile
 constexpr int LDH = BKH + 8;                  // 72 bf16 = 36 dwords per LDS row
@@ -59,26 +57,17 @@ __device__ __forceinline__ bf16_t f32_to_bf16(float f) {  // round to nearest ev
     return (bf16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
 }
 
-// per-format pieces: MFMA, 16-bit -> fp32, fp32 -> 16-bit (round to nearest even)
-struct BF16 {
-    static __device__ __forceinline__ f32x16 mma(const bf16_t* pa, const bf16_t* pb, f32x16 acc) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(pa), *reinterpret_cast<const bf16x8*>(pb),
-                                                      acc, 0, 0, 0);
-    }
-    static __device__ __forceinline__ float up(unsigned lo16) { return __uint_as_float(lo16 << 16); }
-    static __device__ __forceinline__ unsigned down(float f) { return f32_to_bf16(f); }
-};
-struct F16 {
-    static __device__ __forceinline__ f32x16 mma(const bf16_t* pa, const bf16_t* pb, f32x16 acc) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(pa), *reinterpret_cast<const f16x8*>(pb),
-                                                     acc, 0, 0, 0);
-    }
-    static __device__ __forceinline__ float up(unsigned lo16) {
-        const unsigned short h = (unsigned short)lo16;
-        return (float)__builtin_bit_cast(_Float16, h);
-    }
-    static __device__ __forceinline__ unsigned down(float f) { return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)f); }
-};
+// this file's own per-format pieces on top of mfma.hpp's BF16 / F16 (H): the MFMA on two fragments in the LDS, and fp32 -> 16-bit
+// of ONE number (round to nearest even)
+template <typename H>
+__device__ __forceinline__ f32x16 mma_at(const bf16_t* pa, const bf16_t* pb, f32x16 acc) {
+    return H::mma(*reinterpret_cast<const uint4*>(pa), *reinterpret_cast<const uint4*>(pb), acc);
+}
+template <typename H>
+__device__ __forceinline__ unsigned down(float f) {
+    if constexpr (H::io == PECLR_DTYPE_BF16) return f32_to_bf16(f);
+    else return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)f);
+}
 
 template <typename H>
 __global__ __launch_bounds__(256) void gemm_bf16_nt_add_kernel(GemmHArgs g) {
@@ -87,12 +76,11 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_add_kernel(GemmHArgs g) {
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int i = lane & 31, kh = lane >> 5;
-    // XCD-aware tile order (see gemm_f32.hip): all column tiles of a row block on one XCD
     const int nct = (g.N + BN - 1) / BN;
-    const int j = blockIdx.x / 8;
-    const int row_block = 8 * (j / nct) + (int)(blockIdx.x % 8);
+    const XcdTile tile = xcd_tile(blockIdx.x, nct);
+    const int row_block = tile.row_block;
     if (row_block * BM >= g.M) return;
-    const int m0 = row_block * BM, n0 = (j % nct) * BN;
+    const int m0 = row_block * BM, n0 = tile.col_tile * BN;
     const int nk = (g.K + BKH - 1) / BKH;
 
     f32x16 acc;
@@ -129,7 +117,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_add_kernel(GemmHArgs g) {
         const bf16_t* tb = lds[cur][1];
 #pragma unroll
         for (int t = 0; t < BKH / 16; ++t) {
-            acc = H::mma(ta + (wm * 32 + i) * LDH + 16 * t + 8 * kh, tb + (wn * 32 + i) * LDH + 16 * t + 8 * kh, acc);
+            acc = mma_at<H>(ta + (wm * 32 + i) * LDH + 16 * t + 8 * kh, tb + (wn * 32 + i) * LDH + 16 * t + 8 * kh, acc);
         }
         if (more) {
             tile_store_h(lds[cur ^ 1][0], tid, ra);
@@ -149,14 +137,13 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_add_kernel(GemmHArgs g) {
         const float4 c1 = *reinterpret_cast<const float4*>(ct + (er + 32 * rep) * LDC + ec + 4);
         const float c[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
         const unsigned d[4] = {dw[rep].x, dw[rep].y, dw[rep].z, dw[rep].w};
-        typedef unsigned u4 __attribute__((ext_vector_type(4)));
-        u4 o;
+        u32x4 o;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float lo = c[2 * k] + H::up(d[k] & 0xFFFFu), hi = c[2 * k + 1] + H::up(d[k] >> 16);
-            o[k] = H::down(lo) | (H::down(hi) << 16);
+            o[k] = down<H>(lo) | (down<H>(hi) << 16);
         }
-        __builtin_nontemporal_store(o, reinterpret_cast<u4*>(g.out + (size_t)m * g.ldo + n));
+        __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(g.out + (size_t)m * g.ldo + n));
     }
 }
 
@@ -182,10 +169,10 @@ __global__ __launch_bounds__(256, 3) void gemm_h_nt128_add_kernel(GemmHArgs g, i
     const int wm = wave >> 1, wn = wave & 1;
     const int i = lane & 31, kh = lane >> 5;
     const int nct = (g.N + TNH - 1) / TNH;
-    const int j = blockIdx.x / 8;
-    const int row_block = 8 * (j / nct) + (int)(blockIdx.x % 8);      // all column tiles of a row block on one XCD
+    const XcdTile tile = xcd_tile(blockIdx.x, nct);
+    const int row_block = tile.row_block;
     if (row_block * TMH >= g.M) return;
-    const int m0 = row_block * TMH, n0 = (j % nct) * TNH;
+    const int m0 = row_block * TMH, n0 = tile.col_tile * TNH;
     const int nk = (g.K + BKH - 1) / BKH;
 
     f32x16 acc[2][2];
@@ -221,10 +208,10 @@ __global__ __launch_bounds__(256, 3) void gemm_h_nt128_add_kernel(GemmHArgs g, i
         for (int t = 0; t < BKH / 16; ++t) {
             const bf16_t* a0 = la + (wm * 64 + i) * LDH + 16 * t + 8 * kh;
             const bf16_t* b0 = lb + (wn * 64 + i) * LDH + 16 * t + 8 * kh;
-            acc[0][0] = H::mma(a0, b0, acc[0][0]);
-            acc[0][1] = H::mma(a0, b0 + 32 * LDH, acc[0][1]);
-            acc[1][0] = H::mma(a0 + 32 * LDH, b0, acc[1][0]);
-            acc[1][1] = H::mma(a0 + 32 * LDH, b0 + 32 * LDH, acc[1][1]);
+            acc[0][0] = mma_at<H>(a0, b0, acc[0][0]);
+            acc[0][1] = mma_at<H>(a0, b0 + 32 * LDH, acc[0][1]);
+            acc[1][0] = mma_at<H>(a0 + 32 * LDH, b0, acc[1][0]);
+            acc[1][1] = mma_at<H>(a0 + 32 * LDH, b0 + 32 * LDH, acc[1][1]);
         }
     };
     gload(0);
@@ -238,9 +225,8 @@ __global__ __launch_bounds__(256, 3) void gemm_h_nt128_add_kernel(GemmHArgs g, i
         __syncthreads();
     }
     // last K-tile: the addend travels under its MFMAs.  Lane -> row er (+16 s) of strip p, columns ec .. ec + 15.
-    typedef unsigned u4 __attribute__((ext_vector_type(4)));
     const int er = lane >> 2, ec = (lane & 3) * 16;
-    u4 dw[2][2][2];
+    u32x4 dw[2][2][2];
 #pragma unroll
     for (int p = 0; p < 2; ++p)
 #pragma unroll
@@ -248,9 +234,9 @@ __global__ __launch_bounds__(256, 3) void gemm_h_nt128_add_kernel(GemmHArgs g, i
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int m = m0 + wm * 64 + p * 32 + er + 16 * s2, n = n0 + wn * 64 + ec + 8 * h;
-                u4 v = {0u, 0u, 0u, 0u};
+                u32x4 v = {0u, 0u, 0u, 0u};
                 if (g.addend && m < g.M && n < g.N) {
-                    const u4* src = reinterpret_cast<const u4*>(g.addend + (size_t)m * g.ldd + n);
+                    const u32x4* src = reinterpret_cast<const u32x4*>(g.addend + (size_t)m * g.ldd + n);
                     v = stream_out ? __builtin_nontemporal_load(src) : *src;
                 }
                 dw[p][s2][h] = v;
@@ -275,15 +261,15 @@ __global__ __launch_bounds__(256, 3) void gemm_h_nt128_add_kernel(GemmHArgs g, i
                 const float4 c0 = *reinterpret_cast<const float4*>(wl + row * EPH + ec + 8 * h);
                 const float4 c1 = *reinterpret_cast<const float4*>(wl + row * EPH + ec + 8 * h + 4);
                 const float c[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-                const u4 d = dw[p][s2][h];
-                u4 o;
+                const u32x4 d = dw[p][s2][h];
+                u32x4 o;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const float lo = c[2 * k] + H::up(d[k] & 0xFFFFu), hi = c[2 * k + 1] + H::up(d[k] >> 16);
-                    o[k] = H::down(lo) | (H::down(hi) << 16);
+                    o[k] = down<H>(lo) | (down<H>(hi) << 16);
                 }
                 if (m < g.M && n < g.N) {
-                    u4* dst = reinterpret_cast<u4*>(g.out + (size_t)m * g.ldo + n);
+                    u32x4* dst = reinterpret_cast<u32x4*>(g.out + (size_t)m * g.ldo + n);
                     if (stream_out) __builtin_nontemporal_store(o, dst);
                     else *dst = o;
                 }

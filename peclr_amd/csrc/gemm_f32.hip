@@ -19,7 +19,7 @@
 // rule).
 #include <cstdlib>
 
-#include "common.hpp"
+#include "mfma.hpp"
 
 namespace peclr {
 namespace {
@@ -87,11 +87,8 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int i = lane & 31, kh = lane >> 5;
-    // XCD-aware tile order: the grid is 1-D (x), 8 * ceil(row blocks / 8) * column tiles.  Workgroups go to
-    // the 8 XCDs round-robin, so hardware block b runs row block 8 * (j / nct) + b % 8, column tile j % nct
-    // with j = b / 8: every column tile of a row block lands on the SAME XCD, one after the other, and the
-    // 64 x K operand tile they share is read from HBM once and from that XCD's L2 afterwards.
-    // With fewer than 8 row blocks (the projection head: M = 256 rows = 4 row blocks) that order would leave XCDs
+    // XCD-aware tile order (mfma.hpp xcd_tile): the column tiles of a row block share an XCD and its L2 copy of their 64 x K
+    // operand tile.  With fewer than 8 row blocks (the projection head: M = 256 rows = 4 row blocks) that order would leave XCDs
     // idle -- there the tiles are simply dealt out one by one (g.flat_tiles), which spreads them over all XCDs.
     const int nct = (g.N + BN - 1) / BN;
     int row_block, col_tile;
@@ -99,9 +96,9 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
         row_block = blockIdx.x / nct;
         col_tile = blockIdx.x % nct;
     } else {
-        const int j = blockIdx.x / 8;
-        row_block = 8 * (j / nct) + (int)(blockIdx.x % 8);
-        col_tile = j % nct;
+        const XcdTile tile = xcd_tile(blockIdx.x, nct);
+        row_block = tile.row_block;
+        col_tile = tile.col_tile;
     }
     if (row_block * BM >= g.M) return;
     const int m0 = row_block * BM, n0 = col_tile * BN;
@@ -200,10 +197,10 @@ __global__ __launch_bounds__(256, 4) void gemm_f32_nn128_kernel(GemmArgs g) {
     const int wm = wave >> 1, wn = wave & 1;
     const int i = lane & 31, kh = lane >> 5;
     const int nct = (g.N + TN - 1) / TN;
-    const int j = blockIdx.x / 8;
-    const int row_block = 8 * (j / nct) + (int)(blockIdx.x % 8);      // all column tiles of a row block on one XCD
+    const XcdTile tile = xcd_tile(blockIdx.x, nct);
+    const int row_block = tile.row_block;
     if (row_block * TM >= g.M) return;
-    const int m0 = row_block * TM, n0 = (j % nct) * TN;
+    const int m0 = row_block * TM, n0 = tile.col_tile * TN;
     const int nk = (g.K + BK - 1) / BK;
 
     f32x16 acc[2][2];

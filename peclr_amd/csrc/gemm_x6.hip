@@ -20,14 +20,12 @@
 // every addend load / store is 16 bytes per lane.
 #include <stdlib.h>
 
-#include "common.hpp"
+#include "mfma.hpp"
 
 namespace peclr {
 namespace {
 
-typedef uint16_t bf16_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef h16_t bf16_t;
 
 constexpr int XM = 128, XN = 128, XK = 32;
 constexpr int XLD = XK + 8;              // bf16 per LDS row: 80 bytes
@@ -52,9 +50,6 @@ __device__ __forceinline__ void split_store(bf16_t* planes, int offset, const fl
     *reinterpret_cast<uint2*>(planes + plane + offset) = make_uint2(m[0], m[1]);
     *reinterpret_cast<uint2*>(planes + 2 * plane + offset) = make_uint2(l[0], l[1]);
 }
-__device__ __forceinline__ f32x16 mma(const uint4& a, const uint4& b, f32x16 acc) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-}
 
 // NB = MFMA tiles per wave along N: 2 -> 128 x 128 workgroup tile; 1 -> 128 x 64 for outputs that are 64 wide (layer1's
 // 256 -> 64 convolutions: with the 128-wide tile half of every MFMA would multiply zeros and the HBM-bound shape
@@ -71,10 +66,10 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void gemm_x6_nt128_kernel(X6A
     const int wm = wave >> 1, wn = wave & 1;
     const int i = lane & 31, kh = lane >> 5;
     const int nct = (g.N + TNW - 1) / TNW;
-    const int j = blockIdx.x / 8;
-    const int row_block = 8 * (j / nct) + (int)(blockIdx.x % 8);      // all column tiles of a row block on one XCD
+    const XcdTile tile = xcd_tile(blockIdx.x, nct);
+    const int row_block = tile.row_block;
     if (row_block * XM >= g.M) return;
-    const int m0 = row_block * XM, n0 = (j % nct) * TNW;
+    const int m0 = row_block * XM, n0 = tile.col_tile * TNW;
     const int nk = (g.K + XK - 1) / XK;
 
     f32x16 acc[2][NB];
@@ -128,8 +123,8 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void gemm_x6_nt128_kernel(X6A
             // smallest products first; the accumulators are independent chains
 #define PECLR_X6(P, Q)                                                        \
     _Pragma("unroll") for (int y = 0; y < NB; ++y) {                          \
-        acc[0][y] = mma(a[0][P], b[y][Q], acc[0][y]);                         \
-        acc[1][y] = mma(a[1][P], b[y][Q], acc[1][y]);                         \
+        acc[0][y] = mma_bf16(a[0][P], b[y][Q], acc[0][y]);                         \
+        acc[1][y] = mma_bf16(a[1][P], b[y][Q], acc[1][y]);                         \
     }
             PECLR_X6(2, 0) PECLR_X6(0, 2) PECLR_X6(1, 1) PECLR_X6(1, 0) PECLR_X6(0, 1) PECLR_X6(0, 0)
 #undef PECLR_X6
@@ -285,8 +280,8 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void gemm_x6_tn128_kernel(X6A
             }
 #define PECLR_X6(P, Q)                                                        \
     _Pragma("unroll") for (int y = 0; y < NB; ++y) {                          \
-        acc[0][y] = mma(a[0][P], b[y][Q], acc[0][y]);                         \
-        acc[1][y] = mma(a[1][P], b[y][Q], acc[1][y]);                         \
+        acc[0][y] = mma_bf16(a[0][P], b[y][Q], acc[0][y]);                         \
+        acc[1][y] = mma_bf16(a[1][P], b[y][Q], acc[1][y]);                         \
     }
             PECLR_X6(2, 0) PECLR_X6(0, 2) PECLR_X6(1, 1) PECLR_X6(1, 0) PECLR_X6(0, 1) PECLR_X6(0, 0)
 #undef PECLR_X6

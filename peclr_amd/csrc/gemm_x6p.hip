@@ -8,7 +8,7 @@
 //     the fused entry gradient).  peclr_x6_pack_f32 splits it ONCE into three bf16 planes stored in MFMA fragment
 //     order -- per (128 output columns, 16 k) one contiguous 12 KiB chunk of twelve 1 KiB pieces [32-column block]
 //     [plane], a piece being lane l's 16 bytes at l * 16: columns n0 + (l & 31), k0 + 8 * (l >> 5) ... + 7.
-//     The GEMM brings a chunk into LDS with twelve `global_load_lds_dwordx4` (LDS-DMA: no VGPRs, no VALU, no
+//     The GEMM brings a chunk into LDS with twelve `lds_dma16` (mfma.hpp; LDS-DMA: no VGPRs, no VALU, no
 //     ds_write, lane-linear = fragment order, bank-conflict free) and reads B fragments with ds_read_b128.
 //   * The ACTIVATION operand still has to be split in the kernel (its producer is an HBM-bound BatchNorm pass that
 //     cannot afford 6 more bytes per element).  Each wave owns 32 * WM rows x all 128 columns of the workgroup tile
@@ -25,15 +25,12 @@
 // VGPR -> LDS port: 49 KiB per 1536 MFMA cycles) carries 24 KiB per 3072 MFMA cycles here.
 #include <type_traits>
 
-#include "common.hpp"
+#include "mfma.hpp"
 
 #include <cstddef>
 
 namespace peclr {
 namespace {
-
-typedef uint16_t bf16_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // A/B builds: bit 0 = the A rows of 1x1 products with ONE column tile, bit 1 = the epilogue's BatchNorm-x rows load with the non-temporal
 // hint.  Measured neutral (round 5, same box: every tag within 1 us; on ALL A rows, shared ones included: + 1.5 ms per step): these
@@ -99,25 +96,13 @@ struct X6PArgs {
     float* bb_partial;
 };
 
-__device__ __forceinline__ f32x16 mma(const uint4& a, const uint4& b, f32x16 acc) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-}
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-template <int NP>
+template <int NP>                         // the product of the bf16 triple's planes (3) / of the fp16 pair's (2)
 __device__ __forceinline__ f32x16 mman(const uint4& a, const uint4& b, f32x16 acc) {
-    if constexpr (NP == 3) return mma(a, b, acc);
-    else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
+    if constexpr (NP == 3) return mma_bf16(a, b, acc);
+    else return mma_f16(a, b, acc);
 }
-// 16 bytes per lane, global -> LDS at (wave-uniform) dst + lane * 16.  Issued through inline assembly on purpose: for
-// the builtin, hipcc's wait-count pass makes EVERY later ds_read wait for the DMA (vmcnt(0) right behind the issue --
-// LDS accesses carry no alias information that would tell the B buffer being filled from the one being read), which
-// serialises the pipeline.  Here the compiler does not know the instruction touches the vm counter; every wait on
-// it is written by hand below (and no other VMEM instruction is in flight while DMAs are).
-__device__ __forceinline__ void dma16(const void* src, unsigned lds_byte_offset) {   // offset: wave-uniform, in an SGPR
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
-                 :: "v"(src), "s"(lds_byte_offset) : "memory", "m0");
-}
-#define PECLR_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
+// (LDS-DMA through mfma.hpp lds_dma16: every wait on the vm counter is written by hand below, and no other VMEM instruction is
+// in flight while DMAs are)
 
 // WM: 32-row MFMA tiles per wave (2 -> 256 x 128 workgroup tile, 1 -> 128 x 128 for problems with few row blocks)
 // AREG: the fp32 rows travel global -> registers (inline-asm loads, hand-counted) instead of global -> LDS (DMA) -> registers
@@ -176,8 +161,10 @@ __global__ __launch_bounds__(256, 2) void gemm_x6p_kernel(X6PArgs g) {
     const unsigned b_a = __builtin_amdgcn_readfirstlane(lds0);
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);             // wave-uniform copy in an SGPR (LDS-DMA targets)
 
+    // XCD-aware tile order, as mfma.hpp xcd_tile -- written out: this kernel has always divided the SIGNED index, and the unsigned
+    // division of the shared helper is other instructions
     const int j = vb / 8;
-    const int row_block = 8 * (j / nct) + vb % 8;         // all column tiles of a row block on one XCD
+    const int row_block = 8 * (j / nct) + vb % 8;
     if (row_block * TM >= g.M) return;
     const int m0 = row_block * TM + wave * RM, ct = j % nct, n0 = ct * PNL;
     // s2d: parity class of this workgroup (the four-tap class first: longest workgroups first)
@@ -269,10 +256,10 @@ __global__ __launch_bounds__(256, 2) void gemm_x6p_kernel(X6PArgs g) {
         const unsigned d = b_a + (t % NB) * CHL;
         if constexpr (NTL == 4) {
 #pragma unroll
-            for (int q = 0; q < NP; ++q) dma16(s + (NP * wave_s + q) * 1024, d + (NP * wave_s + q) * 1024);
+            for (int q = 0; q < NP; ++q) lds_dma16(s + (NP * wave_s + q) * 1024, d + (NP * wave_s + q) * 1024);
         } else {                                          // 2 NP pieces: (six: waves 0, 1 two each, waves 2, 3 one; four: one each)
-            dma16(s + wave_s * 1024, d + wave_s * 1024);
-            if (NP == 3 && wave_s < 2) dma16(s + (4 + wave_s) * 1024, d + (4 + wave_s) * 1024);
+            lds_dma16(s + wave_s * 1024, d + wave_s * 1024);
+            if (NP == 3 && wave_s < 2) lds_dma16(s + (4 + wave_s) * 1024, d + (4 + wave_s) * 1024);
         }
     };
     auto issue_a = [&](int t) {
@@ -302,7 +289,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x6p_kernel(X6PArgs g) {
 #endif
                 ar[c] = *reinterpret_cast<const f32x4*>(src);
             }
-            else dma16(src, raw_a + c * 1024);
+            else lds_dma16(src, raw_a + c * 1024);
         }
     };
     // rows of the k-step just landed -> three planes [k-half][row][8 k] (this lane: row 16 c + (lane >> 2),
@@ -339,9 +326,9 @@ __global__ __launch_bounds__(256, 2) void gemm_x6p_kernel(X6PArgs g) {
     // publishes them.  Three B buffers: t being read, t + 1 landed, t + 2 landing.
     issue_b(0);
     issue_a(0);
-    if constexpr (!AREG) PECLR_VMCNT(0);
+    if constexpr (!AREG) wait_vmcnt<0>();
     split_store();
-    if constexpr (!AREG) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if constexpr (!AREG) wait_lgkmcnt0();
     if (nk > 1) { issue_b(1); issue_a(1); }
 
     const int foff = kh * HALF + i * 16;                  // this lane's fragment inside a plane (+ 512 per 32-row tile)
@@ -371,7 +358,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x6p_kernel(X6PArgs g) {
             PECLR_X6(1, 0) PECLR_X6(0, 1) PECLR_X6(0, 0)                  // (NP = 2: lo.hi, hi.lo, hi.hi -- smallest first)
 #undef PECLR_X6
             if (half == 0 && SPLIT) {
-                if constexpr (!AREG) PECLR_VMCNT(0);
+                if constexpr (!AREG) wait_vmcnt<0>();
                 if constexpr (!(ABL & 1)) split_store();       // after this step's fragment reads in program (= LDS) order
                 else if constexpr (AREG) { asm volatile("" :: "v"(ar[0]), "v"(ar[NRAW - 1])); }
                 if constexpr (AREG && !(ABL & 9) && ILV) {   // (ABL 64: the interleave pattern below still assumes 24 WM products: harmless)
@@ -383,7 +370,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x6p_kernel(X6PArgs g) {
                         if (q % 4 == 3 || NP == 2) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
                     }
                 }
-                if constexpr (!AREG) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                if constexpr (!AREG) wait_lgkmcnt0();
                 if (t + 2 < nk) {
                     if constexpr (!(ABL & 4)) issue_b(t + 2);
                     if constexpr (!(ABL & 2)) issue_a(t + 2);
@@ -391,7 +378,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x6p_kernel(X6PArgs g) {
             }
         }
     };
-    PECLR_VMCNT(0);                                       // (B chunk 0; for nk > 1 also what was just issued)
+    wait_vmcnt<0>();                                       // (B chunk 0; for nk > 1 also what was just issued)
     for (int t = 0; t + 1 < nk; ++t) kstep(t, std::true_type{});
     kstep(nk - 1, std::false_type{});
     } else {
@@ -460,10 +447,10 @@ __global__ __launch_bounds__(256, 2) void gemm_x6p_kernel(X6PArgs g) {
             const unsigned d = b_a + (s % NB) * CHL;
             if constexpr (NTL == 4) {
 #pragma unroll
-                for (int q = 0; q < NP; ++q) dma16(src + (NP * wave_s + q) * 1024, d + (NP * wave_s + q) * 1024);
+                for (int q = 0; q < NP; ++q) lds_dma16(src + (NP * wave_s + q) * 1024, d + (NP * wave_s + q) * 1024);
             } else {
-                dma16(src + wave_s * 1024, d + wave_s * 1024);
-                if (NP == 3 && wave_s < 2) dma16(src + (4 + wave_s) * 1024, d + (4 + wave_s) * 1024);
+                lds_dma16(src + wave_s * 1024, d + wave_s * 1024);
+                if (NP == 3 && wave_s < 2) lds_dma16(src + (4 + wave_s) * 1024, d + (4 + wave_s) * 1024);
             }
         };
         const int nsteps = 9 * nkc;
@@ -472,15 +459,15 @@ __global__ __launch_bounds__(256, 2) void gemm_x6p_kernel(X6PArgs g) {
         issue_bh(0);
         issue_bh(1);
         store_patch();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // the plane stores are in the LDS before the (raw) barrier lets other waves read
-        PECLR_VMCNT(0);
+        wait_lgkmcnt0();    // the plane stores are in the LDS before the (raw) barrier lets other waves read
+        wait_vmcnt<0>();
         for (int kc = 0; kc < nkc; ++kc) {
             for (int j = 0; j < 9; ++j) {
                 const int s = kc * 9 + j;
                 // B chunk s has landed: issued after it are chunk s + 1 (and, at j == 1, the next patch's rows)
-                if (j == 1 && kc + 1 < nkc) asm volatile("s_waitcnt vmcnt(%0)" :: "n"((ABL & 2) ? NDMA : NDMA + NLD) : "memory");
-                else if (s + 1 == nsteps) PECLR_VMCNT(0);        // (nothing was issued after the last chunk)
-                else if (s > 0) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NDMA) : "memory");
+                if (j == 1 && kc + 1 < nkc) wait_vmcnt<(ABL & 2) ? NDMA : NDMA + NLD>();
+                else if (s + 1 == nsteps) wait_vmcnt<0>();        // (nothing was issued after the last chunk)
+                else if (s > 0) wait_vmcnt<NDMA>();
                 if constexpr (!(ABL & 16)) __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
                 const int ja = j / 3, jb = j - 3 * ja;
@@ -524,7 +511,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x6p_kernel(X6PArgs g) {
                 if constexpr (!(ABL & 16)) __builtin_amdgcn_s_barrier();             // every wave has read this chunk's patch
                 asm volatile("" ::: "memory");
                 store_patch();
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // (published by the barrier at the top of the next step)
+                wait_lgkmcnt0();    // (published by the barrier at the top of the next step)
             }
         }
     }

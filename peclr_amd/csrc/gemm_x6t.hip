@@ -18,14 +18,12 @@
 // K is split over gridDim.y workgroup rows writing fp32 slabs [split][M][ldc] that peclr_slab_reduce_f32 adds in a fixed
 // order (deterministic).  taps = 9: gridDim.z = 9, B rows shifted by the tap's pixel offset (zeros outside the image),
 // output columns tap * N + n (the [Cout][3][3][Cin] layout of a channels_last weight).
-#include "common.hpp"
+#include "mfma.hpp"
 
 #include <type_traits>
 
 namespace peclr {
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int TK = 16;
 
@@ -40,9 +38,6 @@ struct X6TArgs {
     const float* zeros;
 };
 
-__device__ __forceinline__ f32x16 mma(const uint4& a, const uint4& b, f32x16 acc) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-}
 __device__ __forceinline__ int slot_of(int i) { return (i & 3) * 8 + ((i >> 2) ^ (((i >> 1) & 1) << 2)); }
 
 // MT x NT: 32 x 32 MFMA tiles per wave; waves WGM (M) x 8 / WGM (N): workgroup tile 32 WGM MT x 256 / WGM NT (4 x 2 waves:
@@ -181,7 +176,7 @@ __global__ __launch_bounds__(512, 2) void gemm_x6t_kernel(X6TArgs g) {
                 for (int p = 0; p < 3; ++p) bf[y][p] = *reinterpret_cast<const uint4*>(bufp + fb + (half * YH + y) * 512 + p * PL_B);
 #define PECLR_X6(P, Q)                                                                        \
     _Pragma("unroll") for (int y = 0; y < YH; ++y) _Pragma("unroll") for (int a = 0; a < MT; ++a) \
-        acc[a][half * YH + y] = mma(af[a][P], bf[y][Q], acc[a][half * YH + y]);
+        acc[a][half * YH + y] = mma_bf16(af[a][P], bf[y][Q], acc[a][half * YH + y]);
             PECLR_X6(2, 0) PECLR_X6(0, 2) PECLR_X6(1, 1) PECLR_X6(1, 0) PECLR_X6(0, 1) PECLR_X6(0, 0)
 #undef PECLR_X6
             if (half == 0 && t + 1 < nk) {
@@ -339,12 +334,12 @@ __global__ __launch_bounds__(512, 2) void gemm_x6w_kernel(X6TArgs g) {
                 uint4 bf[3];
 #pragma unroll
                 for (int p = 0; p < 3; ++p) bf[p] = *reinterpret_cast<const uint4*>(bufp + fb + tp * GRP + p * 2048);
-                acc[tp] = mma(af[2], bf[0], acc[tp]);
-                acc[tp] = mma(af[0], bf[2], acc[tp]);
-                acc[tp] = mma(af[1], bf[1], acc[tp]);
-                acc[tp] = mma(af[1], bf[0], acc[tp]);
-                acc[tp] = mma(af[0], bf[1], acc[tp]);
-                acc[tp] = mma(af[0], bf[0], acc[tp]);
+                acc[tp] = mma_bf16(af[2], bf[0], acc[tp]);
+                acc[tp] = mma_bf16(af[0], bf[2], acc[tp]);
+                acc[tp] = mma_bf16(af[1], bf[1], acc[tp]);
+                acc[tp] = mma_bf16(af[1], bf[0], acc[tp]);
+                acc[tp] = mma_bf16(af[0], bf[1], acc[tp]);
+                acc[tp] = mma_bf16(af[0], bf[0], acc[tp]);
             }
             if (tp == (WGM == 4 ? 2 : 1) && t + 1 < nk) {
                 if constexpr (!(ABL & 4)) split_store((t + 1) & 1);
@@ -386,7 +381,6 @@ __global__ __launch_bounds__(512, 2) void gemm_x6w_kernel(X6TArgs g) {
 //     rows of one 64-column group: 4 splits, 12 4-byte plane stores, 2 loads) placed between the MFMAs of taps 0 - 7
 //     (sched_barrier fences keep hipcc from clustering them again); fragments of tap t + 1 are read under the MFMAs of tap t.
 // Waves 0 .. NG - 9 own two column groups, the others one: the loop is instantiated for both (TWO) and chosen per wave.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int X6W2_MAX_HW = 3136;                             // table bytes per tap (an image of up to 56 x 56 output pixels)
 constexpr int X6W2_TAB = 9 * X6W2_MAX_HW + 192;               // bytes of the table area
 constexpr int X6W2_S2_MAX_HW = X6W2_TAB / 36 - 3;             // stride 2: four bytes per tap and pixel (+ 3 wrap entries per tap): 28 x 28
@@ -634,20 +628,20 @@ __global__ __launch_bounds__(512, 2) void gemm_x6w2_kernel(X6TArgs g) {
                     else { piece(2 * si); piece(2 * si + 1); }
                 };
 #define PECLR_FENCE __builtin_amdgcn_sched_barrier(0)
-                acc[tp] = mma(af[2], b0[cb], acc[tp]);       PECLR_FENCE;
+                acc[tp] = mma_bf16(af[2], b0[cb], acc[tp]);       PECLR_FENCE;
                 if (more) b0[cb ^ 1] = *reinterpret_cast<const uint4*>(nx);
                 slot(0);                                      PECLR_FENCE;
-                acc[tp] = mma(af[0], b2, acc[tp]);           PECLR_FENCE;
+                acc[tp] = mma_bf16(af[0], b2, acc[tp]);           PECLR_FENCE;
                 if (more) b2 = *reinterpret_cast<const uint4*>(nx + 4096);
                 slot(1);                                      PECLR_FENCE;
-                acc[tp] = mma(af[1], b1, acc[tp]);           PECLR_FENCE;
+                acc[tp] = mma_bf16(af[1], b1, acc[tp]);           PECLR_FENCE;
                 slot(2);                                      PECLR_FENCE;
-                acc[tp] = mma(af[1], b0[cb], acc[tp]);       PECLR_FENCE;
+                acc[tp] = mma_bf16(af[1], b0[cb], acc[tp]);       PECLR_FENCE;
                 slot(3);                                      PECLR_FENCE;
-                acc[tp] = mma(af[0], b1, acc[tp]);           PECLR_FENCE;
+                acc[tp] = mma_bf16(af[0], b1, acc[tp]);           PECLR_FENCE;
                 if (more) b1 = *reinterpret_cast<const uint4*>(nx + 2048);
                 slot(4);                                      PECLR_FENCE;
-                acc[tp] = mma(af[0], b0[cb], acc[tp]);       PECLR_FENCE;
+                acc[tp] = mma_bf16(af[0], b0[cb], acc[tp]);       PECLR_FENCE;
                 slot(5);                                      PECLR_FENCE;
 #undef PECLR_FENCE
             }
@@ -838,7 +832,7 @@ __global__ __launch_bounds__(512, 2) void gemm_x6t2_kernel(X6TArgs g) {
 #pragma unroll
                         for (int a = 0; a < MT; ++a) {
                             const uint4& bb = QB[pr] == 0 ? b0[half & 1][y] : (QB[pr] == 1 ? b1[y] : b2[y]);
-                            acc[a][half * YH + y] = mma(af[a][PA[pr]], bb, acc[a][half * YH + y]);
+                            acc[a][half * YH + y] = mma_bf16(af[a][PA[pr]], bb, acc[a][half * YH + y]);
                             PECLR_FENCE;
                             const int n = (half * 6 + pr) * YH * MT + y * MT + a;
                             // fragments of the second half: plane 0 into its second register set at once, planes 2 / 1 into the

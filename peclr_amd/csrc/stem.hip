@@ -22,14 +22,10 @@
 
 #include <type_traits>
 
-#include "common.hpp"
+#include "mfma.hpp"
 
 namespace peclr {
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
 
 constexpr int SK = 14;                   // k-steps of 16 (28 slices of 8: kh = slice >> 2, pixel pair = slice & 3)
 constexpr int TPX = 128;                 // output pixels of a row per workgroup
@@ -51,36 +47,16 @@ struct StemArgs {
 struct X6 {                              // fp32: three bf16 planes, six products
     static constexpr int NP = 3;
     typedef float Out;
-    static __device__ __forceinline__ f32x16 mma(const uint4& a, const uint4& b, f32x16 acc) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-    }
+    static __device__ __forceinline__ f32x16 mma(const uint4& a, const uint4& b, f32x16 acc) { return mma_bf16(a, b, acc); }
 };
-struct HB {                              // bf16 autocast
+struct HB : BF16 {                       // bf16 autocast
     static constexpr int NP = 1;
-    typedef uint16_t Out;
-    static __device__ __forceinline__ f32x16 mma(const uint4& a, const uint4& b, f32x16 acc) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-    }
-    static __device__ __forceinline__ unsigned pack2(float a, float b) { return pk_bf16(a, b); }
-    static __device__ __forceinline__ float up(unsigned lo16) { return __uint_as_float(lo16 << 16); }
+    typedef h16_t Out;
 };
-struct HF {                              // fp16 autocast (the reference's precision: 16)
+struct HF : F16 {                        // fp16 autocast (the reference's precision: 16)
     static constexpr int NP = 1;
-    typedef uint16_t Out;
-    static __device__ __forceinline__ f32x16 mma(const uint4& a, const uint4& b, f32x16 acc) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
-    }
-    static __device__ __forceinline__ unsigned pack2(float a, float b) {
-        const f32x2_t v = {a, b};
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2v));
-    }
-    static __device__ __forceinline__ float up(unsigned lo16) { return (float)__builtin_bit_cast(_Float16, (unsigned short)lo16); }
+    typedef h16_t Out;
 };
-
-__device__ __forceinline__ void sdma16(const void* src, unsigned lds_byte_offset) {     // see gemm_x6p.hip `dma16`
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
-                 :: "v"(src), "s"(lds_byte_offset) : "memory", "m0");
-}
 
 template <typename F>
 __global__ __launch_bounds__(256, 2) void stem_fwd_kernel(StemArgs g) {
@@ -111,10 +87,10 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_kernel(StemArgs g) {
         const unsigned char* s = bsrc + (size_t)t * CH;
         const unsigned d = lds0 + B0 + (t % NB) * CH;
         if constexpr (NP == 3) {                          // six pieces: waves 0, 1 two each, waves 2, 3 one
-            sdma16(s + wave_s * 1024, d + wave_s * 1024);
-            if (wave_s < 2) sdma16(s + (4 + wave_s) * 1024, d + (4 + wave_s) * 1024);
+            lds_dma16(s + wave_s * 1024, d + wave_s * 1024);
+            if (wave_s < 2) lds_dma16(s + (4 + wave_s) * 1024, d + (4 + wave_s) * 1024);
         } else if (wave_s < 2) {
-            sdma16(s + wave_s * 1024, d + wave_s * 1024);
+            lds_dma16(s + wave_s * 1024, d + wave_s * 1024);
         }
     };
 
@@ -171,12 +147,12 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_kernel(StemArgs g) {
         // filter chunk t has landed: younger than it are at most chunks t + 1 and t + 2 (this wave's pieces: 2 / 1 / 0 requests
         // per chunk; the last two steps simply wait for everything)
         if (t + 2 < SK) {
-            if (NP == 3 && wave_s < 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            else if (NP == 3 || wave_s < 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            if (NP == 3 && wave_s < 2) wait_vmcnt<4>();
+            else if (NP == 3 || wave_s < 2) wait_vmcnt<2>();
         } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vmcnt<0>();
         }
-        if (t == 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the patch stores are in the LDS before the barrier publishes them
+        if (t == 0) wait_lgkmcnt0();      // the patch stores are in the LDS before the barrier publishes them
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (t + 3 < SK) issue_b(t + 3);                   // into the stage step t - 1 read
@@ -453,10 +429,9 @@ __global__ __launch_bounds__(256, F::NP == 3 ? 2 : 3) void stem_wgrad_kernel(Ste
             const size_t row = row0 + (live ? ow0 + p : 0);
             const uint4* src = NP == 3 ? reinterpret_cast<const uint4*>(static_cast<const float*>(g.dy) + row * 64 + 4 * grp)
                                        : reinterpret_cast<const uint4*>(static_cast<const uint16_t*>(g.dy) + row * 64 + 8 * grp);
-            typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
             if (live && !(g.abl & 1)) {
                 if (g.abl & 32) {                         // (A/B: every dY row is read exactly once -- with the non-temporal hint)
-                    const u32x4_t t = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(src));
+                    const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src));
                     dyr[u] = make_uint4(t[0], t[1], t[2], t[3]);
                 } else dyr[u] = *src;
             } else dyr[u] = make_uint4(0u, 0u, 0u, 0u);

@@ -2,7 +2,7 @@
 // dY[r][co] * X[r][ci]  -- the contraction runs over the ROWS of two NHWC activations (channels contiguous), so both MFMA
 // operands have to be transposed on their way into the matrix cores.  gfx950 does that in the LDS read:
 //   * both operands stream global -> LDS by LDS-DMA exactly as they lie in memory (16 pixels x 64 bytes per
-//     `global_load_lds_dwordx4`, four lanes per pixel), into the image [32-channel block][pixel][64 B];
+//     `lds_dma16`, four lanes per pixel), into the image [32-channel block][pixel][64 B];
 //   * `ds_read_b64_tr_b16` hands lane l of a 16-lane group the elements src[(l >> 2) + 4 j][l & 3], j = 0..3, of the 8-byte
 //     words its sixteen lanes address: with source lane r pointing at pixel k0 + (r >> 2), channels 4 (r & 3) .. + 3, lane
 //     l receives channel l of pixels k0 .. k0 + 3 -- two such reads are the 8-k fragment of v_mfma_f32_32x32x16 (4 consecutive
@@ -15,15 +15,12 @@
 // workgroups per CU measured the same or slower: tools/exp/wgrad_h_probe.py).
 #include <stdlib.h>
 
-#include "common.hpp"
+#include "mfma.hpp"
 
 namespace peclr {
 namespace {
 
-typedef uint16_t h16_t;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int WK = 32;                   // pixels per k-step
 
@@ -38,15 +35,10 @@ struct WArgs {
     const h16_t* zeros;                  // >= 64 bytes of zeros (rows past K)
 };
 
-__device__ __forceinline__ void wdma16(const void* src, unsigned lds_byte_offset) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
-                 :: "v"(src), "s"(lds_byte_offset) : "memory", "m0");
-}
-
 template <bool F16>
 __device__ __forceinline__ f32x16 wmma(const uint4& a, const uint4& b, f32x16 acc) {
-    if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
+    if constexpr (F16) return mma_f16(a, b, acc);
+    else return mma_bf16(a, b, acc);
 }
 
 // 8 consecutive k (pixels) of one channel per lane out of the pixel-major image: two transposing reads
@@ -123,7 +115,7 @@ __global__ __launch_bounds__(256, NS == 2 ? 4 : 2) void wgrad_h_kernel(WArgs g) 
                 src = g.B + row * g.ldb + ch + lch;
             }
             if (k >= k_end) src = g.zeros + lch;
-            wdma16(src, st + (isb ? ASZ : 0) + blk * 2048 + half * 1024);
+            lds_dma16(src, st + (isb ? ASZ : 0) + blk * 2048 + half * 1024);
         }
     };
 
@@ -134,8 +126,8 @@ __global__ __launch_bounds__(256, NS == 2 ? 4 : 2) void wgrad_h_kernel(WArgs g) 
     const int foff = (8 * (gq >> 1) + (ll >> 2)) * 64 + (16 * (gq & 1) + 4 * (ll & 3)) * 2;
     for (int t = 0; t < nk; ++t) {
         // stage t has landed: younger than it are the stages t + 1 .. t + NS - 2 (those that exist)
-        if (NS > 2 && t + NS - 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" :: "n"((NS - 2) * ND) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (NS > 2 && t + NS - 2 < nk) wait_vmcnt<(NS - 2) * ND>();
+        else wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (t + NS - 1 < nk) issue(t + NS - 1);
@@ -349,12 +341,12 @@ __global__ __launch_bounds__(256, 2) void wgrad3_h_kernel(W3Args g) {
     };
     auto issue_a = [&](int t) {                           // dY slots [p_begin + 32 t, + 32) -> stage t % NSA
         const int p = p_begin + 32 * t + 16 * dhalf + (lane >> 2);
-        wdma16(src_of(g.A, g.lda, m0 + 32 * dblk, p, p < p_end), lds0 + A0 + (t % NSA) * ASZ + dblk * 2048 + dhalf * 1024);
+        lds_dma16(src_of(g.A, g.lda, m0 + 32 * dblk, p, p < p_end), lds0 + A0 + (t % NSA) * ASZ + dblk * 2048 + dhalf * 1024);
     };
     auto issue_x = [&](int u) {                           // ring group u: X slots [p_begin - L + 32 u, + 32)
         const int p = p_begin - L + 32 * u + 16 * dhalf + (lane >> 2);
         const unsigned slot0 = (unsigned)(32 * u + 16 * dhalf) & (RINGP - 1);
-        wdma16(src_of(g.B, g.ldb, n0 + 32 * dblk, p, true, S2), lds0 + R0 + dblk * RB + slot0 * 64);
+        lds_dma16(src_of(g.B, g.ldb, n0 + 32 * dblk, p, true, S2), lds0 + R0 + dblk * RB + slot0 * 64);
     };
     // k-step t reads ring groups t .. t + 2 L / 32 (slots [32 t, 32 t + 32 + 2 L) relative to p_begin - L); groups are issued two
     // steps ahead of their first use
@@ -368,8 +360,8 @@ __global__ __launch_bounds__(256, 2) void wgrad3_h_kernel(W3Args g) {
     const int fch = (16 * (gq & 1) + 4 * (ll & 3)) * 2;
     for (int t = 0; t < nk; ++t) {
         // landed: dY(t) and ring groups <= t + G0 - 1; younger than those: dY(t + 1) [1 DMA] and ring group t + G0 [1 DMA]
-        if (t + 1 < nk) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (t + 1 < nk) wait_vmcnt<2>();
+        else wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (t + 1 < nk) issue_x(t + G0 + 1);              // (the ring slot group it overwrites was last read in step t - 1 at the latest)
