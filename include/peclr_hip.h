@@ -569,6 +569,55 @@ int peclr_augment_resize_color_norm_ext(const uint8_t* crops, int B, int H, int 
                                         const float* stdv, int channels_last, float* out,
                                         peclr_stream_t stream);
 
+/* The same four stages for a batch whose images DIFFER IN SIZE (the reference's YouTube-3D-Hands frames next to
+ * FreiHAND's 224 x 224; TwoViewAugmenter with a RaggedImages or a list).  Per sample and per view the results are
+ * bit-identical to what the entry points above give for that sample alone.  The kernels are the same code over
+ * another geometry source; the launch count is the same (no launch per sample or per size).
+ *
+ * images : ONE packed uint8 buffer, the B images back to back, each [H_i][W_i][3]; image starts need no alignment.
+ * geom   : device [B][PECLR_AUG_GEOM_INT64S] int64 per sample, computed by the HOST (peclr_amd/augment.py):
+ *            [0] byte offset of the image in `images` (64-bit: a batch may exceed 2^31 bytes)
+ *            [1] H_i   [2] W_i
+ *            [3] kx_i  [4] ky_i  the image's own odd blur lengths (horizontal from H_i, vertical from W_i: the
+ *                                reference's swap), at most PECLR_AUG_MAX_BLUR_KSIZE; read by stage 0 only.
+ *                                A record's `coefs` offset points at kx_i horizontal taps, then ky_i vertical ones.
+ * srcs / blur_tmp (stage 0): [n_views] copies of the packed layout, total_bytes uint8 / uint16 ELEMENTS per view;
+ *   sample i of view v starts at element v * total_bytes + geom[i][0].
+ * wins   : device [n_views][B][PECLR_AUG_WIN_INT64S] int64 per (view, sample), computed by the HOST, which knows every
+ *          crop window before the launch:
+ *            [0] byte offset of the window's first pixel in `crops`
+ *            [1] row stride of the window in PIXELS (>= its width)
+ *            [2] width, [3] height of the window -- the values of params[7..10]'s cw, ch; for the host (grid size,
+ *                slicing a window out of the scratch), not read by the kernels
+ * crops  : uint8 scratch addressed only through `wins`.  peclr_amd packs it: window after window, row stride = the
+ *          window's width, sum of cw * ch * 3 bytes (the uniform scratch is n_views * B * H * W * 3).
+ * Grids take their x, y extent from the batch maximum, passed from the host: max_h x max_w (images, stage 0),
+ * max_ch x max_cw (windows, stage 1), out_h x out_w (stage 2).  max_kx, max_ky: the maxima of geom's [3], [4]
+ * (checked odd and <= PECLR_AUG_MAX_BLUR_KSIZE, as kx, ky above).  With n_views = 1 and the per-view pointers
+ * srcs + v * total_bytes, params + v * B * 16, wins + v * B * 4 (crops unchanged: wins' offsets are absolute) the warp
+ * runs once per view after stage 0.  The noise counter stays (out pixel index, sample, view, call): a sample gets the
+ * same noise at the same batch position whatever its source size. */
+#define PECLR_AUG_GEOM_INT64S 5
+#define PECLR_AUG_WIN_INT64S 4
+int peclr_augment_pre_ragged_u8(const uint8_t* images, int B, int n_views, const int64_t* geom,
+                                int64_t total_bytes, int max_h, int max_w, const int* ext,
+                                const int* coefs, int max_kx, int max_ky, uint8_t* srcs,
+                                uint16_t* blur_tmp, peclr_stream_t stream);
+int peclr_augment_warp_crop_ragged_u8(const uint8_t* images, int B, int n_views, const int64_t* geom,
+                                      const double* params, const int64_t* wins, int max_cw,
+                                      int max_ch, uint8_t* crops, peclr_stream_t stream);
+int peclr_augment_resize_color_norm_ragged(const uint8_t* crops, int B, int n_views,
+                                           const int64_t* wins, const double* params, int out_h,
+                                           int out_w, const float* mean, const float* stdv,
+                                           int channels_last, float* out, peclr_stream_t stream);
+int peclr_augment_resize_color_norm_ragged_ext(const uint8_t* crops, int B, int n_views,
+                                               const int64_t* wins, const double* params,
+                                               const int* ext, const uint32_t* noise_table,
+                                               int n_table, uint64_t noise_seed, uint32_t call,
+                                               int out_h, int out_w, const float* mean,
+                                               const float* stdv, int channels_last, float* out,
+                                               peclr_stream_t stream);
+
 /* ---- 16-bit convolutions of the residual blocks (bf16 / fp16 autocast: BASELINE configs C3 / C5 and the reference's own
  * `precision: 16`, training_config.json:9, peclr_training.py:78-79), csrc/conv_h.hip.  They replace MIOpen's 16-bit
  * convolution kernels behind torchvision's Bottleneck / BasicBlock (resnet_model.py:15) -- forward and input gradient of the

@@ -4,7 +4,7 @@ Host side of libpeclr_hip.so behind the reference's own module surface:
 
     from peclr_amd import Hybrid2Model, SimCLR, peclr_to_torchvision, hybrid2_config
 """
-from .augment import TwoViewAugmenter
+from .augment import RaggedImages, TwoViewAugmenter
 from .config import Config, hybrid2_config
 from .module import BaseModel, Hybrid2Model, SimCLR, get_model
 from .pose_eval import PoseEvaluator, auc_joints, epe_statistics, pck_curves, procrustes_transform
@@ -14,5 +14,5 @@ from .trainer import Trainer
 
 __all__ = ["Config", "hybrid2_config", "BaseModel", "SimCLR", "Hybrid2Model", "get_model",
            "peclr_to_torchvision", "get_encoder_state_dict", "get_latest_checkpoint", "save_checkpoint", "restore_model",
-           "Trainer", "TwoViewAugmenter", "epe_statistics", "procrustes_transform", "pck_curves", "auc_joints",
+           "Trainer", "TwoViewAugmenter", "RaggedImages", "epe_statistics", "procrustes_transform", "pck_curves", "auc_joints",
            "PoseEvaluator"]

@@ -77,6 +77,11 @@ SIGNATURES = {
     "peclr_augment_pre_u8": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P]),
     "peclr_augment_resize_color_norm_ext": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, c_uint64,
                                                     c_uint32, c_int, c_int, _P, _P, c_int, _P, _P]),
+    "peclr_augment_pre_ragged_u8": (c_int, [_P, c_int, c_int, _P, c_int64, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P]),
+    "peclr_augment_warp_crop_ragged_u8": (c_int, [_P, c_int, c_int, _P, _P, _P, c_int, c_int, _P, _P]),
+    "peclr_augment_resize_color_norm_ragged": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, _P, _P, c_int, _P, _P]),
+    "peclr_augment_resize_color_norm_ragged_ext": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, c_int, c_uint64, c_uint32,
+                                                           c_int, c_int, _P, _P, c_int, _P, _P]),
     "peclr_gemm_x6_f32": (c_int, [c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P]),
     "peclr_gemm_x6_tn_slabs": (c_int, [c_int, c_int, c_int]),
     "peclr_gemm_x6_tn_f32": (c_int, [c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, _P]),
@@ -1450,6 +1455,135 @@ def augment_views_ext(images: torch.Tensor, params: torch.Tensor, ext: torch.Ten
                                                        int(channels_last), out.data_ptr(), stream)
         _check(rc, "peclr_augment_resize_color_norm")
     return out, srcs, crops
+
+
+# ---- the same for a batch whose images differ in size (include/peclr_hip.h: the geometry tables)
+AUG_GEOM_INT64S, AUG_WIN_INT64S = 5, 4
+
+
+def ragged_image(buf: torch.Tensor, geom: torch.Tensor, i: int) -> torch.Tensor:
+    """Sample i's [H,W,3] image in one view of a packed buffer (the source, or srcs[v] of augment_views_ragged_ext)."""
+    off, h, w = (int(t) for t in geom[i, :3])
+    return buf[off:off + h * w * 3].view(h, w, 3)
+
+
+def ragged_window(crops: torch.Tensor, wins: torch.Tensor, v: int, i: int) -> torch.Tensor:
+    """The [ch,cw,3] crop window of (view v, sample i) in the scratch the ragged calls return."""
+    off, stride, cw, ch = (int(t) for t in wins[v, i])
+    return crops[off:off + ch * stride * 3].view(ch, stride, 3)[:, :cw]
+
+
+def _ragged_args(packed, geom, wins, params):
+    if not packed.is_cuda or packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+        raise PeclrHipError(f"augment: the packed images must be a contiguous 1-D uint8 HIP tensor, got {packed.dtype} "
+                            f"{tuple(packed.shape)} on {packed.device} (peclr_amd has no CPU path)")
+    if geom.is_cuda or geom.dtype != torch.int64 or geom.dim() != 2 or geom.shape[1] != AUG_GEOM_INT64S or geom.shape[0] < 1:
+        raise PeclrHipError(f"augment: geom must be a host [B,{AUG_GEOM_INT64S}] int64 tensor")
+    b = geom.shape[0]
+    if (params.dtype != torch.float64 or params.dim() != 3 or params.shape[1] != b
+            or params.shape[2] != AUG_PARAM_DOUBLES or not params.is_cuda or not params.is_contiguous()):
+        raise PeclrHipError(f"augment: params must be a contiguous [V,{b},{AUG_PARAM_DOUBLES}] float64 HIP tensor")
+    v = params.shape[0]
+    if wins.is_cuda or wins.dtype != torch.int64 or tuple(wins.shape) != (v, b, AUG_WIN_INT64S):
+        raise PeclrHipError(f"augment: wins must be a host [{v},{b},{AUG_WIN_INT64S}] int64 tensor")
+    ends = geom[:, 0] + geom[:, 1] * geom[:, 2] * 3
+    if int(geom[:, :3].min()) < 0 or int(geom[:, 1:3].min()) < 1 or int(ends.max()) > packed.numel():
+        raise PeclrHipError(f"augment: geom names bytes outside the packed buffer of {packed.numel()}")
+    if int(wins.min()) < 0 or int(wins[..., 2:].min()) < 1 or bool((wins[..., 1] < wins[..., 2]).any()):
+        raise PeclrHipError("augment: wins needs offsets >= 0, windows of at least one pixel and row strides >= their width")
+    # the scratch ends where the last window row does
+    scratch = int((wins[..., 0] + ((wins[..., 3] - 1) * wins[..., 1] + wins[..., 2]) * 3).max())
+    return b, v, scratch
+
+
+def augment_views_ragged(packed: torch.Tensor, geom: torch.Tensor, wins: torch.Tensor, params: torch.Tensor, out_hw, mean,
+                         std, channels_last: bool = True):
+    """augment_views for images of different sizes: `packed` the 1-D uint8 HIP buffer of the images back to back,
+    geom [B,5] / wins [V,B,4] the HOST int64 tables of include/peclr_hip.h (peclr_amd/augment.py builds them; they are
+    uploaded here), params [V,B,16] float64 (HIP).  The same two launches.
+    Returns (out, crops, wins): crops the packed scratch, `ragged_window(crops, wins, v, i)` a window of it."""
+    b, v, scratch = _ragged_args(packed, geom, wins, params)
+    oh, ow = out_hw
+    dev, stream = packed.device, _stream()
+    geom_d, wins_d = geom.contiguous().to(dev, non_blocking=True), wins.contiguous().to(dev, non_blocking=True)
+    crops = torch.empty(scratch, device=dev, dtype=torch.uint8)
+    out = torch.empty((v * b, 3, oh, ow), device=dev, dtype=torch.float32,
+                      memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    mean_arr, std_arr = (c_float * 3)(*mean), (c_float * 3)(*std)
+    win_bytes = int((wins[..., 2] * wins[..., 3]).sum()) * 3
+    with _timed("augment_warp_crop", 2 * win_bytes):
+        rc = lib().peclr_augment_warp_crop_ragged_u8(packed.data_ptr(), b, v, geom_d.data_ptr(), params.data_ptr(),
+                                                     wins_d.data_ptr(), int(wins[..., 2].max()), int(wins[..., 3].max()),
+                                                     crops.data_ptr(), stream)
+    _check(rc, "peclr_augment_warp_crop_ragged_u8")
+    with _timed("augment_resize_color_norm", win_bytes + v * b * oh * ow * 12):
+        rc = lib().peclr_augment_resize_color_norm_ragged(crops.data_ptr(), b, v, wins_d.data_ptr(), params.data_ptr(), oh, ow,
+                                                          ctypes.cast(mean_arr, c_void_p), ctypes.cast(std_arr, c_void_p),
+                                                          int(channels_last), out.data_ptr(), stream)
+    _check(rc, "peclr_augment_resize_color_norm_ragged")
+    return out, crops, wins
+
+
+def augment_views_ragged_ext(packed: torch.Tensor, geom: torch.Tensor, wins: torch.Tensor, params: torch.Tensor,
+                             ext: torch.Tensor, coefs: torch.Tensor, noise_table: torch.Tensor, n_table: int, noise_seed: int,
+                             call: int, ops: int, out_hw, mean, std, channels_last: bool = True):
+    """augment_views_ext for images of different sizes (arguments as augment_views_ragged and augment_views_ext; the
+    blur lengths are geom's, per sample).  Stage 0's per-view sources come back as srcs [V, total bytes] in the packed
+    layout (`ragged_image(srcs[v], geom, i)`).  Returns (out, srcs or None, crops, wins)."""
+    b, v, scratch = _ragged_args(packed, geom, wins, params)
+    if ext.dtype != torch.int32 or tuple(ext.shape) != (v, b, AUG_EXT_INTS) or not ext.is_cuda or not ext.is_contiguous():
+        raise PeclrHipError(f"augment: ext must be a contiguous [{v},{b},{AUG_EXT_INTS}] int32 HIP tensor")
+    for name, t in (("coefs", coefs), ("noise_table", noise_table)):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_cuda or not t.is_contiguous():
+            raise PeclrHipError(f"augment: {name} must be a contiguous 1-D int32 HIP tensor")
+    if not 0 <= n_table <= noise_table.numel():
+        raise PeclrHipError(f"augment: n_table {n_table} exceeds the table's {noise_table.numel()} entries")
+    oh, ow = out_hw
+    dev, stream = packed.device, _stream()
+    total = packed.numel()
+    geom_d, wins_d = geom.contiguous().to(dev, non_blocking=True), wins.contiguous().to(dev, non_blocking=True)
+    crops = torch.empty(scratch, device=dev, dtype=torch.uint8)
+    out = torch.empty((v * b, 3, oh, ow), device=dev, dtype=torch.float32,
+                      memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    mean_arr, std_arr = (c_float * 3)(*mean), (c_float * 3)(*std)
+    win_bytes = int((wins[..., 2] * wins[..., 3]).sum()) * 3
+    max_cw, max_ch = int(wins[..., 2].max()), int(wins[..., 3].max())
+    srcs = None
+    if ops & AUG_EXT_PRE:
+        srcs = torch.empty((v, total), device=dev, dtype=torch.uint8)
+        tmp = torch.empty((v, total), device=dev, dtype=torch.int16) if ops & AUG_EXT_BLUR else None
+        # (without the blur stage the lengths are not read: nothing to check)
+        kx, ky = (int(geom[:, 3].max()), int(geom[:, 4].max())) if tmp is not None else (1, 1)
+        blur_work = int(((geom[:, 3] + geom[:, 4]) * geom[:, 1] * geom[:, 2]).sum()) * 3 if tmp is not None else 0
+        with _timed("augment_pre", v * total * (1 + 1 + (4 if tmp is not None else 0)), v * blur_work):
+            rc = lib().peclr_augment_pre_ragged_u8(packed.data_ptr(), b, v, geom_d.data_ptr(), total, int(geom[:, 1].max()),
+                                                   int(geom[:, 2].max()), ext.data_ptr(), coefs.data_ptr(), kx, ky,
+                                                   srcs.data_ptr(), None if tmp is None else tmp.data_ptr(), stream)
+        _check(rc, "peclr_augment_pre_ragged_u8")
+        for i in range(v):
+            with _timed("augment_warp_crop", 2 * int((wins[i, :, 2] * wins[i, :, 3]).sum()) * 3):
+                rc = lib().peclr_augment_warp_crop_ragged_u8(srcs[i].data_ptr(), b, 1, geom_d.data_ptr(), params[i].data_ptr(),
+                                                             wins_d[i].data_ptr(), max_cw, max_ch, crops.data_ptr(), stream)
+            _check(rc, "peclr_augment_warp_crop_ragged_u8")
+    else:
+        with _timed("augment_warp_crop", 2 * win_bytes):
+            rc = lib().peclr_augment_warp_crop_ragged_u8(packed.data_ptr(), b, v, geom_d.data_ptr(), params.data_ptr(),
+                                                         wins_d.data_ptr(), max_cw, max_ch, crops.data_ptr(), stream)
+        _check(rc, "peclr_augment_warp_crop_ragged_u8")
+    mp, sp = ctypes.cast(mean_arr, c_void_p), ctypes.cast(std_arr, c_void_p)
+    if ops & AUG_EXT_POST:
+        with _timed("augment_resize_color_norm_ext", win_bytes + v * b * oh * ow * 12):
+            rc = lib().peclr_augment_resize_color_norm_ragged_ext(crops.data_ptr(), b, v, wins_d.data_ptr(), params.data_ptr(),
+                                                                  ext.data_ptr(), noise_table.data_ptr(), n_table,
+                                                                  noise_seed & (2 ** 64 - 1), call & 0xFFFFFFFF, oh, ow, mp, sp,
+                                                                  int(channels_last), out.data_ptr(), stream)
+        _check(rc, "peclr_augment_resize_color_norm_ragged_ext")
+    else:
+        with _timed("augment_resize_color_norm", win_bytes + v * b * oh * ow * 12):
+            rc = lib().peclr_augment_resize_color_norm_ragged(crops.data_ptr(), b, v, wins_d.data_ptr(), params.data_ptr(), oh, ow,
+                                                              mp, sp, int(channels_last), out.data_ptr(), stream)
+        _check(rc, "peclr_augment_resize_color_norm_ragged")
+    return out, srcs, crops, wins
 
 
 # ------------------------------------------------------------------ 2.5D hand-pose model at evaluation time (peclr_amd/pose.py)

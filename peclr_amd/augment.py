@@ -22,12 +22,17 @@ color_drop) are opt-in: `TwoViewAugmenter(..., extended=True)`.  Without it they
 NotImplementedError.  With it their draws join the reference's order and their pixels run in two
 more device stages (see `TwoViewAugmenter.__init__`).  `resize` is required either way (without it
 the reference's crops have per-sample sizes and cannot be collated either).
+
+The images of one batch may differ in size (the reference concatenates YouTube-3D-Hands frames, of whatever size
+the video had, with FreiHAND's 224 x 224, and augments each sample on its own): pass `RaggedImages`, or a list of
+HWC arrays, instead of one [B,H,W,3] tensor.  The draws, the launches and the emitted dict are the same; every
+sample comes out as it would alone.
 """
 from __future__ import annotations
 
 import math
 import random as _random
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -135,6 +140,75 @@ def noise_cdf_table(std: float) -> List[int]:
             break
         table.append(t)
     return table
+
+
+def _image_hw(image, i: int) -> Tuple[int, int]:
+    """(H, W) of one HWC uint8 image (NumPy array or tensor), or the reason it is not one."""
+    if not isinstance(image, (np.ndarray, Tensor)):
+        raise TypeError(f"image {i}: expected a NumPy array or a tensor, got {type(image).__name__}")
+    if image.dtype not in (np.uint8, torch.uint8):
+        raise TypeError(f"image {i}: expected uint8 pixels, got {image.dtype}")
+    if len(image.shape) != 3 or image.shape[2] != 3:
+        raise ValueError(f"image {i}: expected [H,W,3], got {tuple(image.shape)}")
+    h, w = int(image.shape[0]), int(image.shape[1])
+    if h < 1 or w < 1:
+        raise ValueError(f"image {i}: empty ({h}x{w})")
+    return h, w
+
+
+class RaggedImages:
+    """A batch of HWC uint8 images of different sizes as ONE packed device buffer, back to back and unpadded (image
+    starts need no alignment).  data: 1-D uint8 HIP tensor; sizes: the B (H, W) pairs; offsets: int64 [B] byte offset
+    of each image in `data` (host tensor)."""
+
+    def __init__(self, data: Tensor, sizes: Sequence[Tuple[int, int]]):
+        self.sizes = [(int(h), int(w)) for h, w in sizes]
+        self.offsets, total = self.layout(self.sizes)
+        if data.dtype != torch.uint8 or data.dim() != 1 or data.numel() != total:
+            raise ValueError(f"RaggedImages: {len(self.sizes)} images of these sizes are {total} bytes, got "
+                             f"{data.dtype} {tuple(data.shape)}")
+        self.data = data
+
+    def __len__(self) -> int:
+        return len(self.sizes)
+
+    @property
+    def device(self):
+        return self.data.device
+
+    @staticmethod
+    def layout(sizes: Sequence[Tuple[int, int]]) -> Tuple[Tensor, int]:
+        """[(H, W), ...] -> (int64 [B] byte offsets, total bytes): the running sums of H * W * 3 (Python integers,
+        so exact past 2^31 bytes)."""
+        offsets, total = [], 0
+        for h, w in sizes:
+            if h < 1 or w < 1:
+                raise ValueError(f"RaggedImages: empty image ({h}x{w})")
+            offsets.append(total)
+            total += int(h) * int(w) * 3
+        return torch.tensor(offsets, dtype=torch.int64), total
+
+    @staticmethod
+    def check(images) -> List[Tuple[int, int]]:
+        """The sizes of a list of HWC uint8 images; raises on anything else.  No device call."""
+        if len(images) == 0:
+            raise ValueError("RaggedImages: an empty list of images")
+        return [_image_hw(im, i) for i, im in enumerate(images)]
+
+    @classmethod
+    def from_list(cls, images, device) -> "RaggedImages":
+        """images: HWC uint8 NumPy arrays or host tensors.  Packed into one pinned host buffer, then ONE non-blocking
+        copy.  (Tensors already on `device` are concatenated there instead.)"""
+        sizes = cls.check(images)
+        if all(isinstance(im, Tensor) and im.is_cuda for im in images):
+            return cls(torch.cat([im.reshape(-1) for im in images]).to(device), sizes)
+        offsets, total = cls.layout(sizes)
+        host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        flat = host.numpy()
+        for im, off, (h, w) in zip(images, offsets.tolist(), sizes):
+            src = im.detach().cpu().numpy() if isinstance(im, Tensor) else im
+            flat[off:off + h * w * 3] = np.ascontiguousarray(src).reshape(-1)
+        return cls(host.to(device, non_blocking=True), sizes)
 
 
 class TwoViewAugmenter:
@@ -294,12 +368,17 @@ class TwoViewAugmenter:
         return ([*(view["minv"] if rot else [1.0, 0.0, 0.0, 0.0, 1.0, 0.0]), float(rot), *map(float, view["crop"]),
                  float(col), *((view["h"], view["s"], view["a"], view["b"]) if col else (1.0, 1.0, 1.0, 0.0))])
 
-    def sample_batch(self, joints25d: Tensor, image_hw: Tuple[int, int]):
-        """Draws view 1 then view 2 for each sample in turn (the order a dataset iterates)."""
+    def sample_batch(self, joints25d: Tensor, image_hw: Union[Tuple[int, int], Sequence[Tuple[int, int]]]):
+        """Draws view 1 then view 2 for each sample in turn (the order a dataset iterates).  image_hw: one (H, W)
+        for the whole batch, or one per sample."""
         views: List[List[Dict]] = [[], []]
-        for j in joints25d:
+        if isinstance(image_hw[0], (int, np.integer)):
+            image_hw = [tuple(image_hw)] * len(joints25d)
+        elif len(image_hw) != len(joints25d):
+            raise ValueError(f"{len(image_hw)} image sizes for {len(joints25d)} samples")
+        for j, hw in zip(joints25d, image_hw):
             for v in (0, 1):
-                views[v].append(self.sample_view(j, image_hw))
+                views[v].append(self.sample_view(j, (int(hw[0]), int(hw[1]))))
         params = torch.tensor([[self.pack(w) for w in views[v]] for v in (0, 1)], dtype=torch.float64)
         return params, views
 
@@ -320,10 +399,74 @@ class TwoViewAugmenter:
                 out[f"{key}_{v + 1}"] = t
         return out
 
+    @staticmethod
+    def ragged_tables(sizes: Sequence[Tuple[int, int]], offsets: Tensor, views: List[List[Dict]]) -> Tuple[Tensor, Tensor]:
+        """include/peclr_hip.h's host tables of a mixed-size batch: geom [B,5] int64 (byte offset, H, W and the
+        image's own blur lengths) and wins [V,B,4] int64 (byte offset, row stride, width, height of each crop window
+        in the PACKED scratch: window after window, row stride = width)."""
+        geom = torch.tensor([[off, h, w, *blur_ksize((h, w))] for off, (h, w) in zip(offsets.tolist(), sizes)],
+                            dtype=torch.int64)
+        wins, at = [], 0
+        for vs in views:
+            rows = []
+            for w in vs:
+                _, _, cw, ch = w["crop"]
+                rows.append([at, cw, cw, ch])
+                at += cw * ch * 3
+            wins.append(rows)
+        return geom, torch.tensor(wins, dtype=torch.int64)
+
+    def _check_blur_sizes(self, sizes: Sequence[Tuple[int, int]]):
+        if self.extended and self.flags.get("gaussian_blur"):
+            for h, w in sizes:
+                if max(blur_ksize((h, w))) > MAX_BLUR_KSIZE:
+                    raise ValueError(f"gaussian_blur: a {h}x{w} image needs kernels {blur_ksize((h, w))}, "
+                                     f"longer than the device's {MAX_BLUR_KSIZE}")
+
+    def _call_ragged(self, images, joints25d: Tensor) -> Dict[str, Tensor]:
+        """Everything that can be refused is refused before the first device call."""
+        if isinstance(images, RaggedImages):
+            sizes = images.sizes
+        else:
+            sizes = RaggedImages.check(images)
+        b = len(sizes)
+        if len(joints25d) != b:
+            raise ValueError(f"{b} images for {len(joints25d)} samples of joints")
+        self._check_blur_sizes(sizes)
+        params, views = self.sample_batch(joints25d, sizes)
+        if not isinstance(images, RaggedImages):
+            dev = next((im.device for im in images if isinstance(im, Tensor) and im.is_cuda), torch.device("cuda"))
+            images = RaggedImages.from_list(images, dev)
+        dev = images.device
+        geom, wins = self.ragged_tables(sizes, images.offsets, views)
+        rw, rh = self.params["resize_shape"]
+        call = self.noise_call
+        self.noise_call += 1
+        ops = 0
+        for vs in views:
+            for view in vs:
+                ops |= self.ext_flags(view)
+        if not ops:  # as in __call__: the recipe's two launches
+            out = _capi.augment_views_ragged(images.data, geom, wins, params.to(dev, non_blocking=True), (rh, rw),
+                                             IMAGENET_MEAN, IMAGENET_STD, self.channels_last)[0]
+        else:
+            ext, coefs = self.pack_ext(views)
+            table, n_table = self.noise_table()
+            out = _capi.augment_views_ragged_ext(images.data, geom, wins, params.to(dev, non_blocking=True),
+                                                 ext.to(dev, non_blocking=True), coefs.to(dev, non_blocking=True),
+                                                 table.to(dev, non_blocking=True), n_table, self.noise_seed, call, ops,
+                                                 (rh, rw), IMAGENET_MEAN, IMAGENET_STD, self.channels_last)[0]
+        batch = {"transformed_images": out, "transformed_image1": out[:b], "transformed_image2": out[b:]}
+        batch.update({k: t.to(dev, non_blocking=True) for k, t in self.collate(views).items()})
+        return batch
+
     # ---- device: the batch
-    def __call__(self, images: Tensor, joints25d: Tensor) -> Dict[str, Tensor]:
+    def __call__(self, images: Union[Tensor, RaggedImages, Sequence], joints25d: Tensor) -> Dict[str, Tensor]:
         """images: [B,H,W,3] uint8 on the HIP device (the reference's RGB HWC arrays, one size per
-        batch); joints25d: [B,21,3] (any device; the parameter logic runs on the host)."""
+        batch), or -- for a batch whose images differ in size -- a `RaggedImages`, or a list / tuple of HWC uint8
+        arrays (packed and copied here); joints25d: [B,21,3] (any device; the parameter logic runs on the host)."""
+        if not isinstance(images, Tensor):
+            return self._call_ragged(images, joints25d)
         b, h, w, _ = images.shape
         params, views = self.sample_batch(joints25d, (h, w))
         rw, rh = self.params["resize_shape"]

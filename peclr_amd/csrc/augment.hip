@@ -24,6 +24,13 @@
 //                      uint8 wrap-around add) and colour drop (BGR2GRAY to all three channels)
 // warp_crop_kernel then reads the per-view sources, one launch per view.
 //
+// Every kernel is written once over a GEOMETRY SOURCE (template parameters SRC / WIN below): the uniform one restates
+// the [B][H][W][3] batch of the first four entry points, the ragged one reads per-sample offsets and sizes from device
+// tables, so that one batch may mix image sizes (the *_ragged entry points; include/peclr_hip.h has the tables).  Ragged
+// grids are sized by the batch maximum; a block outside its own sample's extent leaves before any barrier.  The ragged
+// crop scratch is PACKED: the host knows every window before the launch, so window (view, sample) sits at its own byte
+// offset with its own width as row stride, and the scratch is the sum of the windows instead of V*B*H*W*3.
+//
 // Work per batch is tiny (B=128: ~40 MB read, ~50 MB written): these kernels exist to take the
 // cv2-on-CPU producer off the critical path, not to approach a roofline.  One thread per pixel,
 // consecutive lanes = consecutive x, so the float32 NHWC / NCHW stores coalesce.
@@ -92,6 +99,50 @@ __device__ __forceinline__ int gray_at(const uint8_t* __restrict__ src, int W, i
     return gray_u8(s[0], s[1], s[2]);
 }
 
+// ---- geometry sources
+struct SrcGeom {
+    size_t off;  // byte offset of the sample's image in `images`
+    int H, W, kx, ky;
+};
+struct WinGeom {
+    size_t off, stride;  // crop window in the scratch: byte offset of its first pixel, bytes per row
+};
+
+// image(n): the source image of (view, sample) n = view * B + sample; view_off(n, g): the element offset of n's copy in
+// the per-view buffers `srcs` / `blur_tmp`; kRagged: grids are the batch maximum's, so blocks test their own extent.
+struct UniformSrc {
+    static constexpr bool kRagged = false;
+    int B, H, W, kx, ky;
+    __device__ __forceinline__ SrcGeom image(int n) const { return SrcGeom{(size_t)(n % B) * H * W * 3, H, W, kx, ky}; }
+    __device__ __forceinline__ size_t view_off(int n, const SrcGeom&) const { return (size_t)n * H * W * 3; }
+};
+struct UniformWin {  // the window of (view, sample) n at the origin of its own H x W image, rows at the source stride
+    int H, W;
+    __device__ __forceinline__ WinGeom window(int n) const { return WinGeom{(size_t)n * H * W * 3, (size_t)W * 3}; }
+};
+
+constexpr int NG = PECLR_AUG_GEOM_INT64S, NW = PECLR_AUG_WIN_INT64S;
+struct RaggedSrc {
+    int B;
+    const long long* __restrict__ geom;  // [B][NG]
+    size_t total;                        // bytes of the packed source = elements of one view of srcs / blur_tmp
+    static constexpr bool kRagged = true;
+    __device__ __forceinline__ SrcGeom image(int n) const {
+        const long long* g = geom + (size_t)(n % B) * NG;
+        // (the lengths are bounded on the host; the clamp only keeps a bad table inside the LDS arrays)
+        return SrcGeom{(size_t)g[0], (int)g[1], (int)g[2], min((int)g[3], PECLR_AUG_MAX_BLUR_KSIZE),
+                       min((int)g[4], PECLR_AUG_MAX_BLUR_KSIZE)};
+    }
+    __device__ __forceinline__ size_t view_off(int n, const SrcGeom& g) const { return (size_t)(n / B) * total + g.off; }
+};
+struct RaggedWin {
+    const long long* __restrict__ wins;  // [V][B][NW]
+    __device__ __forceinline__ WinGeom window(int n) const {
+        const long long* w = wins + (size_t)n * NW;
+        return WinGeom{(size_t)w[0], (size_t)w[1] * 3};
+    }
+};
+
 constexpr int SEG = BX + 2 * PRE_RMAX;  // row positions a block of pre_rows_kernel covers, halo included
 constexpr int COL_ROWS = 8;               // output rows per thread of pre_cols_kernel (sliding window)
 
@@ -119,18 +170,23 @@ __device__ __forceinline__ uint32_t pre_packed(const uint8_t* __restrict__ src, 
 // ---- stage 0, rows: Sobel -> cut-out -> [horizontal blur pass (u8 x Q8, exact in 16 bits)]
 // A block covers BX columns x BY rows.  Row positions x in [x0 - rx, min(x0 + BX, W) + rx) are evaluated at
 // their reflect-101 image column, which always lies in [lo, hi); the gray tile covers [lo - 1, hi + 1).
-__global__ __launch_bounds__(BX* BY) void pre_rows_kernel(const uint8_t* __restrict__ images, int B, int H, int W,
+template <class SRC>
+__global__ __launch_bounds__(BX* BY) void pre_rows_kernel(const uint8_t* __restrict__ images, SRC geo,
                                                            const int* __restrict__ ext, const int* __restrict__ coefs,
-                                                           int kx, uint8_t* __restrict__ srcs, uint16_t* __restrict__ tmp) {
+                                                           uint8_t* __restrict__ srcs, uint16_t* __restrict__ tmp) {
     __shared__ uint8_t gray[BY + 2][SEG + 2];
     __shared__ uint32_t seg[BY][SEG];
     __shared__ int taps[2 * PRE_RMAX + 1];
     const int n = blockIdx.z;  // view * B + sample
     const ExtParam e = load_ext(ext, n);
-    const uint8_t* src = images + (size_t)(n % B) * H * W * 3;
+    const SrcGeom g = geo.image(n);
+    const int H = g.H, W = g.W, kx = g.kx;
+    const int x0 = blockIdx.x * BX, y0 = blockIdx.y * BY, tid = threadIdx.y * BX + threadIdx.x;
+    if (SRC::kRagged && (x0 >= W || y0 >= H)) return;  // block-uniform, before any barrier
+    const uint8_t* src = images + g.off;
+    const size_t view = geo.view_off(n, g);  // this (view, sample) in srcs / tmp
     const bool blur = (e.flags & PECLR_AUG_EXT_BLUR) && tmp;  // block-uniform
     const int rx = blur ? kx >> 1 : 0;
-    const int x0 = blockIdx.x * BX, y0 = blockIdx.y * BY, tid = threadIdx.y * BX + threadIdx.x;
     const int lo = max(x0 - rx, 0), hi = min(x0 + BX + rx, W);
     if (blur)
         for (int i = tid; i < kx; i += BX * BY) taps[i] = coefs[e.coef + i];
@@ -156,7 +212,7 @@ __global__ __launch_bounds__(BX* BY) void pre_rows_kernel(const uint8_t* __restr
     if (x >= W || y >= H) return;
     if (!blur) {
         const uint32_t p = seg[threadIdx.y][threadIdx.x];
-        uint8_t* d = srcs + ((size_t)n * H * W + (size_t)y * W + x) * 3;
+        uint8_t* d = srcs + view + ((size_t)y * W + x) * 3;
         d[0] = (uint8_t)p, d[1] = (uint8_t)(p >> 8), d[2] = (uint8_t)(p >> 16);
         return;
     }
@@ -167,25 +223,30 @@ __global__ __launch_bounds__(BX* BY) void pre_rows_kernel(const uint8_t* __restr
         a02 += t * (p & 0x00FF00FFu);
         a1 += t * ((p >> 8) & 0xFFu);
     }
-    uint16_t* d = tmp + ((size_t)n * H * W + (size_t)y * W + x) * 3;
+    uint16_t* d = tmp + view + ((size_t)y * W + x) * 3;
     d[0] = (uint16_t)a02, d[1] = (uint16_t)a1, d[2] = (uint16_t)(a02 >> 16);
 }
 
 // ---- stage 0, columns: vertical blur pass (16-bit x Q8, (acc + 2^15) >> 16) of the blurred samples.
 // Each thread produces COL_ROWS consecutive rows from one pass over the COL_ROWS + ky - 1 input rows.
-__global__ __launch_bounds__(BX* BY) void pre_cols_kernel(int H, int W, const int* __restrict__ ext,
-                                                           const int* __restrict__ coefs, int kx, int ky,
+template <class SRC>
+__global__ __launch_bounds__(BX* BY) void pre_cols_kernel(SRC geo, const int* __restrict__ ext,
+                                                           const int* __restrict__ coefs,
                                                            const uint16_t* __restrict__ tmp, uint8_t* __restrict__ srcs) {
     __shared__ int taps[2 * PRE_RMAX + 1];
     const int n = blockIdx.z;
     const ExtParam e = load_ext(ext, n);
     if (!(e.flags & PECLR_AUG_EXT_BLUR)) return;  // block-uniform; pre_rows_kernel wrote this sample already
+    const SrcGeom g = geo.image(n);
+    const int H = g.H, W = g.W, kx = g.kx, ky = g.ky;
+    if (SRC::kRagged && (blockIdx.x * BX >= W || blockIdx.y * (BY * COL_ROWS) >= H)) return;  // as in pre_rows_kernel
+    const size_t view = geo.view_off(n, g);
     for (int i = threadIdx.y * BX + threadIdx.x; i < ky; i += BX * BY) taps[i] = coefs[e.coef + kx + i];
     __syncthreads();
     const int x = blockIdx.x * BX + threadIdx.x, y0 = (blockIdx.y * BY + threadIdx.y) * COL_ROWS;
     if (x >= W || y0 >= H) return;
     const int ry = ky >> 1;
-    const uint16_t* t = tmp + (size_t)n * H * W * 3 + (size_t)x * 3;
+    const uint16_t* t = tmp + view + (size_t)x * 3;
     uint32_t acc[COL_ROWS][3] = {};
     for (int r = 0; r < COL_ROWS + ky - 1; ++r) {
         const uint16_t* s = t + (size_t)reflect101(y0 - ry + r, H) * W * 3;
@@ -202,22 +263,26 @@ __global__ __launch_bounds__(BX* BY) void pre_cols_kernel(int H, int W, const in
 #pragma unroll
     for (int j = 0; j < COL_ROWS; ++j) {
         if (y0 + j >= H) break;
-        uint8_t* d = srcs + ((size_t)n * H * W + (size_t)(y0 + j) * W + x) * 3;
+        uint8_t* d = srcs + view + ((size_t)(y0 + j) * W + x) * 3;
 #pragma unroll
         for (int c = 0; c < 3; ++c) d[c] = (uint8_t)((acc[j][c] + (1u << 15)) >> 16);
     }
 }
 
 // ---- stage 1: rotation (8-bit warpAffine, bilinear, zero border), evaluated on the crop window only
-__global__ __launch_bounds__(BX* BY) void warp_crop_kernel(const uint8_t* __restrict__ images, int B, int H, int W,
+template <class SRC, class WIN>
+__global__ __launch_bounds__(BX* BY) void warp_crop_kernel(const uint8_t* __restrict__ images, SRC geo, WIN win,
                                                             const double* __restrict__ params,
                                                             uint8_t* __restrict__ crops) {
     const int n = blockIdx.z;  // view * B + sample
     const ViewParam v = load_param(params, n);
     const int cx = blockIdx.x * BX + threadIdx.x, cy = blockIdx.y * BY + threadIdx.y;
     if (cx >= v.cw || cy >= v.ch) return;
-    const uint8_t* src = images + (size_t)(n % B) * H * W * 3;
-    uint8_t* dst = crops + ((size_t)n * H * W + (size_t)cy * W + cx) * 3;
+    const SrcGeom g = geo.image(n);
+    const WinGeom wg = win.window(n);
+    const int H = g.H, W = g.W;
+    const uint8_t* src = images + g.off;
+    uint8_t* dst = crops + wg.off + (size_t)cy * wg.stride + (size_t)cx * 3;
     const int x = v.x0 + cx, y = v.y0 + cy;
     if (!v.rotate) {
         const uint8_t* s = src + ((size_t)y * W + x) * 3;
@@ -396,16 +461,17 @@ __device__ __forceinline__ void post_ops(int px[3], const PostExt& pe, int n, in
 }
 
 // ---- stage 2: resize -> colour jitter -> ToTensor/Normalize
-template <bool NHWC, bool EXT>
-__global__ __launch_bounds__(BX* BY) void resize_color_norm_kernel(const uint8_t* __restrict__ crops, int B, int H, int W,
+template <bool NHWC, bool EXT, class WIN>
+__global__ __launch_bounds__(BX* BY) void resize_color_norm_kernel(const uint8_t* __restrict__ crops, int B, WIN win,
                                                                     const double* __restrict__ params, int out_h, int out_w,
                                                                     Norm norm, float* __restrict__ out, PostExt pe) {
     const int n = blockIdx.z;
     const int dx = blockIdx.x * BX + threadIdx.x, dy = blockIdx.y * BY + threadIdx.y;
     if (dx >= out_w || dy >= out_h) return;
     const ViewParam v = load_param(params, n);
-    const uint8_t* img = crops + (size_t)n * H * W * 3;  // window rows have the source stride W
-    const size_t stride = (size_t)W * 3;
+    const WinGeom wg = win.window(n);
+    const uint8_t* img = crops + wg.off;
+    const size_t stride = wg.stride;
     const int sw = v.cw, sh = v.ch;
     int px[3];
     const Axis ax = make_axis(sw, out_w), ay = make_axis(sh, out_h);
@@ -485,21 +551,39 @@ __global__ __launch_bounds__(BX* BY) void resize_color_norm_kernel(const uint8_t
 
 using namespace peclr;
 
-extern "C" int peclr_augment_warp_crop_u8(const uint8_t* images, int B, int H, int W, int n_views, const double* params,
-                                          uint8_t* crops, peclr_stream_t stream) {
-    if (!images || !params || !crops) return PECLR_ERR_NULL;
-    if (B <= 0 || H <= 0 || W <= 0 || n_views <= 0 || (long long)B * n_views > 65535) return PECLR_ERR_SHAPE;
-    dim3 grid((W + BX - 1) / BX, (H + BY - 1) / BY, B * n_views);
-    hipLaunchKernelGGL(warp_crop_kernel, grid, dim3(BX, BY), 0, static_cast<hipStream_t>(stream), images, B, H, W, params, crops);
+namespace {
+
+inline bool bad_batch(int B, int n_views) { return B <= 0 || n_views <= 0 || (long long)B * n_views > 65535; }
+
+inline bool bad_ksize(int kx, int ky) {
+    return kx < 1 || ky < 1 || !(kx & 1) || !(ky & 1) || kx > PECLR_AUG_MAX_BLUR_KSIZE || ky > PECLR_AUG_MAX_BLUR_KSIZE;
+}
+
+// stage 0 over the grid of an ext_h x ext_w image (the batch maximum for a ragged batch)
+template <class SRC>
+int launch_pre(const uint8_t* images, SRC geo, int n_views, int ext_h, int ext_w, const int* ext, const int* coefs,
+               uint8_t* srcs, uint16_t* blur_tmp, hipStream_t s) {
+    dim3 grid((ext_w + BX - 1) / BX, (ext_h + BY - 1) / BY, geo.B * n_views);
+    hipLaunchKernelGGL(pre_rows_kernel<SRC>, grid, dim3(BX, BY), 0, s, images, geo, ext, coefs, srcs, blur_tmp);
+    if (blur_tmp) {
+        dim3 gcol((ext_w + BX - 1) / BX, (ext_h + BY * COL_ROWS - 1) / (BY * COL_ROWS), geo.B * n_views);
+        hipLaunchKernelGGL(pre_cols_kernel<SRC>, gcol, dim3(BX, BY), 0, s, geo, ext, coefs, blur_tmp, srcs);
+    }
     return launch_status();
 }
 
-extern "C" int peclr_augment_resize_color_norm(const uint8_t* crops, int B, int H, int W, int n_views, const double* params,
-                                               int out_h, int out_w, const float* mean, const float* stdv,
-                                               int channels_last, float* out, peclr_stream_t stream) {
-    if (!crops || !params || !mean || !stdv || !out) return PECLR_ERR_NULL;
-    if (B <= 0 || H <= 0 || W <= 0 || n_views <= 0 || out_h <= 0 || out_w <= 0 || (long long)B * n_views > 65535)
-        return PECLR_ERR_SHAPE;
+template <class SRC, class WIN>
+int launch_warp(const uint8_t* images, SRC geo, WIN win, int n_views, int ext_h, int ext_w, const double* params,
+                uint8_t* crops, hipStream_t s) {
+    dim3 grid((ext_w + BX - 1) / BX, (ext_h + BY - 1) / BY, geo.B * n_views);
+    hipLaunchKernelGGL((warp_crop_kernel<SRC, WIN>), grid, dim3(BX, BY), 0, s, images, geo, win, params, crops);
+    return launch_status();
+}
+
+// stage 2; pe == nullptr: the recipe's form (no noise, no colour drop)
+template <class WIN>
+int launch_resize(const uint8_t* crops, int B, int n_views, WIN win, const double* params, int out_h, int out_w,
+                  const float* mean, const float* stdv, int channels_last, float* out, const PostExt* pe, hipStream_t s) {
     Norm norm;
     for (int c = 0; c < 3; ++c) {
         norm.mean[c] = mean[c];  // host pointers: three floats each, passed by value to the kernel
@@ -507,30 +591,45 @@ extern "C" int peclr_augment_resize_color_norm(const uint8_t* crops, int B, int 
         if (!(norm.stdv[c] > 0.f)) return PECLR_ERR_SHAPE;
     }
     dim3 grid((out_w + BX - 1) / BX, (out_h + BY - 1) / BY, B * n_views);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const PostExt none{};
-    if (channels_last)
-        hipLaunchKernelGGL((resize_color_norm_kernel<true, false>), grid, dim3(BX, BY), 0, s, crops, B, H, W, params, out_h, out_w, norm, out, none);
+    const PostExt post = pe ? *pe : PostExt{};
+    if (pe && channels_last)
+        hipLaunchKernelGGL((resize_color_norm_kernel<true, true, WIN>), grid, dim3(BX, BY), 0, s, crops, B, win, params, out_h, out_w, norm, out, post);
+    else if (pe)
+        hipLaunchKernelGGL((resize_color_norm_kernel<false, true, WIN>), grid, dim3(BX, BY), 0, s, crops, B, win, params, out_h, out_w, norm, out, post);
+    else if (channels_last)
+        hipLaunchKernelGGL((resize_color_norm_kernel<true, false, WIN>), grid, dim3(BX, BY), 0, s, crops, B, win, params, out_h, out_w, norm, out, post);
     else
-        hipLaunchKernelGGL((resize_color_norm_kernel<false, false>), grid, dim3(BX, BY), 0, s, crops, B, H, W, params, out_h, out_w, norm, out, none);
+        hipLaunchKernelGGL((resize_color_norm_kernel<false, false, WIN>), grid, dim3(BX, BY), 0, s, crops, B, win, params, out_h, out_w, norm, out, post);
     return launch_status();
+}
+
+}  // namespace
+
+extern "C" int peclr_augment_warp_crop_u8(const uint8_t* images, int B, int H, int W, int n_views, const double* params,
+                                          uint8_t* crops, peclr_stream_t stream) {
+    if (!images || !params || !crops) return PECLR_ERR_NULL;
+    if (H <= 0 || W <= 0 || bad_batch(B, n_views)) return PECLR_ERR_SHAPE;
+    return launch_warp(images, UniformSrc{B, H, W, 1, 1}, UniformWin{H, W}, n_views, H, W, params, crops,
+                       static_cast<hipStream_t>(stream));
+}
+
+extern "C" int peclr_augment_resize_color_norm(const uint8_t* crops, int B, int H, int W, int n_views, const double* params,
+                                               int out_h, int out_w, const float* mean, const float* stdv,
+                                               int channels_last, float* out, peclr_stream_t stream) {
+    if (!crops || !params || !mean || !stdv || !out) return PECLR_ERR_NULL;
+    if (H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0 || bad_batch(B, n_views)) return PECLR_ERR_SHAPE;
+    return launch_resize(crops, B, n_views, UniformWin{H, W}, params, out_h, out_w, mean, stdv, channels_last, out, nullptr,
+                         static_cast<hipStream_t>(stream));
 }
 
 extern "C" int peclr_augment_pre_u8(const uint8_t* images, int B, int H, int W, int n_views, const int* ext,
                                     const int* coefs, int kx, int ky, uint8_t* srcs, uint16_t* blur_tmp,
                                     peclr_stream_t stream) {
     if (!images || !ext || !coefs || !srcs) return PECLR_ERR_NULL;
-    if (B <= 0 || H <= 0 || W <= 0 || n_views <= 0 || (long long)B * n_views > 65535) return PECLR_ERR_SHAPE;
-    if (kx < 1 || ky < 1 || !(kx & 1) || !(ky & 1) || kx > PECLR_AUG_MAX_BLUR_KSIZE || ky > PECLR_AUG_MAX_BLUR_KSIZE)
-        return PECLR_ERR_SHAPE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    dim3 grid((W + BX - 1) / BX, (H + BY - 1) / BY, B * n_views);
-    hipLaunchKernelGGL(pre_rows_kernel, grid, dim3(BX, BY), 0, s, images, B, H, W, ext, coefs, kx, srcs, blur_tmp);
-    if (blur_tmp) {
-        dim3 gcol((W + BX - 1) / BX, (H + BY * COL_ROWS - 1) / (BY * COL_ROWS), B * n_views);
-        hipLaunchKernelGGL(pre_cols_kernel, gcol, dim3(BX, BY), 0, s, H, W, ext, coefs, kx, ky, blur_tmp, srcs);
-    }
-    return launch_status();
+    if (H <= 0 || W <= 0 || bad_batch(B, n_views)) return PECLR_ERR_SHAPE;
+    if (bad_ksize(kx, ky)) return PECLR_ERR_SHAPE;
+    return launch_pre(images, UniformSrc{B, H, W, kx, ky}, n_views, H, W, ext, coefs, srcs, blur_tmp,
+                      static_cast<hipStream_t>(stream));
 }
 
 extern "C" int peclr_augment_resize_color_norm_ext(const uint8_t* crops, int B, int H, int W, int n_views,
@@ -539,21 +638,54 @@ extern "C" int peclr_augment_resize_color_norm_ext(const uint8_t* crops, int B, 
                                                    const float* mean, const float* stdv, int channels_last, float* out,
                                                    peclr_stream_t stream) {
     if (!crops || !params || !ext || !noise_table || !mean || !stdv || !out) return PECLR_ERR_NULL;
-    if (B <= 0 || H <= 0 || W <= 0 || n_views <= 0 || out_h <= 0 || out_w <= 0 || (long long)B * n_views > 65535 ||
-        n_table < 0 || n_table > 255)
+    if (H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0 || bad_batch(B, n_views) || n_table < 0 || n_table > 255)
         return PECLR_ERR_SHAPE;
-    Norm norm;
-    for (int c = 0; c < 3; ++c) {
-        norm.mean[c] = mean[c];
-        norm.stdv[c] = stdv[c];
-        if (!(norm.stdv[c] > 0.f)) return PECLR_ERR_SHAPE;
-    }
     const PostExt pe{ext, noise_table, n_table, (uint32_t)noise_seed, (uint32_t)(noise_seed >> 32), call};
-    dim3 grid((out_w + BX - 1) / BX, (out_h + BY - 1) / BY, B * n_views);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (channels_last)
-        hipLaunchKernelGGL((resize_color_norm_kernel<true, true>), grid, dim3(BX, BY), 0, s, crops, B, H, W, params, out_h, out_w, norm, out, pe);
-    else
-        hipLaunchKernelGGL((resize_color_norm_kernel<false, true>), grid, dim3(BX, BY), 0, s, crops, B, H, W, params, out_h, out_w, norm, out, pe);
-    return launch_status();
+    return launch_resize(crops, B, n_views, UniformWin{H, W}, params, out_h, out_w, mean, stdv, channels_last, out, &pe,
+                         static_cast<hipStream_t>(stream));
+}
+
+// ---- the same four stages for a batch whose images differ in size (tables: include/peclr_hip.h)
+extern "C" int peclr_augment_pre_ragged_u8(const uint8_t* images, int B, int n_views, const int64_t* geom,
+                                           int64_t total_bytes, int max_h, int max_w, const int* ext, const int* coefs,
+                                           int max_kx, int max_ky, uint8_t* srcs, uint16_t* blur_tmp,
+                                           peclr_stream_t stream) {
+    if (!images || !geom || !ext || !coefs || !srcs) return PECLR_ERR_NULL;
+    if (max_h <= 0 || max_w <= 0 || total_bytes <= 0 || bad_batch(B, n_views)) return PECLR_ERR_SHAPE;
+    if (bad_ksize(max_kx, max_ky)) return PECLR_ERR_SHAPE;
+    const RaggedSrc geo{B, reinterpret_cast<const long long*>(geom), (size_t)total_bytes};
+    return launch_pre(images, geo, n_views, max_h, max_w, ext, coefs, srcs, blur_tmp, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int peclr_augment_warp_crop_ragged_u8(const uint8_t* images, int B, int n_views, const int64_t* geom,
+                                                 const double* params, const int64_t* wins, int max_cw, int max_ch,
+                                                 uint8_t* crops, peclr_stream_t stream) {
+    if (!images || !geom || !params || !wins || !crops) return PECLR_ERR_NULL;
+    if (max_cw <= 0 || max_ch <= 0 || bad_batch(B, n_views)) return PECLR_ERR_SHAPE;
+    const RaggedSrc geo{B, reinterpret_cast<const long long*>(geom), 0};
+    return launch_warp(images, geo, RaggedWin{reinterpret_cast<const long long*>(wins)}, n_views, max_ch, max_cw, params,
+                       crops, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int peclr_augment_resize_color_norm_ragged(const uint8_t* crops, int B, int n_views, const int64_t* wins,
+                                                      const double* params, int out_h, int out_w, const float* mean,
+                                                      const float* stdv, int channels_last, float* out,
+                                                      peclr_stream_t stream) {
+    if (!crops || !wins || !params || !mean || !stdv || !out) return PECLR_ERR_NULL;
+    if (out_h <= 0 || out_w <= 0 || bad_batch(B, n_views)) return PECLR_ERR_SHAPE;
+    return launch_resize(crops, B, n_views, RaggedWin{reinterpret_cast<const long long*>(wins)}, params, out_h, out_w, mean,
+                         stdv, channels_last, out, nullptr, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int peclr_augment_resize_color_norm_ragged_ext(const uint8_t* crops, int B, int n_views, const int64_t* wins,
+                                                          const double* params, const int* ext,
+                                                          const uint32_t* noise_table, int n_table, uint64_t noise_seed,
+                                                          uint32_t call, int out_h, int out_w, const float* mean,
+                                                          const float* stdv, int channels_last, float* out,
+                                                          peclr_stream_t stream) {
+    if (!crops || !wins || !params || !ext || !noise_table || !mean || !stdv || !out) return PECLR_ERR_NULL;
+    if (out_h <= 0 || out_w <= 0 || bad_batch(B, n_views) || n_table < 0 || n_table > 255) return PECLR_ERR_SHAPE;
+    const PostExt pe{ext, noise_table, n_table, (uint32_t)noise_seed, (uint32_t)(noise_seed >> 32), call};
+    return launch_resize(crops, B, n_views, RaggedWin{reinterpret_cast<const long long*>(wins)}, params, out_h, out_w, mean,
+                         stdv, channels_last, out, &pe, static_cast<hipStream_t>(stream));
 }

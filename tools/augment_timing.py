@@ -3,7 +3,11 @@
 compares with the CPU restatement of the reference's per-sample pipeline.  The last row turns on all ten of
 the reference's flags (TwoViewAugmenter(extended=True)): stage 0 ("augment_pre"), one warp per view, and the
 noise / colour-drop form of stage 2.  kernel_us: device-event time per call, summed over a name's launches.
-Usage: python tools/augment_timing.py [out.json]"""
+With a second file name it also times batches whose images differ in size (`RaggedImages`, recipe flags, B = 128,
+128 x 128 out): five repeats of the uniform 224 x 224 row (their spread is the yardstick), (a) the same images through
+the ragged path, (b) half 224 x 224 and half 480 x 640 through the ragged path, (c) the same mixed images as two
+uniform calls, one per size -- the only way to process them without the ragged path.
+Usage: python tools/augment_timing.py [out.json [ragged_out.json]]"""
 import json
 import os
 import random
@@ -15,12 +19,82 @@ import numpy as np
 import torch
 
 from oracle import augment_oracle as A
-from peclr_amd import TwoViewAugmenter, _capi
+from peclr_amd import RaggedImages, TwoViewAugmenter, _capi
 from peclr_amd.augment import RECIPE_FLAGS
 
 ALL_TEN = dict(RECIPE_FLAGS, sobel_filter=True, cut_out=True, gaussian_blur=True, gaussian_noise=True, color_drop=True)
 
 DEV = torch.device("cuda:0")
+
+
+def timed(calls, draw):
+    """calls: the augmenter calls of one batch; draw: its host parameter draws alone.  Three warm-up batches, then the
+    same measurement as main()'s rows."""
+    for _ in range(3):
+        calls()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(5):
+        draw()
+    host_ms = (time.perf_counter() - t0) / 5 * 1e3
+    _capi.EVENT_LOG = {}
+    t0 = time.perf_counter()
+    for _ in range(10):
+        calls()
+    torch.cuda.synchronize()
+    total_ms = (time.perf_counter() - t0) / 10 * 1e3
+    ev = {k: round(sum(s.elapsed_time(e) for s, e, *_ in v) / 10 * 1e3, 1) for k, v in _capi.EVENT_LOG.items()}
+    _capi.EVENT_LOG = None
+    return {"host_param_ms": round(host_ms, 2), "kernel_us": ev, "kernel_total_us": round(sum(ev.values()), 1),
+            "end_to_end_ms": round(total_ms, 2)}
+
+
+def ragged_rows():
+    b, size = 128, 128
+    g = np.random.default_rng(0)
+    small = [g.integers(0, 256, (224, 224, 3), dtype=np.uint8) for _ in range(b)]
+    big = [g.integers(0, 256, (480, 640, 3), dtype=np.uint8) for _ in range(b // 2)]
+
+    def joints(sizes):
+        return torch.from_numpy(np.stack([np.concatenate([g.normal((w / 2, h / 2 - 4), min(h, w) / 9, (21, 2)),
+                                                          g.normal(0, 1, (21, 1))], 1) for h, w in sizes])).float()
+
+    def aug():
+        return TwoViewAugmenter(params={"resize_shape": [size, size]}, rng=random.Random(1))
+
+    rows = []
+    j224 = joints([(224, 224)] * b)
+    uniform = torch.from_numpy(np.stack(small)).to(DEV)
+    for rep in range(5):
+        a = aug()
+        rows.append(dict(row=f"uniform 224 (repeat {rep})", batch=b, out=size,
+                         **timed(lambda: a(uniform, j224), lambda: a.sample_batch(j224, (224, 224)))))
+    tot = [r["kernel_total_us"] for r in rows]
+    e2e = [r["end_to_end_ms"] for r in rows]
+    spread = {"row": "spread of the five uniform repeats", "kernel_total_us": [min(tot), max(tot)],
+              "end_to_end_ms": [min(e2e), max(e2e)]}
+    # (a) the same images, ragged path (the device buffer is built once, like `uniform` above)
+    a, ragged = aug(), RaggedImages.from_list(small, DEV)
+    rows.append(dict(row="(a) ragged path, 128 x 224^2", batch=b, out=size,
+                     **timed(lambda: a(ragged, j224), lambda: a.sample_batch(j224, ragged.sizes))))
+    # (b) half 224^2, half 480 x 640, interleaved, ragged path
+    mixed = [im for pair in zip(small[:b // 2], big) for im in pair]
+    sizes = [im.shape[:2] for im in mixed]
+    jmix = joints(sizes)
+    a, ragged = aug(), RaggedImages.from_list(mixed, DEV)
+    rows.append(dict(row="(b) ragged path, 64 x 224^2 + 64 x 480x640", batch=b, out=size,
+                     **timed(lambda: a(ragged, jmix), lambda: a.sample_batch(jmix, sizes))))
+    # (c) the same images as two uniform calls, one per size
+    a = aug()
+    u_small, u_big = torch.from_numpy(np.stack(mixed[0::2])).to(DEV), torch.from_numpy(np.stack(mixed[1::2])).to(DEV)
+    j_small, j_big = jmix[0::2].contiguous(), jmix[1::2].contiguous()
+    rows.append(dict(row="(c) two uniform calls, 64 x 224^2 then 64 x 480x640", batch=b, out=size,
+                     **timed(lambda: (a(u_small, j_small), a(u_big, j_big)),
+                             lambda: (a.sample_batch(j_small, (224, 224)), a.sample_batch(j_big, (480, 640))))))
+    rows.append(spread)
+    for r in rows:
+        print(r, flush=True)
+    return rows
 
 
 def main():
@@ -64,6 +138,9 @@ def main():
     if len(sys.argv) > 1:
         with open(sys.argv[1], "w") as f:
             json.dump(rows, f, indent=1)
+    if len(sys.argv) > 2:
+        with open(sys.argv[2], "w") as f:
+            json.dump(ragged_rows(), f, indent=1)
 
 
 if __name__ == "__main__":

@@ -2,7 +2,8 @@
 """End-to-end functional run: uint8 source images + 2.5D joints -> GPU two-view augmentation -> Hybrid2Model
 (ResNet-18, crop+rotate alignment) -> NT-Xent -> LARS(Adam), through Trainer.fit with hipGraph replay.
 The "dataset" is a fixed set of structured synthetic images, so instance discrimination is learnable and
-the loss must fall.  Usage: python tools/train_synthetic.py [out.json]"""
+the loss must fall.  --mixed-sizes: every second image is a 240 x 320 one, so that each batch mixes sizes and fit() runs
+from the augmenter's ragged path (`RaggedImages`).  Usage: python tools/train_synthetic.py [--mixed-sizes] [out.json]"""
 import json
 import os
 import random
@@ -15,29 +16,35 @@ warnings.simplefilter("ignore")
 import numpy as np
 import torch
 
-from peclr_amd import Hybrid2Model, Trainer, TwoViewAugmenter, hybrid2_config
+from peclr_amd import Hybrid2Model, RaggedImages, Trainer, TwoViewAugmenter, hybrid2_config
 from peclr_amd.bn2d import enable_hip_batchnorm
 
 DEV = torch.device("cuda:0")
 N_IMAGES, PAIRS, EPOCHS, SIZE = 512, 64, 12, 128
 
 
-def make_dataset():
+def make_dataset(mixed=False):
     g = np.random.default_rng(0)
-    yy, xx = np.mgrid[0:224, 0:224]
-    imgs = []
+    imgs, centres = [], []
     for i in range(N_IMAGES):
+        h, w = (240, 320) if mixed and i % 2 else (224, 224)
+        yy, xx = np.mgrid[0:h, 0:w]
+        centres.append((w / 2, h / 2 - 4))
         f = g.uniform(5, 40, 3)
         ph = g.uniform(0, 6.28, 3)
         base = np.stack([127 + 100 * np.sin(xx / f[0] + ph[0]), 127 + 100 * np.cos(yy / f[1] + ph[1]),
                          127 + 100 * np.sin((xx + yy) / f[2] + ph[2])], axis=2)
         imgs.append(np.clip(base + g.normal(0, 10, base.shape), 0, 255).astype(np.uint8))
-    joints = np.concatenate([g.normal((112, 108), 25, (N_IMAGES, 21, 2)), g.normal(0, 1, (N_IMAGES, 21, 1))], axis=2)
+    joints = np.concatenate([g.normal(np.array(centres)[:, None], 25, (N_IMAGES, 21, 2)), g.normal(0, 1, (N_IMAGES, 21, 1))], axis=2)
+    if mixed:  # a list of device tensors: a batch is packed on the device
+        return [torch.from_numpy(im).to(DEV) for im in imgs], torch.from_numpy(joints).float()
     return torch.from_numpy(np.stack(imgs)).to(DEV), torch.from_numpy(joints).float()
 
 
 def main():
-    images, joints = make_dataset()
+    args = [a for a in sys.argv[1:] if a != "--mixed-sizes"]
+    mixed = len(args) != len(sys.argv) - 1
+    images, joints = make_dataset(mixed)
     cfg = hybrid2_config(resnet_size="18", projection_head_input_dim=512, augmentation=["crop", "rotate"],
                          batch_size=PAIRS, num_samples=N_IMAGES, warmup_epochs=2, pretrained=False)
     torch.manual_seed(0)
@@ -52,7 +59,10 @@ def main():
         order.shuffle(idx)
         for s in range(0, N_IMAGES, PAIRS):
             sel = torch.tensor(idx[s:s + PAIRS])
-            yield aug(images[sel.to(DEV)], joints[sel])
+            if mixed:
+                yield aug(RaggedImages.from_list([images[i] for i in sel.tolist()], DEV), joints[sel])
+            else:
+                yield aug(images[sel.to(DEV)], joints[sel])
 
     curve = []
     orig = model.training_epoch_end
@@ -68,12 +78,12 @@ def main():
     tr.fit(model, batches)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    out = {"epochs": EPOCHS, "steps": tr.global_step, "pairs_per_step": PAIRS, "seconds": round(dt, 1),
+    out = {"mixed_sizes": mixed, "epochs": EPOCHS, "steps": tr.global_step, "pairs_per_step": PAIRS, "seconds": round(dt, 1),
            "images_per_s_incl_augmentation_and_capture": round(2 * PAIRS * tr.global_step / dt), "epoch_mean_loss": curve}
     print(json.dumps(out))
     assert curve[-1] < 0.8 * curve[0], "the loss did not fall"
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "w") as f:
+    if args:
+        with open(args[0], "w") as f:
             json.dump(out, f, indent=1)
 
 
