@@ -19,6 +19,7 @@ _LIB_PATH = os.environ.get("PECLR_HIP_LIB") or os.path.join(os.path.dirname(os.p
 _LIB = None
 
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
+DTYPE_F32, DTYPE_BF16, DTYPE_F16, DTYPE_F64 = 0, 1, 2, 3   # PECLR_DTYPE_*: the element type of an activation tensor
 ALIGN_CROP, ALIGN_ROTATE, ALIGN_SINGLE_NORM = 1, 2, 4
 OPT_CHUNK = 4096
 
@@ -174,15 +175,6 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def capture_id() -> int:
-    """Identity of the hipGraph capture the current stream is in; 0 when it is not capturing."""
-    if not torch.cuda.is_current_stream_capturing():
-        return 0
-    out = ctypes.c_ulonglong(0)
-    _check(lib().peclr_stream_capture_id(_stream(), ctypes.addressof(out)), "peclr_stream_capture_id")
-    return int(out.value) or 1
-
-
 # ---- optional per-kernel HIP-event timing (bench.py): one entry point = one launch, so an event
 # pair recorded on the launch stream around a call times exactly that kernel.
 EVENT_LOG = None  # None = off; dict name -> list[(start, end)] when bench.py turns it on
@@ -222,6 +214,28 @@ class _timed:
         return False
 
 
+def _call(name: str, *args):
+    """Call the status-returning entry point `name` (a SIGNATURES key) with `args` as the header orders them -- the stream
+    last, spelled out by the caller -- and raise under that same name if it refuses."""
+    _check(getattr(lib(), name)(*args), name)
+
+
+def _launch(tag: str, name: str, *args, nbytes=0, flops=0, kernel=None):
+    """`_call` for an entry point that is one kernel launch, timed under `tag` (see `_timed`)."""
+    with _timed(tag, nbytes, flops, kernel):
+        rc = getattr(lib(), name)(*args)
+    _check(rc, name)
+
+
+def capture_id() -> int:
+    """Identity of the hipGraph capture the current stream is in; 0 when it is not capturing."""
+    if not torch.cuda.is_current_stream_capturing():
+        return 0
+    out = ctypes.c_ulonglong(0)
+    _call("peclr_stream_capture_id", _stream(), ctypes.addressof(out))
+    return int(out.value) or 1
+
+
 # ------------------------------------------------------------------ GEMM
 def pick_split_k(m: int, n: int, k: int) -> int:
     return lib().peclr_gemm_pick_split_k(m, n, k)
@@ -244,21 +258,23 @@ def gemm(layout: int, a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Ten
     else:
         out = torch.empty((split_k, m, n), device=a.device, dtype=torch.float32)
         c_ptr, slab_ptr = None, out.data_ptr()
-    with _timed(tag or f"gemm_{('nt', 'nn', 'tn')[layout]}_{m}x{n}x{k}"):
-        rc = lib().peclr_gemm_f32(layout, m, n, k, _ptr(a, what="gemm A"), a.stride(0), _ptr(b, what="gemm B"),
-                                  b.stride(0), c_ptr, n, _ptr(bias, what="gemm bias"), split_k, slab_ptr,
-                                  _stream())
-    _check(rc, "peclr_gemm_f32")
+    _launch(tag or f"gemm_{('nt', 'nn', 'tn')[layout]}_{m}x{n}x{k}", "peclr_gemm_f32",
+            layout, m, n, k, _ptr(a, what="gemm A"), a.stride(0), _ptr(b, what="gemm B"), b.stride(0), c_ptr, n,
+            _ptr(bias, what="gemm bias"), split_k, slab_ptr, _stream())
     return out
 
 
 def slab_reduce(slabs: torch.Tensor, bias: Optional[torch.Tensor] = None, tag: str = "slab_reduce") -> torch.Tensor:
     s, rows, cols = slabs.shape
     out = torch.empty((rows, cols), device=slabs.device, dtype=torch.float32)
-    with _timed(tag, 4 * (s + 1) * rows * cols, kernel="slab_reduce_kernel"):
-        rc = lib().peclr_slab_reduce_f32(_ptr(slabs), s, rows, cols, _ptr(bias), out.data_ptr(), _stream())
-    _check(rc, "peclr_slab_reduce_f32")
+    _launch(tag, "peclr_slab_reduce_f32", _ptr(slabs), s, rows, cols, _ptr(bias), out.data_ptr(), _stream(),
+            nbytes=4 * (s + 1) * rows * cols, kernel="slab_reduce_kernel")
     return out
+
+
+def _sum_slabs(slabs: torch.Tensor, tag: str = "slab_reduce") -> torch.Tensor:
+    """The tail of every split-K wrapper: the only slab as it is, several summed in their fixed order."""
+    return slabs[0] if slabs.shape[0] == 1 else slab_reduce(slabs, tag=tag)
 
 
 # ------------------------------------------------------------------ BN + ReLU
@@ -269,13 +285,11 @@ def bn_relu_fwd(a_slabs, bias, gamma, beta, eps, momentum, training, running_mea
     a_pre = torch.empty((m, h), device=dev, dtype=torch.float32)
     a_out = torch.empty((m, h), device=dev, dtype=torch.float32)
     save = torch.empty((2, h), device=dev, dtype=torch.float32)
-    with _timed("bn_relu_fwd"):
-        rc = lib().peclr_bn_relu_fwd_f32(
+    _launch("bn_relu_fwd", "peclr_bn_relu_fwd_f32",
             _ptr(a_slabs), s, _ptr(bias), m, h, _ptr(gamma), _ptr(beta), eps, momentum, int(training),
             _ptr(running_mean), _ptr(running_var),
             _ptr(num_batches_tracked, torch.int64, "num_batches_tracked"), a_pre.data_ptr(), a_out.data_ptr(),
             save[0].data_ptr(), save[1].data_ptr(), _stream())
-    _check(rc, "peclr_bn_relu_fwd_f32")
     return a_pre, a_out, save
 
 
@@ -283,12 +297,10 @@ def bn_relu_bwd(d_a_out, a_pre, save, gamma, beta, training=True):
     m, h = a_pre.shape
     d_a_pre = torch.empty_like(a_pre)
     dparams = torch.empty((3, h), device=a_pre.device, dtype=torch.float32)  # dgamma, dbeta, dbias
-    with _timed("bn_relu_bwd"):
-        rc = lib().peclr_bn_relu_bwd_f32(_ptr(d_a_out), _ptr(a_pre), save[0].data_ptr(), save[1].data_ptr(),
-                                         _ptr(gamma), _ptr(beta), m, h, int(training), d_a_pre.data_ptr(),
-                                         dparams[0].data_ptr(), dparams[1].data_ptr(), dparams[2].data_ptr(),
-                                         _stream())
-    _check(rc, "peclr_bn_relu_bwd_f32")
+    _launch("bn_relu_bwd", "peclr_bn_relu_bwd_f32",
+            _ptr(d_a_out), _ptr(a_pre), save[0].data_ptr(), save[1].data_ptr(), _ptr(gamma), _ptr(beta), m, h,
+            int(training), d_a_pre.data_ptr(), dparams[0].data_ptr(), dparams[1].data_ptr(), dparams[2].data_ptr(),
+            _stream())
     return d_a_pre, dparams[0], dparams[1], dparams[2]
 
 
@@ -303,11 +315,9 @@ def align_fwd(p_slabs, n_pairs, flags, jitter, extents, angles, want_stats=True)
     row_stats = torch.empty((m, 8), device=dev, dtype=torch.float32) if want_stats else None
     j = [_ptr(t, torch.int64, "jitter") for t in jitter] if jitter is not None else [None] * 4
     a = [_ptr(t, torch.float64, "angle") for t in angles] if angles is not None else [None] * 2
-    with _timed("align_fwd"):
-        rc = lib().peclr_align_fwd_f32(_ptr(p_slabs), s, m, d, n_pairs, flags, j[0], j[1], j[2], j[3],
-                                       float(extents[0]), float(extents[1]), a[0], a[1], p.data_ptr(),
-                                       z.data_ptr(), norms.data_ptr(), _ptr(row_stats), _stream())
-    _check(rc, "peclr_align_fwd_f32")
+    _launch("align_fwd", "peclr_align_fwd_f32",
+            _ptr(p_slabs), s, m, d, n_pairs, flags, j[0], j[1], j[2], j[3], float(extents[0]), float(extents[1]),
+            a[0], a[1], p.data_ptr(), z.data_ptr(), norms.data_ptr(), _ptr(row_stats), _stream())
     return p, z, norms, row_stats
 
 
@@ -315,10 +325,8 @@ def align_bwd(dz, p, z, norms, n_pairs, flags, angles):
     m, d = p.shape
     dp = torch.empty_like(p)
     a = [_ptr(t, torch.float64, "angle") for t in angles] if angles is not None else [None] * 2
-    with _timed("align_bwd"):
-        rc = lib().peclr_align_bwd_f32(_ptr(dz, what="dz"), _ptr(p), _ptr(z), _ptr(norms), m, d, n_pairs,
-                                       flags, a[0], a[1], dp.data_ptr(), _stream())
-    _check(rc, "peclr_align_bwd_f32")
+    _launch("align_bwd", "peclr_align_bwd_f32",
+            _ptr(dz, what="dz"), _ptr(p), _ptr(z), _ptr(norms), m, d, n_pairs, flags, a[0], a[1], dp.data_ptr(), _stream())
     return dp
 
 
@@ -342,16 +350,12 @@ def ntxent_fwd(z_rows, row_offset, z_all, n_half, inv_tau, loss_scale, row_stats
     row_lse = torch.empty(mr, device=dev, dtype=torch.float32)
     out17 = torch.zeros(17, device=dev, dtype=torch.float32)
     sim = torch.empty((mr, mg), device=dev, dtype=torch.float32) if want_sim else None
-    with _timed("ntxent_fwd"):
-        rc = lib().peclr_ntxent_fwd_f32(_ptr(z_rows, what="z_rows"), mr, row_offset, _ptr(z_all, what="z_all"),
-                                        mg, d, n_half, inv_tau, _ptr(sim), partial.data_ptr(), pos.data_ptr(),
-                                        js, _stream())
-    _check(rc, "peclr_ntxent_fwd_f32")
-    with _timed("ntxent_finalize"):
-        rc = lib().peclr_ntxent_finalize_f32(partial.data_ptr(), js, pos.data_ptr(), mr, loss_scale,
-                                             row_lse.data_ptr(), _ptr(row_stats), n_pairs_stats,
-                                             out17.data_ptr(), _stream())
-    _check(rc, "peclr_ntxent_finalize_f32")
+    _launch("ntxent_fwd", "peclr_ntxent_fwd_f32",
+            _ptr(z_rows, what="z_rows"), mr, row_offset, _ptr(z_all, what="z_all"), mg, d, n_half, inv_tau, _ptr(sim),
+            partial.data_ptr(), pos.data_ptr(), js, _stream())
+    _launch("ntxent_finalize", "peclr_ntxent_finalize_f32",
+            partial.data_ptr(), js, pos.data_ptr(), mr, loss_scale, row_lse.data_ptr(), _ptr(row_stats), n_pairs_stats,
+            out17.data_ptr(), _stream())
     return out17, row_lse, sim
 
 
@@ -360,12 +364,10 @@ def ntxent_bwd(z_rows, row_offset, z_all, n_half, inv_tau, lse_all, dloss, grad_
     mg = z_all.shape[0]
     js = ntxent_jsplit(mr, mg, True)
     slabs = torch.empty((js, mr, d), device=z_rows.device, dtype=torch.float32)
-    with _timed("ntxent_bwd"):
-        rc = lib().peclr_ntxent_bwd_f32(_ptr(z_rows, what="z_rows"), mr, row_offset, _ptr(z_all, what="z_all"),
-                                        mg, d, n_half, inv_tau, _ptr(lse_all, what="lse_all"),
-                                        _ptr(dloss, what="dloss"), grad_scale, slabs.data_ptr(), js, _stream())
-    _check(rc, "peclr_ntxent_bwd_f32")
-    return slabs[0] if js == 1 else slab_reduce(slabs)
+    _launch("ntxent_bwd", "peclr_ntxent_bwd_f32",
+            _ptr(z_rows, what="z_rows"), mr, row_offset, _ptr(z_all, what="z_all"), mg, d, n_half, inv_tau,
+            _ptr(lse_all, what="lse_all"), _ptr(dloss, what="dloss"), grad_scale, slabs.data_ptr(), js, _stream())
+    return _sum_slabs(slabs)
 
 
 # ------------------------------------------------------------------ optimiser
@@ -390,31 +392,21 @@ def lars_adam_step(ptrs, sizes, n_tensors, chunk_tensor, chunk_offset, tensor_ch
         st = _ptr(state, torch.int32, "amp state")
         if state.numel() != 4:
             raise PeclrHipError("amp state: expected 4 x 32-bit words (peclr_amp_state)")
-        with _timed("lars_sumsq"):
-            rc = lib().peclr_lars_sumsq_amp_f32(p, sz, n_tensors, ct, co, n_chunks, _ptr(norms_ws), st, _stream())
-        _check(rc, "peclr_lars_sumsq_amp_f32")
-        with _timed("lars_adam_update"):
-            rc = lib().peclr_lars_adam_update_amp_f32(
+        _launch("lars_sumsq", "peclr_lars_sumsq_amp_f32", p, sz, n_tensors, ct, co, n_chunks, _ptr(norms_ws), st, _stream())
+        _launch("lars_adam_update", "peclr_lars_adam_update_amp_f32",
                 p, sz, n_tensors, ct, co, _ptr(tensor_chunk_begin, torch.int32, "tensor_chunk_begin"),
                 _ptr(tensor_group, torch.int32, "tensor_group"), n_chunks, _ptr(norms_ws), _ptr(device_hyper),
                 ctypes.cast(lr_arr, c_void_p), ctypes.cast(wd_arr, c_void_p), ng, beta1, beta2, adam_eps,
                 int(use_lars), lars_eta, lars_eps, int(lars_clip), st, _stream())
-        _check(rc, "peclr_lars_adam_update_amp_f32")
-        with _timed("amp_update", nbytes=16):
-            rc = lib().peclr_amp_update(st, growth, backoff, int(interval), _stream())
-        _check(rc, "peclr_amp_update")
+        _launch("amp_update", "peclr_amp_update", st, growth, backoff, int(interval), _stream(), nbytes=16)
         return
     if use_lars:
-        with _timed("lars_sumsq"):
-            rc = lib().peclr_lars_sumsq_f32(p, sz, n_tensors, ct, co, n_chunks, _ptr(norms_ws), _stream())
-        _check(rc, "peclr_lars_sumsq_f32")
-    with _timed("lars_adam_update"):
-        rc = lib().peclr_lars_adam_update_f32(
+        _launch("lars_sumsq", "peclr_lars_sumsq_f32", p, sz, n_tensors, ct, co, n_chunks, _ptr(norms_ws), _stream())
+    _launch("lars_adam_update", "peclr_lars_adam_update_f32",
             p, sz, n_tensors, ct, co, _ptr(tensor_chunk_begin, torch.int32, "tensor_chunk_begin"),
             _ptr(tensor_group, torch.int32, "tensor_group"), n_chunks, _ptr(norms_ws), _ptr(device_hyper),
             ctypes.cast(lr_arr, c_void_p), ctypes.cast(wd_arr, c_void_p), ng, beta1, beta2, adam_eps, bias_corr1,
             bias_corr2, int(use_lars), lars_eta, lars_eps, int(lars_clip), _stream())
-    _check(rc, "peclr_lars_adam_update_f32")
 
 
 def gemm_add(layout: int, a: torch.Tensor, b: torch.Tensor, addend: torch.Tensor, tag: str = "gemm_add") -> torch.Tensor:
@@ -428,10 +420,9 @@ def gemm_add(layout: int, a: torch.Tensor, b: torch.Tensor, addend: torch.Tensor
     if k != k2 or tuple(addend.shape) != (m, n):
         raise PeclrHipError(f"gemm_add: shapes {tuple(a.shape)} x {tuple(b.shape)} + {tuple(addend.shape)} (layout {layout})")
     out = torch.empty((m, n), device=a.device, dtype=torch.float32)
-    with _timed(tag, 4 * (m * k + k * n + 2 * m * n), 2 * m * n * k, kernel="gemm_f32 (v_mfma_f32)"):
-        rc = lib().peclr_gemm_add_f32(layout, m, n, k, _ptr(a), a.shape[1], _ptr(b), b.shape[1], out.data_ptr(), n,
-                                      _ptr(addend), n, _stream())
-    _check(rc, "peclr_gemm_add_f32")
+    _launch(tag, "peclr_gemm_add_f32", layout, m, n, k, _ptr(a), a.shape[1], _ptr(b), b.shape[1], out.data_ptr(), n,
+            _ptr(addend), n, _stream(),
+            nbytes=4 * (m * k + k * n + 2 * m * n), flops=2 * m * n * k, kernel="gemm_f32 (v_mfma_f32)")
     return out
 
 
@@ -444,9 +435,8 @@ def gemm_x6(a: torch.Tensor, b_t: torch.Tensor, addend: Optional[torch.Tensor] =
         raise PeclrHipError(f"gemm_x6: shapes {tuple(a.shape)} x {tuple(b_t.shape)}^T")
     if out is None:
         out = torch.empty((m, n), device=a.device, dtype=torch.float32)
-    with _timed(tag, 4 * (m * k + k * n + (2 if addend is not None else 1) * m * n), 2 * m * n * k, kernel="gemm_x6_nt128_kernel"):
-        rc = lib().peclr_gemm_x6_f32(m, n, k, _ptr(a), k, _ptr(b_t), k, _ptr(out), n, _ptr(addend), n, _stream())
-    _check(rc, "peclr_gemm_x6_f32")
+    _launch(tag, "peclr_gemm_x6_f32", m, n, k, _ptr(a), k, _ptr(b_t), k, _ptr(out), n, _ptr(addend), n, _stream(),
+            nbytes=4 * (m * k + k * n + (2 if addend is not None else 1) * m * n), flops=2 * m * n * k, kernel="gemm_x6_nt128_kernel")
     return out
 
 
@@ -464,32 +454,77 @@ def _byref(struct):
 
 
 def _epilogue(who: str, m: int, n: int, tile_rows: int, stat_shift, bn_bwd, device, groups: int = 1, dtype=torch.float32,
-              row_blocks: int = 0):
+              row_blocks: int = 0, pick_rows=None):
     """The fused epilogue of a packed-operand GEMM / convolution `who` whose [m, n] output is computed in blocks of `tile_rows` rows
-    -> (partial, n_split, fuse).  n_split: `row_blocks` where the kernel reports its own count, else the row blocks of each of
-    `groups` equal row sets.
+    -> (tile_rows, partial, n_split, fuse).  tile_rows: as given, or -- 0 and an epilogue asked for -- what `pick_rows()` says the
+    library will choose.  n_split: `row_blocks` where the kernel reports its own count, else the row blocks of each of `groups`
+    equal row sets.
     stat_shift (fp32 [n]): the output's BatchNorm statistics -- partial [2 n_split + 1, n] in peclr_bn2d_stats' layout (the shift in
     the last row), fuse None;
     else bn_bwd = (x, save [2, n], ss [2, n], mask or None, relu) of the BatchNorm layer whose incoming gradient the output is (x:
     that layer's input, m * n elements of `dtype`) -- partial [2 n_split, n] in peclr_bn2d_bwd_reduce's layout, fuse the
     peclr_bn_bwd_fuse to pass by reference (`_byref`);
-    neither: (None, 0, None)."""
+    neither: (tile_rows, None, 0, None)."""
     if stat_shift is None and bn_bwd is None:
-        return None, 0, None
+        return tile_rows, None, 0, None
+    if pick_rows is not None:
+        tile_rows = tile_rows or pick_rows()
     ns = row_blocks or groups * ((m // groups + tile_rows - 1) // tile_rows)
     if stat_shift is not None:
         if stat_shift.numel() != n:
             raise PeclrHipError(f"{who}: stat_shift has {stat_shift.numel()} entries for {n} columns")
-        return torch.empty((2 * ns + 1, n), device=device, dtype=torch.float32), ns, None
+        return tile_rows, torch.empty((2 * ns + 1, n), device=device, dtype=torch.float32), ns, None
     x, save, ss, mask, relu = bn_bwd
     if x.dtype != dtype or x.numel() != m * n or not x.is_cuda:
         raise PeclrHipError(f"bn backward fusion: layer input of {x.numel()} {x.dtype} elements for a {dtype} [{m}, {n}] gradient")
     partial = torch.empty((2 * ns, n), device=device, dtype=torch.float32)
-    return partial, ns, _BnBwdFuse(x.data_ptr(), save[0].data_ptr(), save[1].data_ptr(), _ptr(ss), _ptr(mask, torch.int32, "relu mask"),
-                                   int(relu), partial.data_ptr())
+    return tile_rows, partial, ns, _BnBwdFuse(x.data_ptr(), save[0].data_ptr(), save[1].data_ptr(), _ptr(ss),
+                                              _ptr(mask, torch.int32, "relu mask"), int(relu), partial.data_ptr())
 
 
-class X6Planes:
+def _with_partial(out, partial, ns):
+    """What a wrapper with a fused epilogue returns: the output alone, or (output, partial, n_split) when `_epilogue` made one."""
+    return out if partial is None else (out, partial, ns)
+
+
+def _check_addend_modes(who: str, m: int, n: int, addend, stat_shift, addend_s2, addend_mask):
+    """The compact (addend_s2) and the masked (addend_mask) addend of the packed-operand GEMM `who` with an [m, n] output."""
+    if addend_s2 is not None and (addend is None or stat_shift is not None or addend_mask is not None):
+        raise PeclrHipError(f"{who}: addend_s2 needs the compact addend (and has no statistics output / mask)")
+    if addend_mask is not None and (addend is None or stat_shift is not None or n % 32 or addend_mask.dtype != torch.int32
+                                    or addend_mask.numel() != m * (n // 32) or not addend_mask.is_contiguous()):
+        raise PeclrHipError(f"{who}: addend_mask is the int32 [M, n / 32] bit mask of a dense addend (no statistics output)")
+
+
+class _WeightPlanes:
+    """What X6Planes and HPlanes share: one plane buffer per matrix, and the int64 device table [count, 8] the pack kernels walk
+    (weight pointer, plane pointer, n, k, row stride, transposed, first chunk, format).  `who` names the class in messages,
+    `what` the weights in `_ptr`'s; `pack_bytes`: the entry point that sizes one matrix's planes; `k_step`: the k extent of a chunk."""
+
+    def __init__(self, who: str, what: str, specs, pack_bytes: str, k_step: int, fmt: int):
+        dev = specs[0][0].device
+        rows, self.planes, self.shapes, chunk = [], [], [], 0
+        for w, transposed in specs:
+            _ptr(w, what=what)
+            if w.dim() != 2:
+                raise PeclrHipError(f"{who}: 2-D weight matrices expected")
+            t = int(transposed)                     # 0 plain, 1 transposed, T > 1: T-tap filter [Cout * T, Cin] for its input gradient
+            n, k = (w.shape[1], w.shape[0]) if t else (w.shape[0], w.shape[1])
+            nbytes = getattr(lib(), pack_bytes)(n, k)
+            if nbytes <= 0:
+                raise PeclrHipError(f"{who}: B_t[{n}, {k}] needs n % 64 == 0 and k % {k_step} == 0")
+            planes = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+            rows.append([w.data_ptr(), planes.data_ptr(), n, k, w.stride(0), t, chunk, fmt])
+            chunk += ((n + 127) // 128) * (k // k_step)
+            self.planes.append(planes)
+            self.shapes.append((n, k))
+        self._sources = [w for w, _ in specs]          # keep the storage alive
+        self.table = torch.tensor(rows, dtype=torch.int64).to(dev)
+        self.count, self.chunks = len(rows), chunk
+        self.nbytes = sum(p.numel() for p in self.planes) + 4 * sum(w.numel() for w in self._sources)
+
+
+class X6Planes(_WeightPlanes):
     """Weight matrices split once into fragment-ordered bf16 planes (peclr_x6_pack_f32) for peclr_gemm_x6p_f32.
     `specs`: list of (fp32 2-D HIP tensor W, transposed) -- B_t = W ([N, K]) or W^T (W is [K, N]).  The device table is
     built once (the tensors' storage must stay where it is: parameters do); `pack()` is ONE launch that re-splits every
@@ -500,28 +535,10 @@ class X6Planes:
         the three bf16 planes."""
         if not specs:
             raise PeclrHipError("X6Planes: nothing to pack")
-        dev = specs[0][0].device
         self.pair = bool(pair)
-        rows, self.planes, self.shapes, chunk = [], [], [], 0
-        for w, transposed in specs:
-            _ptr(w, what="x6 weight")
-            if w.dim() != 2:
-                raise PeclrHipError("X6Planes: 2-D weight matrices expected")
-            t = int(transposed)                     # 0 plain, 1 transposed, T > 1: T-tap filter [Cout * T, Cin] for its input gradient
-            n, k = (w.shape[1], w.shape[0]) if t else (w.shape[0], w.shape[1])
-            nbytes = lib().peclr_x6_pack_pair_bytes(n, k) if self.pair else lib().peclr_x6_pack_bytes(n, k)
-            if nbytes <= 0:
-                raise PeclrHipError(f"X6Planes: B_t[{n}, {k}] needs n % 64 == 0 and k % 16 == 0")
-            planes = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-            rows.append([w.data_ptr(), planes.data_ptr(), n, k, w.stride(0), t, chunk, 0])
-            chunk += ((n + 127) // 128) * (k // 16)
-            self.planes.append(planes)
-            self.shapes.append((n, k))
-        self._sources = [w for w, _ in specs]          # keep the storage alive
-        self.table = torch.tensor(rows, dtype=torch.int64).to(dev)
-        self.count, self.chunks = len(rows), chunk
-        self.nbytes = sum(p.numel() for p in self.planes) + 4 * sum(w.numel() for w in self._sources)
+        super().__init__("X6Planes", "x6 weight", specs, "peclr_x6_pack_pair_bytes" if self.pair else "peclr_x6_pack_bytes", 16, 0)
         if self.pair:
+            dev = self.table.device
             self.wbytes = 4 * sum(w.numel() for w in self._sources)       # (the maxima's pass reads the weights once more)
             self.absmax = torch.zeros(self.count, device=dev, dtype=torch.float32)
             self.scales = torch.ones(self.count, device=dev, dtype=torch.float32)
@@ -532,17 +549,13 @@ class X6Planes:
 
     def pack(self):
         if self.pair:
-            with _timed("x6_absmax", self.wbytes, kernel="x6_pair_kernel"):
-                rc = lib().peclr_x6_absmax_f32(self.table.data_ptr(), self.count, self.chunks, self.absmax.data_ptr(), _stream())
-            _check(rc, "peclr_x6_absmax_f32")
-            with _timed("x6_pack", self.nbytes, kernel="x6_pair_kernel"):
-                rc = lib().peclr_x6_pack_pair_f32(self.table.data_ptr(), self.count, self.chunks, self.absmax.data_ptr(),
-                                                  self.scales.data_ptr(), _stream())
-            _check(rc, "peclr_x6_pack_pair_f32")
+            _launch("x6_absmax", "peclr_x6_absmax_f32", self.table.data_ptr(), self.count, self.chunks, self.absmax.data_ptr(), _stream(),
+                    nbytes=self.wbytes, kernel="x6_pair_kernel")
+            _launch("x6_pack", "peclr_x6_pack_pair_f32", self.table.data_ptr(), self.count, self.chunks, self.absmax.data_ptr(),
+                    self.scales.data_ptr(), _stream(), nbytes=self.nbytes, kernel="x6_pair_kernel")
             return self
-        with _timed("x6_pack", self.nbytes, kernel="x6_pack_kernel"):
-            rc = lib().peclr_x6_pack_f32(self.table.data_ptr(), self.count, self.chunks, _stream())
-        _check(rc, "peclr_x6_pack_f32")
+        _launch("x6_pack", "peclr_x6_pack_f32", self.table.data_ptr(), self.count, self.chunks, _stream(),
+                nbytes=self.nbytes, kernel="x6_pack_kernel")
         return self
 
 
@@ -582,32 +595,22 @@ def gemm_x6p(a: torch.Tensor, planes: torch.Tensor, n: int, addend: Optional[tor
     pst, wb = _pair_arg(pair, "gemm_x6p")
     if planes.dtype != torch.uint8 or planes.numel() != wb * ((n + 127) // 128 * 128) * k or (addend is not None and tuple(addend.shape) != (add_rows, n)):
         raise PeclrHipError(f"gemm_x6p: A {tuple(a.shape)}, planes of {planes.numel()} bytes for B_t[{n}, {k}]")
-    if addend_s2 is not None and (addend is None or stat_shift is not None or addend_mask is not None):
-        raise PeclrHipError("gemm_x6p: addend_s2 needs the compact addend (and has no statistics output / mask)")
-    if addend_mask is not None and (addend is None or stat_shift is not None or n % 32 or addend_mask.dtype != torch.int32
-                                    or addend_mask.numel() != m * (n // 32) or not addend_mask.is_contiguous()):
-        raise PeclrHipError("gemm_x6p: addend_mask is the int32 [M, n / 32] bit mask of a dense addend (no statistics output)")
+    _check_addend_modes("gemm_x6p", m, n, addend, stat_shift, addend_s2, addend_mask)
     out = torch.empty((m, n), device=a.device, dtype=torch.float32)
-    tile_rows = tile_rows or _X6P_TILE_ROWS
-    if stat_shift is not None or bn_bwd is not None:
-        tile_rows = tile_rows or lib().peclr_gemm_x6p_tile_rows(m, n, k)
-    partial, ns, fuse = _epilogue("gemm_x6p", m, n, tile_rows, stat_shift, bn_bwd, a.device)
+    tile_rows, partial, ns, fuse = _epilogue("gemm_x6p", m, n, tile_rows or _X6P_TILE_ROWS, stat_shift, bn_bwd, a.device,
+                                             pick_rows=lambda: lib().peclr_gemm_x6p_tile_rows(m, n, k))
     add_elems = 0 if addend is None else addend.numel() + (0 if addend_mask is None else addend_mask.numel())
-    with _timed(tag, 4 * (m * k + m * n + add_elems + (m * n if fuse is not None else 0)) + wb * k * n, 2 * m * n * k,
-                kernel="gemm_x6p_kernel" if pst is None else "gemm_x6p_kernel<pair>"):
-        if addend_mask is not None:
-            rc = lib().peclr_gemm_x6p_maskadd_f32(m, n, k, _ptr(a), k, _ptr(planes, torch.uint8), out.data_ptr(), n, _ptr(addend), n,
-                                                  _ptr(addend_mask, torch.int32), tile_rows, _byref(fuse), _byref(pst), _stream())
-        elif addend_s2 is not None:
-            rc = lib().peclr_gemm_x6p_s2add_f32(m, n, k, _ptr(a), k, _ptr(planes, torch.uint8), out.data_ptr(), n, _ptr(addend), n,
-                                                int(addend_s2[0]), int(addend_s2[1]), tile_rows, _byref(fuse), _byref(pst), _stream())
-        else:
-            rc = lib().peclr_gemm_x6p_f32(m, n, k, _ptr(a), k, _ptr(planes, torch.uint8), out.data_ptr(), n, _ptr(addend), n,
-                                          tile_rows, _ptr(stat_shift), partial.data_ptr() if stat_shift is not None else None,
-                                          _byref(fuse), _byref(pst), _stream())
-    _check(rc, "peclr_gemm_x6p_maskadd_f32" if addend_mask is not None else "peclr_gemm_x6p_s2add_f32" if addend_s2 is not None
-           else "peclr_gemm_x6p_f32")
-    return out if partial is None else (out, partial, ns)
+    head = (m, n, k, _ptr(a), k, _ptr(planes, torch.uint8), out.data_ptr(), n, _ptr(addend), n)
+    if addend_mask is not None:
+        name, args = "peclr_gemm_x6p_maskadd_f32", (_ptr(addend_mask, torch.int32), tile_rows)
+    elif addend_s2 is not None:
+        name, args = "peclr_gemm_x6p_s2add_f32", (int(addend_s2[0]), int(addend_s2[1]), tile_rows)
+    else:
+        name, args = "peclr_gemm_x6p_f32", (tile_rows, _ptr(stat_shift), partial.data_ptr() if stat_shift is not None else None)
+    _launch(tag, name, *head, *args, _byref(fuse), _byref(pst), _stream(),
+            nbytes=4 * (m * k + m * n + add_elems + (m * n if fuse is not None else 0)) + wb * k * n, flops=2 * m * n * k,
+            kernel="gemm_x6p_kernel" if pst is None else "gemm_x6p_kernel<pair>")
+    return _with_partial(out, partial, ns)
 
 
 _CONV3X3_VARIANT = int(os.environ.get("PECLR_CONV3X3_HALO", "1"))   # A/B: 1 = one split per 16-channel chunk and workgroup (halo patch in LDS)
@@ -635,17 +638,15 @@ def conv3x3_x6p(x: torch.Tensor, planes: torch.Tensor, cout: int, flip: bool = F
         raise PeclrHipError(f"conv3x3_x6p: planes of {planes.numel()} bytes for [{cout}, 9 * {cin}]")
     y = torch.empty((nb, cout, h, w), device=x.device, dtype=torch.float32, memory_format=torch.channels_last)
     m = nb * h * w
-    if stat_shift is not None or bn_bwd is not None:
-        tile_rows = tile_rows or lib().peclr_gemm_x6p_tile_rows(m, cout, 9 * cin)
-    partial, ns, fuse = _epilogue("conv3x3_x6p", m, cout, tile_rows, stat_shift, bn_bwd, x.device)
+    tile_rows, partial, ns, fuse = _epilogue("conv3x3_x6p", m, cout, tile_rows, stat_shift, bn_bwd, x.device,
+                                             pick_rows=lambda: lib().peclr_gemm_x6p_tile_rows(m, cout, 9 * cin))
     ap = _nhwc_ptr(addend, "conv3x3 addend", torch.float32) if addend is not None else None
-    with _timed(tag, 4 * (m * cin + (2 if addend is not None else 1) * m * cout + (m * cout if fuse is not None else 0)) + 9 * wb * cin * cout,
-                18 * m * cin * cout, kernel="gemm_x6p_kernel (3x3)" if pst is None else "gemm_x6p_kernel<pair> (3x3)"):
-        rc = lib().peclr_conv3x3_x6p_f32(nb, h, w, cin, cout, xp, _ptr(planes, torch.uint8), y.data_ptr(), ap, int(flip), tile_rows,
-                                         _CONV3X3_VARIANT if variant is None else int(variant), _zeros(x.device).data_ptr(), _ptr(stat_shift),
-                                         partial.data_ptr() if stat_shift is not None else None, _byref(fuse), _byref(pst), _stream())
-    _check(rc, "peclr_conv3x3_x6p_f32")
-    return y if partial is None else (y, partial, ns)
+    _launch(tag, "peclr_conv3x3_x6p_f32", nb, h, w, cin, cout, xp, _ptr(planes, torch.uint8), y.data_ptr(), ap, int(flip), tile_rows,
+            _CONV3X3_VARIANT if variant is None else int(variant), _zeros(x.device).data_ptr(), _ptr(stat_shift),
+            partial.data_ptr() if stat_shift is not None else None, _byref(fuse), _byref(pst), _stream(),
+            nbytes=4 * (m * cin + (2 if addend is not None else 1) * m * cout + (m * cout if fuse is not None else 0)) + 9 * wb * cin * cout,
+            flops=18 * m * cin * cout, kernel="gemm_x6p_kernel (3x3)" if pst is None else "gemm_x6p_kernel<pair> (3x3)")
+    return _with_partial(y, partial, ns)
 
 
 def conv3x3_s2_dgrad_x6p(gy: torch.Tensor, planes: torch.Tensor, cin: int, tag: str = "conv3x3_s2_dgrad", tile_rows: int = 0, bn_bwd=None,
@@ -661,15 +662,13 @@ def conv3x3_s2_dgrad_x6p(gy: torch.Tensor, planes: torch.Tensor, cin: int, tag: 
         raise PeclrHipError(f"conv3x3_s2_dgrad_x6p: planes of {planes.numel()} bytes for [{cin}, 9 * {cout}]")
     dx = torch.empty((nb, cin, 2 * ho, 2 * wo), device=gy.device, dtype=torch.float32, memory_format=torch.channels_last)
     mc = nb * ho * wo
-    if bn_bwd is not None:
-        tile_rows = tile_rows or lib().peclr_gemm_x6p_tile_rows(mc, cin, 4 * cout)
-    partial, ns, fuse = _epilogue("conv3x3_s2_dgrad_x6p", 4 * mc, cin, tile_rows, None, bn_bwd, gy.device, groups=4)
-    with _timed(tag, 4 * (mc * cout + 4 * mc * cin * (2 if fuse is not None else 1)) + 9 * wb * cin * cout, 18 * mc * cin * cout,
-                kernel="gemm_x6p_kernel (3x3)" if pst is None else "gemm_x6p_kernel<pair> (3x3)"):
-        rc = lib().peclr_conv3x3_s2_dgrad_x6p_f32(nb, ho, wo, cout, cin, gp, _ptr(planes, torch.uint8), dx.data_ptr(), tile_rows,
-                                                  _zeros(gy.device).data_ptr(), _byref(fuse), _byref(pst), _stream())
-    _check(rc, "peclr_conv3x3_s2_dgrad_x6p_f32")
-    return dx if partial is None else (dx, partial, ns)
+    tile_rows, partial, ns, fuse = _epilogue("conv3x3_s2_dgrad_x6p", 4 * mc, cin, tile_rows, None, bn_bwd, gy.device, groups=4,
+                                             pick_rows=lambda: lib().peclr_gemm_x6p_tile_rows(mc, cin, 4 * cout))
+    _launch(tag, "peclr_conv3x3_s2_dgrad_x6p_f32", nb, ho, wo, cout, cin, gp, _ptr(planes, torch.uint8), dx.data_ptr(), tile_rows,
+            _zeros(gy.device).data_ptr(), _byref(fuse), _byref(pst), _stream(),
+            nbytes=4 * (mc * cout + 4 * mc * cin * (2 if fuse is not None else 1)) + 9 * wb * cin * cout, flops=18 * mc * cin * cout,
+            kernel="gemm_x6p_kernel (3x3)" if pst is None else "gemm_x6p_kernel<pair> (3x3)")
+    return _with_partial(dx, partial, ns)
 
 
 def conv_s2_x6p(x: torch.Tensor, planes: torch.Tensor, cout: int, taps: int, tag: str = "conv_s2_x6p", tile_rows: int = 0,
@@ -684,15 +683,13 @@ def conv_s2_x6p(x: torch.Tensor, planes: torch.Tensor, cout: int, taps: int, tag
         raise PeclrHipError(f"conv_s2_x6p: planes of {planes.numel()} bytes for [{cout}, {taps} * {cin}], input {h} x {w}")
     y = torch.empty((nb, cout, h // 2, w // 2), device=x.device, dtype=torch.float32, memory_format=torch.channels_last)
     m = nb * (h // 2) * (w // 2)
-    if stat_shift is not None:
-        tile_rows = tile_rows or lib().peclr_gemm_x6p_tile_rows(m, cout, taps * cin)
-    partial, ns, _ = _epilogue("conv_s2_x6p", m, cout, tile_rows, stat_shift, None, x.device)
-    with _timed(tag, 4 * (nb * h * w * cin + m * cout) + wb * taps * cin * cout, 2 * m * taps * cin * cout,
-                kernel="gemm_x6p_kernel (stride 2)" if pst is None else "gemm_x6p_kernel<pair> (stride 2)"):
-        rc = lib().peclr_conv_s2_x6p_f32(nb, h, w, cin, cout, taps, xp, _ptr(planes, torch.uint8), y.data_ptr(), tile_rows,
-                                         _zeros(x.device).data_ptr(), _ptr(stat_shift), _ptr(partial), _byref(pst), _stream())
-    _check(rc, "peclr_conv_s2_x6p_f32")
-    return y if partial is None else (y, partial, ns)
+    tile_rows, partial, ns, _ = _epilogue("conv_s2_x6p", m, cout, tile_rows, stat_shift, None, x.device,
+                                          pick_rows=lambda: lib().peclr_gemm_x6p_tile_rows(m, cout, taps * cin))
+    _launch(tag, "peclr_conv_s2_x6p_f32", nb, h, w, cin, cout, taps, xp, _ptr(planes, torch.uint8), y.data_ptr(), tile_rows,
+            _zeros(x.device).data_ptr(), _ptr(stat_shift), _ptr(partial), _byref(pst), _stream(),
+            nbytes=4 * (nb * h * w * cin + m * cout) + wb * taps * cin * cout, flops=2 * m * taps * cin * cout,
+            kernel="gemm_x6p_kernel (stride 2)" if pst is None else "gemm_x6p_kernel<pair> (stride 2)")
+    return _with_partial(y, partial, ns)
 
 
 def gemm_x6_tn(a: torch.Tensor, b: torch.Tensor, tag: str = "gemm_x6_tn") -> torch.Tensor:
@@ -706,10 +703,9 @@ def gemm_x6_tn(a: torch.Tensor, b: torch.Tensor, tag: str = "gemm_x6_tn") -> tor
     if ns < 1:
         raise PeclrHipError(f"gemm_x6_tn: unsupported shape M={m} N={n} K={k}")
     slabs = torch.empty((ns, m, n), device=a.device, dtype=torch.float32)
-    with _timed(tag, 4 * (k * m + k * n + ns * m * n), 2 * m * n * k, kernel="gemm_x6_tn128_kernel"):
-        rc = lib().peclr_gemm_x6_tn_f32(m, n, k, _ptr(a), m, _ptr(b), n, slabs.data_ptr(), ns, _stream())
-    _check(rc, "peclr_gemm_x6_tn_f32")
-    return slabs[0] if ns == 1 else slab_reduce(slabs, tag="wgrad_slab_reduce")
+    _launch(tag, "peclr_gemm_x6_tn_f32", m, n, k, _ptr(a), m, _ptr(b), n, slabs.data_ptr(), ns, _stream(),
+            nbytes=4 * (k * m + k * n + ns * m * n), flops=2 * m * n * k, kernel="gemm_x6_tn128_kernel")
+    return _sum_slabs(slabs, "wgrad_slab_reduce")
 
 
 def gemm_x6t(a: torch.Tensor, b: torch.Tensor, taps: int = 1, hw=None, stride: int = 1, tag: str = "gemm_x6t") -> torch.Tensor:
@@ -727,12 +723,11 @@ def gemm_x6t(a: torch.Tensor, b: torch.Tensor, taps: int = 1, hw=None, stride: i
     if ns < 1:
         raise PeclrHipError(f"gemm_x6t: unsupported shape M={m} N={n} K={k}")
     slabs = torch.empty((ns, m, taps * n), device=a.device, dtype=torch.float32)
-    with _timed(tag, 4 * (k * m + k2 * n // (stride * stride) * (1 if taps == 1 else stride * stride) + ns * m * n * taps),
-                2 * m * n * k * taps, kernel="gemm_x6w2_kernel | gemm_x6w_kernel" if taps == 9 else "gemm_x6t2_kernel | gemm_x6t_kernel"):
-        rc = lib().peclr_gemm_x6t_f32(m, n, k, _ptr(a), a.stride(0), _ptr(b), b.stride(0), slabs.data_ptr(), ns, taps, h, w, stride,
-                                      _zeros(a.device).data_ptr(), _stream())
-    _check(rc, "peclr_gemm_x6t_f32")
-    return slabs[0] if ns == 1 else slab_reduce(slabs, tag="wgrad_slab_reduce")
+    _launch(tag, "peclr_gemm_x6t_f32", m, n, k, _ptr(a), a.stride(0), _ptr(b), b.stride(0), slabs.data_ptr(), ns, taps, h, w, stride,
+            _zeros(a.device).data_ptr(), _stream(),
+            nbytes=4 * (k * m + k2 * n // (stride * stride) * (1 if taps == 1 else stride * stride) + ns * m * n * taps),
+            flops=2 * m * n * k * taps, kernel="gemm_x6w2_kernel | gemm_x6w_kernel" if taps == 9 else "gemm_x6t2_kernel | gemm_x6t_kernel")
+    return _sum_slabs(slabs, "wgrad_slab_reduce")
 
 
 def gemm_add_half(a: torch.Tensor, b_t: torch.Tensor, addend: Optional[torch.Tensor], tag: str = "gemm_add") -> torch.Tensor:
@@ -748,19 +743,14 @@ def gemm_add_half(a: torch.Tensor, b_t: torch.Tensor, addend: Optional[torch.Ten
     if k != k2 or (addend is not None and tuple(addend.shape) != (m, n)):
         raise PeclrHipError(f"gemm_add_half: shapes {tuple(a.shape)} x {tuple(b_t.shape)}^T")
     out = torch.empty((m, n), device=a.device, dtype=half)
-    fn = lib().peclr_gemm_add_bf16 if half == torch.bfloat16 else lib().peclr_gemm_add_f16
-    with _timed(tag, 2 * (m * k + k * n + 2 * m * n), 2 * m * n * k):
-        rc = fn(m, n, k, a.data_ptr(), k, b_t.data_ptr(), k, out.data_ptr(), n,
-                addend.data_ptr() if addend is not None else None, n, _stream())
-    _check(rc, "peclr_gemm_add_bf16" if half == torch.bfloat16 else "peclr_gemm_add_f16")
+    _launch(tag, "peclr_gemm_add_bf16" if half == torch.bfloat16 else "peclr_gemm_add_f16",
+            m, n, k, a.data_ptr(), k, b_t.data_ptr(), k, out.data_ptr(), n, addend.data_ptr() if addend is not None else None, n, _stream(),
+            nbytes=2 * (m * k + k * n + 2 * m * n), flops=2 * m * n * k)
     return out
 
 
-gemm_add_bf16 = gemm_add_half   # round-1 name
-
-
 # ------------------------------------------------------------------ 16-bit convolutions (csrc/conv_h.hip)
-_HALF_IO = {torch.bfloat16: 1, torch.float16: 2}      # PECLR_DTYPE_BF16 / _F16
+_HALF_IO = {torch.bfloat16: DTYPE_BF16, torch.float16: DTYPE_F16}
 _HZEROS = {}
 
 
@@ -777,7 +767,7 @@ def _half_io(t: torch.Tensor, what: str) -> int:
     return _HALF_IO[t.dtype]
 
 
-class HPlanes:
+class HPlanes(_WeightPlanes):
     """Weight matrices packed once per optimiser step from the fp32 MASTER weights into 16-bit MFMA-fragment order
     (peclr_h_pack) for peclr_gemm_h / peclr_conv_h -- the cast autocast performs per forward rides in that launch.
     `specs`: list of (fp32 2-D HIP tensor W, transposed) exactly as X6Planes; dtype: torch.bfloat16 or torch.float16."""
@@ -787,32 +777,11 @@ class HPlanes:
             raise PeclrHipError("HPlanes: nothing to pack")
         if dtype not in _HALF_IO:
             raise PeclrHipError(f"HPlanes: bf16 or fp16, got {dtype}")
-        dev = specs[0][0].device
         self.dtype = dtype
-        rows, self.planes, self.shapes, chunk = [], [], [], 0
-        for w, transposed in specs:
-            _ptr(w, what="16-bit pack: fp32 master weight")
-            if w.dim() != 2:
-                raise PeclrHipError("HPlanes: 2-D weight matrices expected")
-            t = int(transposed)
-            n, k = (w.shape[1], w.shape[0]) if t else (w.shape[0], w.shape[1])
-            nbytes = lib().peclr_h_pack_bytes(n, k)
-            if nbytes <= 0:
-                raise PeclrHipError(f"HPlanes: B_t[{n}, {k}] needs n % 64 == 0 and k % 32 == 0")
-            planes = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-            rows.append([w.data_ptr(), planes.data_ptr(), n, k, w.stride(0), t, chunk, _HALF_IO[dtype]])
-            chunk += ((n + 127) // 128) * (k // 32)
-            self.planes.append(planes)
-            self.shapes.append((n, k))
-        self._sources = [w for w, _ in specs]
-        self.table = torch.tensor(rows, dtype=torch.int64).to(dev)
-        self.count, self.chunks = len(rows), chunk
-        self.nbytes = sum(p.numel() for p in self.planes) + 4 * sum(w.numel() for w in self._sources)
+        super().__init__("HPlanes", "16-bit pack: fp32 master weight", specs, "peclr_h_pack_bytes", 32, _HALF_IO[dtype])
 
     def pack(self):
-        with _timed("h_pack", self.nbytes, kernel="h_pack_kernel"):
-            rc = lib().peclr_h_pack(self.table.data_ptr(), self.count, self.chunks, _stream())
-        _check(rc, "peclr_h_pack")
+        _launch("h_pack", "peclr_h_pack", self.table.data_ptr(), self.count, self.chunks, _stream(), nbytes=self.nbytes, kernel="h_pack_kernel")
         return self
 
 
@@ -833,26 +802,20 @@ def gemm_h(a: torch.Tensor, planes: torch.Tensor, n: int, addend: Optional[torch
     add_rows = m if addend_s2 is None else m // 4
     if not a.is_contiguous() or (addend is not None and (tuple(addend.shape) != (add_rows, n) or addend.dtype != a.dtype or not addend.is_contiguous())):
         raise PeclrHipError(f"gemm_h: contiguous {a.dtype} A {tuple(a.shape)} / addend expected")
-    if addend_s2 is not None and (addend is None or stat_shift is not None or addend_mask is not None):
-        raise PeclrHipError("gemm_h: addend_s2 needs the compact addend (and has no statistics output / mask)")
-    if addend_mask is not None and (addend is None or stat_shift is not None or n % 32 or addend_mask.dtype != torch.int32
-                                    or addend_mask.numel() != m * (n // 32) or not addend_mask.is_contiguous()):
-        raise PeclrHipError("gemm_h: addend_mask is the int32 [M, n / 32] bit mask of a dense addend (no statistics output)")
+    _check_addend_modes("gemm_h", m, n, addend, stat_shift, addend_s2, addend_mask)
     out = torch.empty((m, n), device=a.device, dtype=a.dtype)
-    if stat_shift is not None or bn_bwd is not None:
-        tile_rows = tile_rows or lib().peclr_conv_h_tile_rows(m, n)
-    partial, ns, fuse = _epilogue("gemm_h", m, n, tile_rows, stat_shift, bn_bwd, a.device, dtype=a.dtype)
+    tile_rows, partial, ns, fuse = _epilogue("gemm_h", m, n, tile_rows, stat_shift, bn_bwd, a.device, dtype=a.dtype,
+                                             pick_rows=lambda: lib().peclr_conv_h_tile_rows(m, n))
     add_elems = 0 if addend is None else addend.numel()
     mask_bytes = 0 if addend_mask is None else 4 * addend_mask.numel()
-    with _timed(tag, 2 * (m * k + m * n + add_elems + (m * n if fuse is not None else 0) + k * n) + mask_bytes, 2 * m * n * k,
-                kernel="conv_h_kernel"):
-        rc = lib().peclr_gemm_h(io, m, n, k, a.data_ptr(), k, _ptr(planes, torch.uint8), out.data_ptr(), n,
-                                addend.data_ptr() if addend is not None else None, n,
-                                int(addend_s2[0]) if addend_s2 is not None else 0, int(addend_s2[1]) if addend_s2 is not None else 0,
-                                _ptr(addend_mask, torch.int32), tile_rows, _ptr(stat_shift),
-                                partial.data_ptr() if stat_shift is not None else None, _byref(fuse), _stream())
-    _check(rc, "peclr_gemm_h")
-    return out if partial is None else (out, partial, ns)
+    _launch(tag, "peclr_gemm_h", io, m, n, k, a.data_ptr(), k, _ptr(planes, torch.uint8), out.data_ptr(), n,
+            addend.data_ptr() if addend is not None else None, n,
+            int(addend_s2[0]) if addend_s2 is not None else 0, int(addend_s2[1]) if addend_s2 is not None else 0,
+            _ptr(addend_mask, torch.int32), tile_rows, _ptr(stat_shift),
+            partial.data_ptr() if stat_shift is not None else None, _byref(fuse), _stream(),
+            nbytes=2 * (m * k + m * n + add_elems + (m * n if fuse is not None else 0) + k * n) + mask_bytes, flops=2 * m * n * k,
+            kernel="conv_h_kernel")
+    return _with_partial(out, partial, ns)
 
 
 def conv_h(x: torch.Tensor, planes: torch.Tensor, cout: int, taps: int = 9, stride: int = 1, flip: bool = False,
@@ -874,14 +837,13 @@ def conv_h(x: torch.Tensor, planes: torch.Tensor, cout: int, taps: int = 9, stri
         ns = lib().peclr_conv_h_row_blocks(nb, h, w, cout, taps, stride, tile_rows)     # (tile_rows 0: the library's choice)
         if ns <= 0:
             raise PeclrHipError(f"conv_h: no launch for tile_rows = {tile_rows} at {h} x {w}, taps {taps}, stride {stride}")
-    partial, ns, fuse = _epilogue("conv_h", m, cout, tile_rows, stat_shift, bn_bwd, x.device, dtype=x.dtype, row_blocks=ns)
-    with _timed(tag, 2 * (nb * h * w * cin + m * cout * (2 if fuse is not None else 1) + taps * cin * cout), 2 * m * taps * cin * cout,
-                kernel="conv_h_kernel (3x3)" if taps == 9 else "conv_h_kernel (stride 2)"):
-        rc = lib().peclr_conv_h(io, nb, h, w, cin, cout, taps, stride, xp, _ptr(planes, torch.uint8), y.data_ptr(), int(flip), tile_rows,
-                                _hzeros(x.device, x.dtype).data_ptr(), _ptr(stat_shift),
-                                partial.data_ptr() if stat_shift is not None else None, _byref(fuse), _stream())
-    _check(rc, "peclr_conv_h")
-    return y if partial is None else (y, partial, ns)
+    tile_rows, partial, ns, fuse = _epilogue("conv_h", m, cout, tile_rows, stat_shift, bn_bwd, x.device, dtype=x.dtype, row_blocks=ns)
+    _launch(tag, "peclr_conv_h", io, nb, h, w, cin, cout, taps, stride, xp, _ptr(planes, torch.uint8), y.data_ptr(), int(flip), tile_rows,
+            _hzeros(x.device, x.dtype).data_ptr(), _ptr(stat_shift),
+            partial.data_ptr() if stat_shift is not None else None, _byref(fuse), _stream(),
+            nbytes=2 * (nb * h * w * cin + m * cout * (2 if fuse is not None else 1) + taps * cin * cout), flops=2 * m * taps * cin * cout,
+            kernel="conv_h_kernel (3x3)" if taps == 9 else "conv_h_kernel (stride 2)")
+    return _with_partial(y, partial, ns)
 
 
 def wgrad_h_ok(gy: torch.Tensor, x: torch.Tensor, taps: int, stride: int) -> bool:
@@ -906,26 +868,24 @@ def wgrad_h(gy: torch.Tensor, x: torch.Tensor, taps: int = 1, stride: int = 1, t
     nb, cout, ho, wo = gy.shape
     cin = x.shape[1]
     gp, xp = _nhwc_ptr(gy, "wgrad_h gy", gy.dtype), _nhwc_ptr(x, "wgrad_h x", gy.dtype)
+    k = nb * ho * wo
     if taps == 9:
         ns = lib().peclr_wgrad3_h_slabs(cout, cin, nb, ho, wo)
         if ns < 1:
             raise PeclrHipError(f"wgrad_h: unsupported 3x3 shape M={cout} N={cin} {nb} x {ho} x {wo}")
         slabs = torch.empty((ns, cout, 9 * cin), device=gy.device, dtype=torch.float32)
-        with _timed("conv3x3_wgrad" if tag == "conv1x1_wgrad" else tag, 2 * nb * ho * wo * (cout + cin) + 4 * ns * cout * 9 * cin,
-                    18 * cout * cin * nb * ho * wo, kernel="wgrad3_h_kernel"):
-            rc = lib().peclr_wgrad3_h(io, cout, cin, nb, ho, wo, gp, xp, slabs.data_ptr(), ns, _hzeros(gy.device, gy.dtype).data_ptr(), _stream())
-        _check(rc, "peclr_wgrad3_h")
-        return slabs[0] if ns == 1 else slab_reduce(slabs, tag="wgrad_slab_reduce")
-    k = nb * ho * wo
-    ns = lib().peclr_wgrad_h_slabs(cout, cin, k)
-    if ns < 1:
-        raise PeclrHipError(f"wgrad_h: unsupported shape M={cout} N={cin} K={k}")
-    slabs = torch.empty((ns, cout, cin), device=gy.device, dtype=torch.float32)
-    with _timed(tag, 2 * k * (cout + cin) + 4 * ns * cout * cin, 2 * cout * cin * k, kernel="wgrad_h_kernel"):
-        rc = lib().peclr_wgrad_h(io, cout, cin, k, gp, cout, xp, cin, slabs.data_ptr(), ns, stride, ho, wo,
-                                 _hzeros(gy.device, gy.dtype).data_ptr(), _stream())
-    _check(rc, "peclr_wgrad_h")
-    return slabs[0] if ns == 1 else slab_reduce(slabs, tag="wgrad_slab_reduce")
+        _launch("conv3x3_wgrad" if tag == "conv1x1_wgrad" else tag, "peclr_wgrad3_h",
+                io, cout, cin, nb, ho, wo, gp, xp, slabs.data_ptr(), ns, _hzeros(gy.device, gy.dtype).data_ptr(), _stream(),
+                nbytes=2 * k * (cout + cin) + 4 * ns * cout * 9 * cin, flops=18 * cout * cin * k, kernel="wgrad3_h_kernel")
+    else:
+        ns = lib().peclr_wgrad_h_slabs(cout, cin, k)
+        if ns < 1:
+            raise PeclrHipError(f"wgrad_h: unsupported shape M={cout} N={cin} K={k}")
+        slabs = torch.empty((ns, cout, cin), device=gy.device, dtype=torch.float32)
+        _launch(tag, "peclr_wgrad_h", io, cout, cin, k, gp, cout, xp, cin, slabs.data_ptr(), ns, stride, ho, wo,
+                _hzeros(gy.device, gy.dtype).data_ptr(), _stream(),
+                nbytes=2 * k * (cout + cin) + 4 * ns * cout * cin, flops=2 * cout * cin * k, kernel="wgrad_h_kernel")
+    return _sum_slabs(slabs, "wgrad_slab_reduce")
 
 
 def conv3x3_s2_dgrad_h(gy: torch.Tensor, planes: torch.Tensor, cin: int, tag: str = "conv3x3_s2_dgrad", tile_rows: int = 0, bn_bwd=None):
@@ -937,19 +897,15 @@ def conv3x3_s2_dgrad_h(gy: torch.Tensor, planes: torch.Tensor, cin: int, tag: st
     _h_planes_ok(planes, cin, 9 * cout, "conv3x3_s2_dgrad_h")
     dx = torch.empty((nb, cin, 2 * ho, 2 * wo), device=gy.device, dtype=gy.dtype, memory_format=torch.channels_last)
     mc = nb * ho * wo
-    if bn_bwd is not None:
-        tile_rows = tile_rows or lib().peclr_conv_h_tile_rows(mc, cin)
-    partial, ns, fuse = _epilogue("conv3x3_s2_dgrad_h", 4 * mc, cin, tile_rows, None, bn_bwd, gy.device, groups=4, dtype=gy.dtype)
-    with _timed(tag, 2 * (mc * cout + 4 * mc * cin * (2 if fuse is not None else 1) + 9 * cin * cout), 18 * mc * cin * cout,
-                kernel="conv_h_kernel (3x3)"):
-        rc = lib().peclr_conv3x3_s2_dgrad_h(io, nb, ho, wo, cout, cin, gp, _ptr(planes, torch.uint8), dx.data_ptr(), tile_rows,
-                                            _hzeros(gy.device, gy.dtype).data_ptr(), _byref(fuse), _stream())
-    _check(rc, "peclr_conv3x3_s2_dgrad_h")
-    return dx if partial is None else (dx, partial, ns)
+    tile_rows, partial, ns, fuse = _epilogue("conv3x3_s2_dgrad_h", 4 * mc, cin, tile_rows, None, bn_bwd, gy.device, groups=4, dtype=gy.dtype,
+                                             pick_rows=lambda: lib().peclr_conv_h_tile_rows(mc, cin))
+    _launch(tag, "peclr_conv3x3_s2_dgrad_h", io, nb, ho, wo, cout, cin, gp, _ptr(planes, torch.uint8), dx.data_ptr(), tile_rows,
+            _hzeros(gy.device, gy.dtype).data_ptr(), _byref(fuse), _stream(),
+            nbytes=2 * (mc * cout + 4 * mc * cin * (2 if fuse is not None else 1) + 9 * cin * cout), flops=18 * mc * cin * cout,
+            kernel="conv_h_kernel (3x3)")
+    return _with_partial(dx, partial, ns)
 
 
-# ------------------------------------------------------------------ backbone glue: BN2d (+add) (+ReLU), NHWC
-DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
 # ------------------------------------------------------------------ stem (csrc/stem.hip)
 STEM_FMT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}      # output / arithmetic of peclr_stem_conv7x7_s2
 
@@ -967,9 +923,8 @@ class StemPlanes:
 
     def pack(self):
         w = self.weight
-        with _timed("stem_pack", 4 * w.numel() + self.planes.numel(), kernel="stem_pack_kernel"):
-            rc = lib().peclr_stem_pack(w.data_ptr(), *w.stride(), self.planes.data_ptr(), self.fmt, _stream())
-        _check(rc, "peclr_stem_pack")
+        _launch("stem_pack", "peclr_stem_pack", w.data_ptr(), *w.stride(), self.planes.data_ptr(), self.fmt, _stream(),
+                nbytes=4 * w.numel() + self.planes.numel(), kernel="stem_pack_kernel")
         return self
 
 
@@ -988,16 +943,12 @@ def stem_conv(x: torch.Tensor, planes: "StemPlanes", stat_shift: Optional[torch.
     out_dtype = {v: k for k, v in STEM_FMT.items()}[planes.fmt]
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     y = torch.empty((n, 64, ho, wo), device=x.device, dtype=out_dtype, memory_format=torch.channels_last)
-    partial, ns, _ = _epilogue("stem_conv", n * ho * wo, 64, 0, stat_shift, None, x.device, row_blocks=ns)     # (one block per workgroup)
-    e = y.element_size()
-    k_mfma = 14 * 16                                        # the contraction the matrix cores run (147 padded to 224)
-    with _timed(tag, 4 * x.numel() + e * y.numel() + planes.planes.numel(), 2 * n * ho * wo * 64 * 147,
-                kernel="stem_fwd_kernel"):
-        rc = lib().peclr_stem_conv7x7_s2(x.data_ptr(), n, h, w, planes.planes.data_ptr(), planes.fmt, y.data_ptr(), _ptr(stat_shift),
-                                         partial.data_ptr() if partial is not None else None, _stream())
-    _check(rc, "peclr_stem_conv7x7_s2")
-    del k_mfma
-    return y if partial is None else (y, partial, ns)
+    _, partial, ns, _ = _epilogue("stem_conv", n * ho * wo, 64, 0, stat_shift, None, x.device, row_blocks=ns)     # (one block per workgroup)
+    _launch(tag, "peclr_stem_conv7x7_s2", x.data_ptr(), n, h, w, planes.planes.data_ptr(), planes.fmt, y.data_ptr(), _ptr(stat_shift),
+            partial.data_ptr() if partial is not None else None, _stream(),
+            nbytes=4 * x.numel() + y.element_size() * y.numel() + planes.planes.numel(), flops=2 * n * ho * wo * 64 * 147,
+            kernel="stem_fwd_kernel")
+    return _with_partial(y, partial, ns)
 
 
 def stem_wgrad(gy: torch.Tensor, x: torch.Tensor, tag: str = "stem_wgrad") -> torch.Tensor:
@@ -1016,13 +967,13 @@ def stem_wgrad(gy: torch.Tensor, x: torch.Tensor, tag: str = "stem_wgrad") -> to
     if ns < 1:
         raise PeclrHipError(f"stem_wgrad: unsupported image size {h} x {w}")
     slabs = torch.empty((ns, 64, 224), device=x.device, dtype=torch.float32)
-    with _timed(tag, 4 * x.numel() + gy.element_size() * gy.numel() + 4 * slabs.numel(), 2 * gy.numel() * 147, kernel="stem_wgrad_kernel"):
-        rc = lib().peclr_stem_wgrad(x.data_ptr(), gy.data_ptr(), n, h, w, fmt, slabs.data_ptr(), ns, _stream())
-    _check(rc, "peclr_stem_wgrad")
-    dw = slabs[0] if ns == 1 else slab_reduce(slabs, tag="wgrad_slab_reduce")
+    _launch(tag, "peclr_stem_wgrad", x.data_ptr(), gy.data_ptr(), n, h, w, fmt, slabs.data_ptr(), ns, _stream(),
+            nbytes=4 * x.numel() + gy.element_size() * gy.numel() + 4 * slabs.numel(), flops=2 * gy.numel() * 147, kernel="stem_wgrad_kernel")
+    dw = _sum_slabs(slabs, "wgrad_slab_reduce")
     return dw.view(64, 7, 8, 4)[:, :, :7, :3].permute(0, 3, 1, 2)          # [n][kh][kw][c] -> [n][c][kh][kw]
 
 
+# ------------------------------------------------------------------ backbone glue: BN2d (+add) (+ReLU), NHWC
 _IO = {torch.float32: (DTYPE_F32, 4), torch.bfloat16: (DTYPE_BF16, 2), torch.float16: (DTYPE_F16, 2)}
 
 
@@ -1049,9 +1000,7 @@ def _sync_totals(partial, ns, c, rows, group):
     import torch.distributed as td
 
     local = torch.empty(2 * c + 1, device=partial.device, dtype=torch.float64)
-    with _timed("bn2d_combine", 8 * ns * c):
-        rc = lib().peclr_bn2d_combine_f64(partial.data_ptr(), ns, c, local.data_ptr(), _stream())
-    _check(rc, "peclr_bn2d_combine_f64")
+    _launch("bn2d_combine", "peclr_bn2d_combine_f64", partial.data_ptr(), ns, c, local.data_ptr(), _stream(), nbytes=8 * ns * c)
     local[2 * c] = float(rows)
     total = local.clone()
     td.all_reduce(total, op=td.ReduceOp.SUM, group=group)
@@ -1087,24 +1036,16 @@ def _bn2d_scale_shift(x, gamma, beta, running_mean, running_var, nbt, training, 
         # synchronised: every rank must subtract the SAME shift before summing -> the (replicated) running mean, or the
         # copy of it the caller kept (re-run of a checkpointed block: the running statistics have moved since)
         shift = (sync_shift if sync_shift is not None else running_mean.detach().clone()) if sync else None
-        with _timed("bn2d_stats", e * r * c):
-            rc = lib().peclr_bn2d_stats(xp, io, r, c, _ptr(shift), part_ptr, ns, _stream())
-        _check(rc, "peclr_bn2d_stats")
+        _launch("bn2d_stats", "peclr_bn2d_stats", xp, io, r, c, _ptr(shift), part_ptr, ns, _stream(), nbytes=e * r * c)
     if training and sync:
         _, total = _sync_totals(partial, ns, c, r, sync_group)
-        with _timed("bn2d_finalize", 16 * c):
-            rc = lib().peclr_bn2d_finalize_totals_f32(total.data_ptr(), shift.data_ptr(), c, eps, momentum,
-                                                      _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var),
-                                                      _ptr(nbt, torch.int64, "num_batches_tracked"),
-                                                      save[0].data_ptr(), save[1].data_ptr(), ss.data_ptr(), _stream())
-        _check(rc, "peclr_bn2d_finalize_totals_f32")
+        _launch("bn2d_finalize", "peclr_bn2d_finalize_totals_f32", total.data_ptr(), shift.data_ptr(), c, eps, momentum,
+                _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), _ptr(nbt, torch.int64, "num_batches_tracked"),
+                save[0].data_ptr(), save[1].data_ptr(), ss.data_ptr(), _stream(), nbytes=16 * c)
     else:
-        with _timed("bn2d_finalize", 8 * ns * c):
-            rc = lib().peclr_bn2d_finalize_f32(part_ptr, ns, r, c, int(training), eps, momentum, _ptr(gamma), _ptr(beta),
-                                               _ptr(running_mean), _ptr(running_var),
-                                               _ptr(nbt, torch.int64, "num_batches_tracked") if training else None,
-                                               save[0].data_ptr(), save[1].data_ptr(), ss.data_ptr(), _stream())
-        _check(rc, "peclr_bn2d_finalize_f32")
+        _launch("bn2d_finalize", "peclr_bn2d_finalize_f32", part_ptr, ns, r, c, int(training), eps, momentum, _ptr(gamma), _ptr(beta),
+                _ptr(running_mean), _ptr(running_var), _ptr(nbt, torch.int64, "num_batches_tracked") if training else None,
+                save[0].data_ptr(), save[1].data_ptr(), ss.data_ptr(), _stream(), nbytes=8 * ns * c)
     return save, ss
 
 
@@ -1141,10 +1082,8 @@ def bn2d_apply(x, ss, relu: bool = True, absmax=None):
     r = n * h * w
     io, e = _IO[x.dtype]
     y = torch.empty_like(x, memory_format=torch.channels_last)
-    with _timed("bn2d_apply", 2 * e * r * c):
-        rc = lib().peclr_bn2d_apply(_nhwc_ptr(x, "bn2d x"), None, io, r, c, ss.data_ptr(), int(relu), y.data_ptr(), None,
-                                    _absmax_ptr(absmax, x), _stream())
-    _check(rc, "peclr_bn2d_apply")
+    _launch("bn2d_apply", "peclr_bn2d_apply", _nhwc_ptr(x, "bn2d x"), None, io, r, c, ss.data_ptr(), int(relu), y.data_ptr(), None,
+            _absmax_ptr(absmax, x), _stream(), nbytes=2 * e * r * c)
     return y
 
 
@@ -1168,22 +1107,33 @@ def bn2d_fwd(x, residual, gamma, beta, running_mean, running_var, nbt, training,
         return None, save, ss, None
     y = torch.empty_like(x, memory_format=torch.channels_last)
     mask = torch.empty((r, c // 32), device=dev, dtype=torch.int32) if (want_mask and relu and c % 32 == 0) else None
+    mask_bytes = r * c // 8 if mask is not None else 0
+    tail = (io, r, c, ss.data_ptr(), int(relu), y.data_ptr(), mask.data_ptr() if mask is not None else None)
     if residual_bn is not None:
         xs, ss_s = residual_bn
         if residual is not None or tuple(xs.shape) != tuple(x.shape) or ss_s.numel() != 2 * c or ss_s.dtype != torch.float32:
             raise PeclrHipError("bn2d_fwd: residual_bn = (input of the shortcut's BatchNorm, its fp32 [2, C] table), no residual tensor")
-        with _timed("bn2d_apply", 3 * e * r * c + (r * c // 8 if mask is not None else 0)):
-            rc = lib().peclr_bn2d_apply_res_bn(xp, _nhwc_ptr(xs, "bn2d shortcut x", x.dtype), ss_s.data_ptr(), io, r, c, ss.data_ptr(),
-                                               int(relu), y.data_ptr(), mask.data_ptr() if mask is not None else None,
-                                               _absmax_ptr(absmax, x), _stream())
-        _check(rc, "peclr_bn2d_apply_res_bn")
-        return y, save, ss, mask
-    with _timed("bn2d_apply", (3 if residual is not None else 2) * e * r * c + (r * c // 8 if mask is not None else 0)):
-        rc = lib().peclr_bn2d_apply(xp, _nhwc_ptr(residual, "bn2d residual", x.dtype) if residual is not None else None,
-                                    io, r, c, ss.data_ptr(), int(relu), y.data_ptr(),
-                                    mask.data_ptr() if mask is not None else None, _absmax_ptr(absmax, x), _stream())
-    _check(rc, "peclr_bn2d_apply")
+        _launch("bn2d_apply", "peclr_bn2d_apply_res_bn", xp, _nhwc_ptr(xs, "bn2d shortcut x", x.dtype), ss_s.data_ptr(), *tail,
+                _absmax_ptr(absmax, x), _stream(), nbytes=3 * e * r * c + mask_bytes)
+    else:
+        _launch("bn2d_apply", "peclr_bn2d_apply", xp, _nhwc_ptr(residual, "bn2d residual", x.dtype) if residual is not None else None, *tail,
+                _absmax_ptr(absmax, x), _stream(), nbytes=(3 if residual is not None else 2) * e * r * c + mask_bytes)
     return y, save, ss, mask
+
+
+def _bn2d_bwd_finalize(partial, ns, r, c, ss, training, sync_group):
+    """The middle launch of every BatchNorm2d backward: the reduction's partials [2 n_split, C] -> (dparams [dgamma, dbeta], coef
+    [2, C] for the apply pass).  Synchronised (training with a `sync_group`): dgamma / dbeta from this rank's totals, coef from
+    the group's."""
+    dparams = torch.empty((2, c), device=partial.device, dtype=torch.float32)
+    coef = torch.empty((2, c), device=partial.device, dtype=torch.float32)
+    out = (ss.data_ptr(), dparams[0].data_ptr(), dparams[1].data_ptr(), coef.data_ptr(), _stream())
+    if training and sync_group is not None:
+        local, total = _sync_totals(partial, ns, c, r, sync_group)
+        _launch("bn2d_bwd_finalize", "peclr_bn2d_bwd_finalize_totals_f32", local.data_ptr(), total.data_ptr(), c, 1, *out, nbytes=32 * c)
+    else:
+        _launch("bn2d_bwd_finalize", "peclr_bn2d_bwd_finalize_f32", partial.data_ptr(), ns, r, c, int(training), *out, nbytes=8 * ns * c)
+    return dparams, coef
 
 
 def bn2d_bwd(dy, x, y, mask, save, ss, training, relu, want_dres, sync_group=None, pre=None, absmax=None):
@@ -1194,14 +1144,13 @@ def bn2d_bwd(dy, x, y, mask, save, ss, training, relu, want_dres, sync_group=Non
     r = n * h * w
     dev = x.device
     io, e = _IO[x.dtype]
-    dparams = torch.empty((2, c), device=dev, dtype=torch.float32)  # dgamma, dbeta
-    coef = torch.empty((2, c), device=dev, dtype=torch.float32)
     dx = torch.empty_like(x, memory_format=torch.channels_last)
     dres = torch.empty_like(x, memory_format=torch.channels_last) if want_dres else None
     dyp, xp = _nhwc_ptr(dy, "bn2d dy", x.dtype), _nhwc_ptr(x, "bn2d x")
     yp = _nhwc_ptr(y, "bn2d y", x.dtype) if (y is not None and mask is None) else None
     mp = _ptr(mask, torch.int32, "relu mask")
     extra = (r * c // 8) if mask is not None else (e * r * c if yp is not None else 0)
+    head = (dyp, xp, yp, mp, io, r, c, int(relu), save[0].data_ptr(), save[1].data_ptr(), ss.data_ptr())
     if pre is not None:
         # the GEMM that produced dy already reduced it against this layer's x in its epilogue (peclr_bn_bwd_fuse)
         partial, ns = pre
@@ -1210,28 +1159,10 @@ def bn2d_bwd(dy, x, y, mask, save, ss, training, relu, want_dres, sync_group=Non
     else:
         ns = bn2d_n_split(r, c, io)
         partial = torch.empty((2 * ns, c), device=dev, dtype=torch.float32)
-        with _timed("bn2d_bwd_reduce", 2 * e * r * c + extra):
-            rc = lib().peclr_bn2d_bwd_reduce(dyp, xp, yp, mp, io, r, c, int(relu), save[0].data_ptr(), save[1].data_ptr(),
-                                             ss.data_ptr(), partial.data_ptr(), ns, _stream())
-        _check(rc, "peclr_bn2d_bwd_reduce")
-    if training and sync_group is not None:
-        local, total = _sync_totals(partial, ns, c, r, sync_group)
-        with _timed("bn2d_bwd_finalize", 32 * c):
-            rc = lib().peclr_bn2d_bwd_finalize_totals_f32(local.data_ptr(), total.data_ptr(), c, 1, ss.data_ptr(),
-                                                          dparams[0].data_ptr(), dparams[1].data_ptr(), coef.data_ptr(),
-                                                          _stream())
-        _check(rc, "peclr_bn2d_bwd_finalize_totals_f32")
-    else:
-        with _timed("bn2d_bwd_finalize", 8 * ns * c):
-            rc = lib().peclr_bn2d_bwd_finalize_f32(partial.data_ptr(), ns, r, c, int(training), ss.data_ptr(),
-                                                   dparams[0].data_ptr(), dparams[1].data_ptr(), coef.data_ptr(),
-                                                   _stream())
-        _check(rc, "peclr_bn2d_bwd_finalize_f32")
-    with _timed("bn2d_bwd_apply", (3 + (1 if want_dres else 0)) * e * r * c + extra):
-        rc = lib().peclr_bn2d_bwd_apply(dyp, xp, yp, mp, io, r, c, int(relu), save[0].data_ptr(), save[1].data_ptr(),
-                                        ss.data_ptr(), coef.data_ptr(), dx.data_ptr(),
-                                        dres.data_ptr() if dres is not None else None, _absmax_ptr(absmax, x), _stream())
-    _check(rc, "peclr_bn2d_bwd_apply")
+        _launch("bn2d_bwd_reduce", "peclr_bn2d_bwd_reduce", *head, partial.data_ptr(), ns, _stream(), nbytes=2 * e * r * c + extra)
+    dparams, coef = _bn2d_bwd_finalize(partial, ns, r, c, ss, training, sync_group)
+    _launch("bn2d_bwd_apply", "peclr_bn2d_bwd_apply", *head, coef.data_ptr(), dx.data_ptr(), dres.data_ptr() if dres is not None else None,
+            _absmax_ptr(absmax, x), _stream(), nbytes=(3 + (1 if want_dres else 0)) * e * r * c + extra)
     return dx, dparams[0], dparams[1], dres
 
 
@@ -1247,10 +1178,8 @@ def bn2d_avgpool_fwd(x, residual, gamma, beta, running_mean, running_var, nbt, t
     save, ss = _bn2d_scale_shift(x, gamma, beta, running_mean, running_var, nbt, training, eps, momentum, sync_group, sync_shift, pre)
     pooled = torch.empty((n, c), device=x.device, dtype=torch.float32)
     mask = torch.empty((r, c // 32), device=x.device, dtype=torch.int32)
-    with _timed("bn2d_apply_avgpool", 2 * e * r * c + r * c // 8 + 4 * n * c):
-        rc = lib().peclr_bn2d_apply_avgpool(_nhwc_ptr(x, "bn2d x"), _nhwc_ptr(residual, "bn2d residual", x.dtype), io, n,
-                                            h * w, c, ss.data_ptr(), pooled.data_ptr(), mask.data_ptr(), _stream())
-    _check(rc, "peclr_bn2d_apply_avgpool")
+    _launch("bn2d_apply_avgpool", "peclr_bn2d_apply_avgpool", _nhwc_ptr(x, "bn2d x"), _nhwc_ptr(residual, "bn2d residual", x.dtype), io, n,
+            h * w, c, ss.data_ptr(), pooled.data_ptr(), mask.data_ptr(), _stream(), nbytes=2 * e * r * c + r * c // 8 + 4 * n * c)
     return pooled, mask, save, ss
 
 
@@ -1260,37 +1189,17 @@ def bn2d_avgpool_bwd(d_pooled, x, mask, save, ss, training, sync_group=None, abs
     n, c, h, w = x.shape
     r = n * h * w
     io, e = _IO[x.dtype]
-    dev = x.device
     ns = bn2d_n_split(r, c, io)
-    partial = torch.empty((2 * ns, c), device=dev, dtype=torch.float32)
-    dparams = torch.empty((2, c), device=dev, dtype=torch.float32)
-    coef = torch.empty((2, c), device=dev, dtype=torch.float32)
+    partial = torch.empty((2 * ns, c), device=x.device, dtype=torch.float32)
     dx = torch.empty_like(x, memory_format=torch.channels_last)
     dres = torch.empty_like(x, memory_format=torch.channels_last)
-    dp = _ptr(d_pooled, what="d_pooled")
-    xp, mp = _nhwc_ptr(x, "bn2d x"), _ptr(mask, torch.int32, "relu mask")
-    with _timed("bn2d_bwd_reduce_avgpool", e * r * c + r * c // 8 + 4 * n * c):
-        rc = lib().peclr_bn2d_bwd_reduce_avgpool(dp, xp, mp, io, n, h * w, c, save[0].data_ptr(), save[1].data_ptr(),
-                                                 ss.data_ptr(), partial.data_ptr(), ns, _stream())
-    _check(rc, "peclr_bn2d_bwd_reduce_avgpool")
-    if training and sync_group is not None:
-        local, total = _sync_totals(partial, ns, c, r, sync_group)
-        with _timed("bn2d_bwd_finalize", 32 * c):
-            rc = lib().peclr_bn2d_bwd_finalize_totals_f32(local.data_ptr(), total.data_ptr(), c, 1, ss.data_ptr(),
-                                                          dparams[0].data_ptr(), dparams[1].data_ptr(), coef.data_ptr(),
-                                                          _stream())
-        _check(rc, "peclr_bn2d_bwd_finalize_totals_f32")
-    else:
-        with _timed("bn2d_bwd_finalize", 8 * ns * c):
-            rc = lib().peclr_bn2d_bwd_finalize_f32(partial.data_ptr(), ns, r, c, int(training), ss.data_ptr(),
-                                                   dparams[0].data_ptr(), dparams[1].data_ptr(), coef.data_ptr(),
-                                                   _stream())
-        _check(rc, "peclr_bn2d_bwd_finalize_f32")
-    with _timed("bn2d_bwd_apply_avgpool", 3 * e * r * c + r * c // 8 + 4 * n * c):
-        rc = lib().peclr_bn2d_bwd_apply_avgpool(dp, xp, mp, io, n, h * w, c, save[0].data_ptr(), save[1].data_ptr(),
-                                                ss.data_ptr(), coef.data_ptr(), dx.data_ptr(), dres.data_ptr(),
-                                                _absmax_ptr(absmax, x), _stream())
-    _check(rc, "peclr_bn2d_bwd_apply_avgpool")
+    head = (_ptr(d_pooled, what="d_pooled"), _nhwc_ptr(x, "bn2d x"), _ptr(mask, torch.int32, "relu mask"), io, n, h * w, c,
+            save[0].data_ptr(), save[1].data_ptr(), ss.data_ptr())
+    _launch("bn2d_bwd_reduce_avgpool", "peclr_bn2d_bwd_reduce_avgpool", *head, partial.data_ptr(), ns, _stream(),
+            nbytes=e * r * c + r * c // 8 + 4 * n * c)
+    dparams, coef = _bn2d_bwd_finalize(partial, ns, r, c, ss, training, sync_group)
+    _launch("bn2d_bwd_apply_avgpool", "peclr_bn2d_bwd_apply_avgpool", *head, coef.data_ptr(), dx.data_ptr(), dres.data_ptr(),
+            _absmax_ptr(absmax, x), _stream(), nbytes=3 * e * r * c + r * c // 8 + 4 * n * c)
     return dx, dparams[0], dparams[1], dres
 
 
@@ -1305,10 +1214,9 @@ def bn2d_pool_fwd(x, gamma, beta, running_mean, running_var, nbt, training, eps,
     y = torch.empty((n, c, ph, pw), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
     x_at_max = torch.empty_like(y)
     code = torch.empty((n, ph, pw, c), device=x.device, dtype=torch.uint8)
-    with _timed("bn2d_pool_apply", e * n * c * (h * w + 2 * ph * pw) + n * c * ph * pw):
-        rc = lib().peclr_bn2d_pool_apply(_nhwc_ptr(x, "bn2d x"), io, n, h, w, c, ss.data_ptr(), y.data_ptr(),
-                                         x_at_max.data_ptr(), code.data_ptr(), _absmax_ptr(absmax, x), _stream())
-    _check(rc, "peclr_bn2d_pool_apply")
+    _launch("bn2d_pool_apply", "peclr_bn2d_pool_apply", _nhwc_ptr(x, "bn2d x"), io, n, h, w, c, ss.data_ptr(), y.data_ptr(),
+            x_at_max.data_ptr(), code.data_ptr(), _absmax_ptr(absmax, x), _stream(),
+            nbytes=e * n * c * (h * w + 2 * ph * pw) + n * c * ph * pw)
     return y, x_at_max, code, save, ss
 
 
@@ -1317,77 +1225,109 @@ def bn2d_pool_bwd(dy, x, x_at_max, code, save, ss, training, sync_group=None):
     r = n * h * w
     ph, pw = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     io, e = _IO[x.dtype]
-    dev = x.device
     ns = lib().peclr_bn2d_pool_n_split(n, h, w, c, io)
     if ns < 1:
         raise PeclrHipError(f"fused stem BN+ReLU+max-pool: unsupported shape {tuple(x.shape)}")
-    partial = torch.empty((2 * ns, c), device=dev, dtype=torch.float32)
-    dparams = torch.empty((2, c), device=dev, dtype=torch.float32)
-    coef = torch.empty((2, c), device=dev, dtype=torch.float32)
+    partial = torch.empty((2 * ns, c), device=x.device, dtype=torch.float32)
     dx = torch.empty_like(x, memory_format=torch.channels_last)
     dyp, xp = _nhwc_ptr(dy, "pooled dy", x.dtype), _nhwc_ptr(x, "bn2d x")
     pooled = n * c * ph * pw
-    with _timed("bn2d_pool_bwd_reduce", 2 * e * pooled):
-        rc = lib().peclr_bn2d_pool_bwd_reduce(dyp, _nhwc_ptr(x_at_max, "x at the maximum", x.dtype), io, n, h, w, c,
-                                              save[0].data_ptr(), save[1].data_ptr(), ss.data_ptr(), partial.data_ptr(),
-                                              ns, _stream())
-    _check(rc, "peclr_bn2d_pool_bwd_reduce")
-    if training and sync_group is not None:
-        local, total = _sync_totals(partial, ns, c, r, sync_group)
-        with _timed("bn2d_bwd_finalize", 32 * c):
-            rc = lib().peclr_bn2d_bwd_finalize_totals_f32(local.data_ptr(), total.data_ptr(), c, 1, ss.data_ptr(),
-                                                          dparams[0].data_ptr(), dparams[1].data_ptr(), coef.data_ptr(),
-                                                          _stream())
-        _check(rc, "peclr_bn2d_bwd_finalize_totals_f32")
-    else:
-        with _timed("bn2d_bwd_finalize", 8 * ns * c):
-            rc = lib().peclr_bn2d_bwd_finalize_f32(partial.data_ptr(), ns, r, c, int(training), ss.data_ptr(),
-                                                   dparams[0].data_ptr(), dparams[1].data_ptr(), coef.data_ptr(),
-                                                   _stream())
-        _check(rc, "peclr_bn2d_bwd_finalize_f32")
-    with _timed("bn2d_pool_bwd_apply", (e + 1) * pooled + 2 * e * r * c):
-        rc = lib().peclr_bn2d_pool_bwd_apply(dyp, xp, code.data_ptr(), io, n, h, w, c, save[0].data_ptr(),
-                                             save[1].data_ptr(), ss.data_ptr(), coef.data_ptr(), dx.data_ptr(), _stream())
-    _check(rc, "peclr_bn2d_pool_bwd_apply")
+    _launch("bn2d_pool_bwd_reduce", "peclr_bn2d_pool_bwd_reduce", dyp, _nhwc_ptr(x_at_max, "x at the maximum", x.dtype), io, n, h, w, c,
+            save[0].data_ptr(), save[1].data_ptr(), ss.data_ptr(), partial.data_ptr(), ns, _stream(), nbytes=2 * e * pooled)
+    dparams, coef = _bn2d_bwd_finalize(partial, ns, r, c, ss, training, sync_group)
+    _launch("bn2d_pool_bwd_apply", "peclr_bn2d_pool_bwd_apply", dyp, xp, code.data_ptr(), io, n, h, w, c, save[0].data_ptr(),
+            save[1].data_ptr(), ss.data_ptr(), coef.data_ptr(), dx.data_ptr(), _stream(), nbytes=(e + 1) * pooled + 2 * e * r * c)
     return dx, dparams[0], dparams[1]
 
 
 # ------------------------------------------------------------------ two-view augmentation (pixel side)
 AUG_PARAM_DOUBLES = 16
+AUG_EXT_INTS = 8
+AUG_EXT_BLUR = 4
+AUG_EXT_PRE, AUG_EXT_POST = 1 | 2 | 4, 8 | 16  # sobel, cut-out, blur | noise, colour drop
 
 
-def augment_views(images: torch.Tensor, params: torch.Tensor, out_hw, mean, std, channels_last: bool = True):
-    """images [B,H,W,3] uint8 (HIP), params [V,B,16] float64 (HIP) -> float32 [V*B,3,out_h,out_w]
-    (channels_last storage if asked).  Two launches: rotate+crop window, then resize+colour+normalise."""
+def _aug_params(params: torch.Tensor, b: int) -> int:
+    """params [V,B,16] float64 (HIP) for a batch of b -> V."""
+    if (params.dtype != torch.float64 or params.dim() != 3 or params.shape[1] != b
+            or params.shape[2] != AUG_PARAM_DOUBLES or not params.is_cuda or not params.is_contiguous()):
+        raise PeclrHipError(f"augment: params must be a contiguous [V,{b},{AUG_PARAM_DOUBLES}] float64 HIP tensor")
+    return params.shape[0]
+
+
+def _aug_uniform_args(images: torch.Tensor, params: torch.Tensor):
+    """images [B,H,W,3] uint8 (HIP) and their params -> (b, v)."""
     if not images.is_cuda or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
         raise PeclrHipError(f"augment: images must be a [B,H,W,3] uint8 HIP tensor, got {images.dtype} "
                             f"{tuple(images.shape)} on {images.device} (peclr_amd has no CPU path)")
     if not images.is_contiguous():
         raise PeclrHipError("augment: images must be contiguous")
-    b, h, w, _ = images.shape
-    if (params.dtype != torch.float64 or params.dim() != 3 or params.shape[1] != b
-            or params.shape[2] != AUG_PARAM_DOUBLES or not params.is_cuda or not params.is_contiguous()):
-        raise PeclrHipError(f"augment: params must be a contiguous [V,{b},{AUG_PARAM_DOUBLES}] float64 HIP tensor")
-    v = params.shape[0]
+    return images.shape[0], _aug_params(params, images.shape[0])
+
+
+class _AugExt:
+    """The checked arguments of the other five augmentations: ext [V,B,8] int32 records, coefs int32 Q8 blur taps, noise_table
+    int32 storage of n_table uint32 thresholds, the Philox key and call index, and `ops`, the OR of all records' bits."""
+
+    def __init__(self, v, b, ext, coefs, noise_table, n_table, noise_seed, call, ops):
+        if ext.dtype != torch.int32 or tuple(ext.shape) != (v, b, AUG_EXT_INTS) or not ext.is_cuda or not ext.is_contiguous():
+            raise PeclrHipError(f"augment: ext must be a contiguous [{v},{b},{AUG_EXT_INTS}] int32 HIP tensor")
+        for name, t in (("coefs", coefs), ("noise_table", noise_table)):
+            if t.dtype != torch.int32 or t.dim() != 1 or not t.is_cuda or not t.is_contiguous():
+                raise PeclrHipError(f"augment: {name} must be a contiguous 1-D int32 HIP tensor")
+        if not 0 <= n_table <= noise_table.numel():
+            raise PeclrHipError(f"augment: n_table {n_table} exceeds the table's {noise_table.numel()} entries")
+        self.ext, self.coefs, self.ops = ext.data_ptr(), coefs.data_ptr(), ops
+        self.noise = (ext.data_ptr(), noise_table.data_ptr(), n_table, noise_seed & (2 ** 64 - 1), call & 0xFFFFFFFF)
+
+
+def _aug_out(v, b, out_hw, mean, std, channels_last, device):
+    """The float32 [V*B,3,oh,ow] output and the tail of both resize entry points' arguments that writes it."""
     oh, ow = out_hw
-    crops = torch.empty((v, b, h, w, 3), device=images.device, dtype=torch.uint8)
-    out = torch.empty((v * b, 3, oh, ow), device=images.device, dtype=torch.float32,
+    out = torch.empty((v * b, 3, oh, ow), device=device, dtype=torch.float32,
                       memory_format=torch.channels_last if channels_last else torch.contiguous_format)
     mean_arr, std_arr = (c_float * 3)(*mean), (c_float * 3)(*std)
-    with _timed("augment_warp_crop", 2 * v * b * h * w * 3):
-        rc = lib().peclr_augment_warp_crop_u8(images.data_ptr(), b, h, w, v, params.data_ptr(), crops.data_ptr(), _stream())
-    _check(rc, "peclr_augment_warp_crop_u8")
-    with _timed("augment_resize_color_norm", v * b * (h * w * 3 + oh * ow * 12)):
-        rc = lib().peclr_augment_resize_color_norm(crops.data_ptr(), b, h, w, v, params.data_ptr(), oh, ow,
-                                                   ctypes.cast(mean_arr, c_void_p), ctypes.cast(std_arr, c_void_p),
-                                                   int(channels_last), out.data_ptr(), _stream())
-    _check(rc, "peclr_augment_resize_color_norm")
+    return out, (oh, ow, ctypes.cast(mean_arr, c_void_p), ctypes.cast(std_arr, c_void_p), int(channels_last), out.data_ptr())
+
+
+def _augment_uniform(images, params, b, v, aug, ksize, out_hw, mean, std, channels_last):
+    """Both stages for same-size images -> (out, srcs or None, crops).  aug: `_AugExt` or None.  Stage 0 (sobel / cut-out /
+    blur), when `aug.ops` names it, writes per-view sources and the warp then runs once per view on them."""
+    _, h, w, _ = images.shape
+    dev, stream = images.device, _stream()
+    crops = torch.empty((v, b, h, w, 3), device=dev, dtype=torch.uint8)
+    out, out_args = _aug_out(v, b, out_hw, mean, std, channels_last, dev)
+    ops = aug.ops if aug is not None else 0
+    srcs = None
+    if ops & AUG_EXT_PRE:
+        kx, ky = ksize
+        srcs = torch.empty((v, b, h, w, 3), device=dev, dtype=torch.uint8)
+        tmp = torch.empty((v, b, h, w, 3), device=dev, dtype=torch.int16) if ops & AUG_EXT_BLUR else None
+        blur_bytes = (kx + ky) * 3 if tmp is not None else 0
+        _launch("augment_pre", "peclr_augment_pre_u8", images.data_ptr(), b, h, w, v, aug.ext, aug.coefs, kx, ky,
+                srcs.data_ptr(), None if tmp is None else tmp.data_ptr(), stream,
+                nbytes=v * b * h * w * (3 + 3 + 4 * (3 if tmp is not None else 0)), flops=v * b * h * w * blur_bytes)
+        for i in range(v):
+            _launch("augment_warp_crop", "peclr_augment_warp_crop_u8", srcs[i].data_ptr(), b, h, w, 1, params[i].data_ptr(),
+                    crops[i].data_ptr(), stream, nbytes=2 * b * h * w * 3)
+    else:
+        _launch("augment_warp_crop", "peclr_augment_warp_crop_u8", images.data_ptr(), b, h, w, v, params.data_ptr(), crops.data_ptr(),
+                stream, nbytes=2 * v * b * h * w * 3)
+    head = (crops.data_ptr(), b, h, w, v, params.data_ptr())
+    nbytes = v * b * (h * w * 3 + out_hw[0] * out_hw[1] * 12)
+    if ops & AUG_EXT_POST:
+        _launch("augment_resize_color_norm_ext", "peclr_augment_resize_color_norm_ext", *head, *aug.noise, *out_args, stream, nbytes=nbytes)
+    else:
+        _launch("augment_resize_color_norm", "peclr_augment_resize_color_norm", *head, *out_args, stream, nbytes=nbytes)
+    return out, srcs, crops
+
+
+def augment_views(images: torch.Tensor, params: torch.Tensor, out_hw, mean, std, channels_last: bool = True):
+    """images [B,H,W,3] uint8 (HIP), params [V,B,16] float64 (HIP) -> float32 [V*B,3,out_h,out_w]
+    (channels_last storage if asked).  Two launches: rotate+crop window, then resize+colour+normalise."""
+    b, v = _aug_uniform_args(images, params)
+    out, _, crops = _augment_uniform(images, params, b, v, None, None, out_hw, mean, std, channels_last)
     return out, crops
-
-
-AUG_EXT_INTS = 8
-AUG_EXT_BLUR = 4
-AUG_EXT_PRE, AUG_EXT_POST = 1 | 2 | 4, 8 | 16  # sobel, cut-out, blur | noise, colour drop
 
 
 def augment_views_ext(images: torch.Tensor, params: torch.Tensor, ext: torch.Tensor, coefs: torch.Tensor, ksize,
@@ -1399,62 +1339,9 @@ def augment_views_ext(images: torch.Tensor, params: torch.Tensor, ext: torch.Ten
     all records' bits (the stages it names are the only ones launched).  Stage 0 (sobel / cut-out / blur) writes
     per-view sources, the warp then runs once per view on them.
     Returns (out, srcs or None, crops)."""
-    if not images.is_cuda or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
-        raise PeclrHipError(f"augment: images must be a [B,H,W,3] uint8 HIP tensor, got {images.dtype} "
-                            f"{tuple(images.shape)} on {images.device} (peclr_amd has no CPU path)")
-    if not images.is_contiguous():
-        raise PeclrHipError("augment: images must be contiguous")
-    b, h, w, _ = images.shape
-    if (params.dtype != torch.float64 or params.dim() != 3 or params.shape[1] != b
-            or params.shape[2] != AUG_PARAM_DOUBLES or not params.is_cuda or not params.is_contiguous()):
-        raise PeclrHipError(f"augment: params must be a contiguous [V,{b},{AUG_PARAM_DOUBLES}] float64 HIP tensor")
-    v = params.shape[0]
-    if ext.dtype != torch.int32 or tuple(ext.shape) != (v, b, AUG_EXT_INTS) or not ext.is_cuda or not ext.is_contiguous():
-        raise PeclrHipError(f"augment: ext must be a contiguous [{v},{b},{AUG_EXT_INTS}] int32 HIP tensor")
-    for name, t in (("coefs", coefs), ("noise_table", noise_table)):
-        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_cuda or not t.is_contiguous():
-            raise PeclrHipError(f"augment: {name} must be a contiguous 1-D int32 HIP tensor")
-    if not 0 <= n_table <= noise_table.numel():
-        raise PeclrHipError(f"augment: n_table {n_table} exceeds the table's {noise_table.numel()} entries")
-    oh, ow = out_hw
-    kx, ky = ksize
-    dev, stream = images.device, _stream()
-    crops = torch.empty((v, b, h, w, 3), device=dev, dtype=torch.uint8)
-    out = torch.empty((v * b, 3, oh, ow), device=dev, dtype=torch.float32,
-                      memory_format=torch.channels_last if channels_last else torch.contiguous_format)
-    mean_arr, std_arr = (c_float * 3)(*mean), (c_float * 3)(*std)
-    srcs = None
-    if ops & AUG_EXT_PRE:
-        srcs = torch.empty((v, b, h, w, 3), device=dev, dtype=torch.uint8)
-        tmp = torch.empty((v, b, h, w, 3), device=dev, dtype=torch.int16) if ops & AUG_EXT_BLUR else None
-        blur_bytes = (kx + ky) * 3 if tmp is not None else 0
-        with _timed("augment_pre", v * b * h * w * (3 + 3 + 4 * (3 if tmp is not None else 0)), v * b * h * w * blur_bytes):
-            rc = lib().peclr_augment_pre_u8(images.data_ptr(), b, h, w, v, ext.data_ptr(), coefs.data_ptr(), kx, ky,
-                                            srcs.data_ptr(), None if tmp is None else tmp.data_ptr(), stream)
-        _check(rc, "peclr_augment_pre_u8")
-        for i in range(v):
-            with _timed("augment_warp_crop", 2 * b * h * w * 3):
-                rc = lib().peclr_augment_warp_crop_u8(srcs[i].data_ptr(), b, h, w, 1, params[i].data_ptr(),
-                                                      crops[i].data_ptr(), stream)
-            _check(rc, "peclr_augment_warp_crop_u8")
-    else:
-        with _timed("augment_warp_crop", 2 * v * b * h * w * 3):
-            rc = lib().peclr_augment_warp_crop_u8(images.data_ptr(), b, h, w, v, params.data_ptr(), crops.data_ptr(), stream)
-        _check(rc, "peclr_augment_warp_crop_u8")
-    mp, sp = ctypes.cast(mean_arr, c_void_p), ctypes.cast(std_arr, c_void_p)
-    if ops & AUG_EXT_POST:
-        with _timed("augment_resize_color_norm_ext", v * b * (h * w * 3 + oh * ow * 12)):
-            rc = lib().peclr_augment_resize_color_norm_ext(crops.data_ptr(), b, h, w, v, params.data_ptr(), ext.data_ptr(),
-                                                           noise_table.data_ptr(), n_table, noise_seed & (2 ** 64 - 1),
-                                                           call & 0xFFFFFFFF, oh, ow, mp, sp, int(channels_last),
-                                                           out.data_ptr(), stream)
-        _check(rc, "peclr_augment_resize_color_norm_ext")
-    else:
-        with _timed("augment_resize_color_norm", v * b * (h * w * 3 + oh * ow * 12)):
-            rc = lib().peclr_augment_resize_color_norm(crops.data_ptr(), b, h, w, v, params.data_ptr(), oh, ow, mp, sp,
-                                                       int(channels_last), out.data_ptr(), stream)
-        _check(rc, "peclr_augment_resize_color_norm")
-    return out, srcs, crops
+    b, v = _aug_uniform_args(images, params)
+    aug = _AugExt(v, b, ext, coefs, noise_table, n_table, noise_seed, call, ops)
+    return _augment_uniform(images, params, b, v, aug, ksize, out_hw, mean, std, channels_last)
 
 
 # ---- the same for a batch whose images differ in size (include/peclr_hip.h: the geometry tables)
@@ -1480,10 +1367,7 @@ def _ragged_args(packed, geom, wins, params):
     if geom.is_cuda or geom.dtype != torch.int64 or geom.dim() != 2 or geom.shape[1] != AUG_GEOM_INT64S or geom.shape[0] < 1:
         raise PeclrHipError(f"augment: geom must be a host [B,{AUG_GEOM_INT64S}] int64 tensor")
     b = geom.shape[0]
-    if (params.dtype != torch.float64 or params.dim() != 3 or params.shape[1] != b
-            or params.shape[2] != AUG_PARAM_DOUBLES or not params.is_cuda or not params.is_contiguous()):
-        raise PeclrHipError(f"augment: params must be a contiguous [V,{b},{AUG_PARAM_DOUBLES}] float64 HIP tensor")
-    v = params.shape[0]
+    v = _aug_params(params, b)
     if wins.is_cuda or wins.dtype != torch.int64 or tuple(wins.shape) != (v, b, AUG_WIN_INT64S):
         raise PeclrHipError(f"augment: wins must be a host [{v},{b},{AUG_WIN_INT64S}] int64 tensor")
     ends = geom[:, 0] + geom[:, 1] * geom[:, 2] * 3
@@ -1496,6 +1380,41 @@ def _ragged_args(packed, geom, wins, params):
     return b, v, scratch
 
 
+def _augment_ragged(packed, geom, wins, params, b, v, scratch, aug, out_hw, mean, std, channels_last):
+    """`_augment_uniform` for a packed batch (`_ragged_args` checked it) -> (out, srcs or None, crops)."""
+    dev, stream = packed.device, _stream()
+    total = packed.numel()
+    geom_d, wins_d = geom.contiguous().to(dev, non_blocking=True), wins.contiguous().to(dev, non_blocking=True)
+    crops = torch.empty(scratch, device=dev, dtype=torch.uint8)
+    out, out_args = _aug_out(v, b, out_hw, mean, std, channels_last, dev)
+    win_bytes = int((wins[..., 2] * wins[..., 3]).sum()) * 3
+    max_cw, max_ch = int(wins[..., 2].max()), int(wins[..., 3].max())
+    ops = aug.ops if aug is not None else 0
+    srcs = None
+    if ops & AUG_EXT_PRE:
+        srcs = torch.empty((v, total), device=dev, dtype=torch.uint8)
+        tmp = torch.empty((v, total), device=dev, dtype=torch.int16) if ops & AUG_EXT_BLUR else None
+        # (without the blur stage the lengths are not read: nothing to check)
+        kx, ky = (int(geom[:, 3].max()), int(geom[:, 4].max())) if tmp is not None else (1, 1)
+        blur_work = int(((geom[:, 3] + geom[:, 4]) * geom[:, 1] * geom[:, 2]).sum()) * 3 if tmp is not None else 0
+        _launch("augment_pre", "peclr_augment_pre_ragged_u8", packed.data_ptr(), b, v, geom_d.data_ptr(), total, int(geom[:, 1].max()),
+                int(geom[:, 2].max()), aug.ext, aug.coefs, kx, ky, srcs.data_ptr(), None if tmp is None else tmp.data_ptr(), stream,
+                nbytes=v * total * (1 + 1 + (4 if tmp is not None else 0)), flops=v * blur_work)
+        for i in range(v):
+            _launch("augment_warp_crop", "peclr_augment_warp_crop_ragged_u8", srcs[i].data_ptr(), b, 1, geom_d.data_ptr(), params[i].data_ptr(),
+                    wins_d[i].data_ptr(), max_cw, max_ch, crops.data_ptr(), stream, nbytes=2 * int((wins[i, :, 2] * wins[i, :, 3]).sum()) * 3)
+    else:
+        _launch("augment_warp_crop", "peclr_augment_warp_crop_ragged_u8", packed.data_ptr(), b, v, geom_d.data_ptr(), params.data_ptr(),
+                wins_d.data_ptr(), max_cw, max_ch, crops.data_ptr(), stream, nbytes=2 * win_bytes)
+    head = (crops.data_ptr(), b, v, wins_d.data_ptr(), params.data_ptr())
+    nbytes = win_bytes + v * b * out_hw[0] * out_hw[1] * 12
+    if ops & AUG_EXT_POST:
+        _launch("augment_resize_color_norm_ext", "peclr_augment_resize_color_norm_ragged_ext", *head, *aug.noise, *out_args, stream, nbytes=nbytes)
+    else:
+        _launch("augment_resize_color_norm", "peclr_augment_resize_color_norm_ragged", *head, *out_args, stream, nbytes=nbytes)
+    return out, srcs, crops
+
+
 def augment_views_ragged(packed: torch.Tensor, geom: torch.Tensor, wins: torch.Tensor, params: torch.Tensor, out_hw, mean,
                          std, channels_last: bool = True):
     """augment_views for images of different sizes: `packed` the 1-D uint8 HIP buffer of the images back to back,
@@ -1503,24 +1422,7 @@ def augment_views_ragged(packed: torch.Tensor, geom: torch.Tensor, wins: torch.T
     uploaded here), params [V,B,16] float64 (HIP).  The same two launches.
     Returns (out, crops, wins): crops the packed scratch, `ragged_window(crops, wins, v, i)` a window of it."""
     b, v, scratch = _ragged_args(packed, geom, wins, params)
-    oh, ow = out_hw
-    dev, stream = packed.device, _stream()
-    geom_d, wins_d = geom.contiguous().to(dev, non_blocking=True), wins.contiguous().to(dev, non_blocking=True)
-    crops = torch.empty(scratch, device=dev, dtype=torch.uint8)
-    out = torch.empty((v * b, 3, oh, ow), device=dev, dtype=torch.float32,
-                      memory_format=torch.channels_last if channels_last else torch.contiguous_format)
-    mean_arr, std_arr = (c_float * 3)(*mean), (c_float * 3)(*std)
-    win_bytes = int((wins[..., 2] * wins[..., 3]).sum()) * 3
-    with _timed("augment_warp_crop", 2 * win_bytes):
-        rc = lib().peclr_augment_warp_crop_ragged_u8(packed.data_ptr(), b, v, geom_d.data_ptr(), params.data_ptr(),
-                                                     wins_d.data_ptr(), int(wins[..., 2].max()), int(wins[..., 3].max()),
-                                                     crops.data_ptr(), stream)
-    _check(rc, "peclr_augment_warp_crop_ragged_u8")
-    with _timed("augment_resize_color_norm", win_bytes + v * b * oh * ow * 12):
-        rc = lib().peclr_augment_resize_color_norm_ragged(crops.data_ptr(), b, v, wins_d.data_ptr(), params.data_ptr(), oh, ow,
-                                                          ctypes.cast(mean_arr, c_void_p), ctypes.cast(std_arr, c_void_p),
-                                                          int(channels_last), out.data_ptr(), stream)
-    _check(rc, "peclr_augment_resize_color_norm_ragged")
+    out, _, crops = _augment_ragged(packed, geom, wins, params, b, v, scratch, None, out_hw, mean, std, channels_last)
     return out, crops, wins
 
 
@@ -1531,59 +1433,8 @@ def augment_views_ragged_ext(packed: torch.Tensor, geom: torch.Tensor, wins: tor
     blur lengths are geom's, per sample).  Stage 0's per-view sources come back as srcs [V, total bytes] in the packed
     layout (`ragged_image(srcs[v], geom, i)`).  Returns (out, srcs or None, crops, wins)."""
     b, v, scratch = _ragged_args(packed, geom, wins, params)
-    if ext.dtype != torch.int32 or tuple(ext.shape) != (v, b, AUG_EXT_INTS) or not ext.is_cuda or not ext.is_contiguous():
-        raise PeclrHipError(f"augment: ext must be a contiguous [{v},{b},{AUG_EXT_INTS}] int32 HIP tensor")
-    for name, t in (("coefs", coefs), ("noise_table", noise_table)):
-        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_cuda or not t.is_contiguous():
-            raise PeclrHipError(f"augment: {name} must be a contiguous 1-D int32 HIP tensor")
-    if not 0 <= n_table <= noise_table.numel():
-        raise PeclrHipError(f"augment: n_table {n_table} exceeds the table's {noise_table.numel()} entries")
-    oh, ow = out_hw
-    dev, stream = packed.device, _stream()
-    total = packed.numel()
-    geom_d, wins_d = geom.contiguous().to(dev, non_blocking=True), wins.contiguous().to(dev, non_blocking=True)
-    crops = torch.empty(scratch, device=dev, dtype=torch.uint8)
-    out = torch.empty((v * b, 3, oh, ow), device=dev, dtype=torch.float32,
-                      memory_format=torch.channels_last if channels_last else torch.contiguous_format)
-    mean_arr, std_arr = (c_float * 3)(*mean), (c_float * 3)(*std)
-    win_bytes = int((wins[..., 2] * wins[..., 3]).sum()) * 3
-    max_cw, max_ch = int(wins[..., 2].max()), int(wins[..., 3].max())
-    srcs = None
-    if ops & AUG_EXT_PRE:
-        srcs = torch.empty((v, total), device=dev, dtype=torch.uint8)
-        tmp = torch.empty((v, total), device=dev, dtype=torch.int16) if ops & AUG_EXT_BLUR else None
-        # (without the blur stage the lengths are not read: nothing to check)
-        kx, ky = (int(geom[:, 3].max()), int(geom[:, 4].max())) if tmp is not None else (1, 1)
-        blur_work = int(((geom[:, 3] + geom[:, 4]) * geom[:, 1] * geom[:, 2]).sum()) * 3 if tmp is not None else 0
-        with _timed("augment_pre", v * total * (1 + 1 + (4 if tmp is not None else 0)), v * blur_work):
-            rc = lib().peclr_augment_pre_ragged_u8(packed.data_ptr(), b, v, geom_d.data_ptr(), total, int(geom[:, 1].max()),
-                                                   int(geom[:, 2].max()), ext.data_ptr(), coefs.data_ptr(), kx, ky,
-                                                   srcs.data_ptr(), None if tmp is None else tmp.data_ptr(), stream)
-        _check(rc, "peclr_augment_pre_ragged_u8")
-        for i in range(v):
-            with _timed("augment_warp_crop", 2 * int((wins[i, :, 2] * wins[i, :, 3]).sum()) * 3):
-                rc = lib().peclr_augment_warp_crop_ragged_u8(srcs[i].data_ptr(), b, 1, geom_d.data_ptr(), params[i].data_ptr(),
-                                                             wins_d[i].data_ptr(), max_cw, max_ch, crops.data_ptr(), stream)
-            _check(rc, "peclr_augment_warp_crop_ragged_u8")
-    else:
-        with _timed("augment_warp_crop", 2 * win_bytes):
-            rc = lib().peclr_augment_warp_crop_ragged_u8(packed.data_ptr(), b, v, geom_d.data_ptr(), params.data_ptr(),
-                                                         wins_d.data_ptr(), max_cw, max_ch, crops.data_ptr(), stream)
-        _check(rc, "peclr_augment_warp_crop_ragged_u8")
-    mp, sp = ctypes.cast(mean_arr, c_void_p), ctypes.cast(std_arr, c_void_p)
-    if ops & AUG_EXT_POST:
-        with _timed("augment_resize_color_norm_ext", win_bytes + v * b * oh * ow * 12):
-            rc = lib().peclr_augment_resize_color_norm_ragged_ext(crops.data_ptr(), b, v, wins_d.data_ptr(), params.data_ptr(),
-                                                                  ext.data_ptr(), noise_table.data_ptr(), n_table,
-                                                                  noise_seed & (2 ** 64 - 1), call & 0xFFFFFFFF, oh, ow, mp, sp,
-                                                                  int(channels_last), out.data_ptr(), stream)
-        _check(rc, "peclr_augment_resize_color_norm_ragged_ext")
-    else:
-        with _timed("augment_resize_color_norm", win_bytes + v * b * oh * ow * 12):
-            rc = lib().peclr_augment_resize_color_norm_ragged(crops.data_ptr(), b, v, wins_d.data_ptr(), params.data_ptr(), oh, ow,
-                                                              mp, sp, int(channels_last), out.data_ptr(), stream)
-        _check(rc, "peclr_augment_resize_color_norm_ragged")
-    return out, srcs, crops, wins
+    aug = _AugExt(v, b, ext, coefs, noise_table, n_table, noise_seed, call, ops)
+    return (*_augment_ragged(packed, geom, wins, params, b, v, scratch, aug, out_hw, mean, std, channels_last), wins)
 
 
 # ------------------------------------------------------------------ 2.5D hand-pose model at evaluation time (peclr_amd/pose.py)
@@ -1613,10 +1464,8 @@ def pose_crop(images: torch.Tensor, T: torch.Tensor, K: Optional[torch.Tensor], 
         raise PeclrHipError("pose_crop: table must be [3,256] float32")
     out = torch.empty((b, 3, size, size), device=images.device, dtype=torch.float32, memory_format=torch.channels_last)
     k_out = torch.empty((b, 3, 3), device=images.device, dtype=torch.float32) if K is not None else None
-    with _timed("pose_crop", b * h * w * 3 + b * size * size * 12):
-        rc = lib().peclr_pose_crop_u8(images.data_ptr(), b, h, w, tp, kp, _ptr(table, what="pose_crop table"), size,
-                                      out.data_ptr(), k_out.data_ptr() if k_out is not None else None, _stream())
-    _check(rc, "peclr_pose_crop_u8")
+    _launch("pose_crop", "peclr_pose_crop_u8", images.data_ptr(), b, h, w, tp, kp, _ptr(table, what="pose_crop table"), size,
+            out.data_ptr(), k_out.data_ptr() if k_out is not None else None, _stream(), nbytes=b * h * w * 3 + b * size * size * 12)
     return out, k_out
 
 
@@ -1646,19 +1495,16 @@ def pose_head(feat: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, mlp, b
         raise PeclrHipError(f"pose_head: scale must be [{b}] float64")
     if tuple(status.shape) != (b,):
         raise PeclrHipError(f"pose_head: status must be [{b}] int32")
-    with _timed("pose_head", 4 * b * (nf + 64 + 63 + 64) + 4 * 64 * nf):
-        rc = lib().peclr_pose_head_f32(fp, b, nf, _ptr(fc_w, what="pose_head fc weight"), _ptr(fc_b, what="pose_head fc bias"),
-                                       ctypes.cast(mlp_arr, c_void_p), float(bn_eps[0]), float(bn_eps[1]), kp,
-                                       int(K.shape[0] != 1 or b == 1), float(eps), out64.data_ptr(), kp3d.data_ptr(),
-                                       _mat_ptr(T1, b, torch.float64, "T1"), T2.data_ptr() if T2 is not None else None, int(size),
-                                       _ptr(scale, torch.float64, "pose_head scale"), fh.data_ptr() if fh is not None else None,
-                                       _ptr(status, torch.int32, "pose_head status"), _stream())
-    _check(rc, "peclr_pose_head_f32")
+    _launch("pose_head", "peclr_pose_head_f32", fp, b, nf, _ptr(fc_w, what="pose_head fc weight"), _ptr(fc_b, what="pose_head fc bias"),
+            ctypes.cast(mlp_arr, c_void_p), float(bn_eps[0]), float(bn_eps[1]), kp,
+            int(K.shape[0] != 1 or b == 1), float(eps), out64.data_ptr(), kp3d.data_ptr(),
+            _mat_ptr(T1, b, torch.float64, "T1"), T2.data_ptr() if T2 is not None else None, int(size),
+            _ptr(scale, torch.float64, "pose_head scale"), fh.data_ptr() if fh is not None else None,
+            _ptr(status, torch.int32, "pose_head status"), _stream(), nbytes=4 * b * (nf + 64 + 63 + 64) + 4 * 64 * nf)
     return out64, kp3d, T2, fh, status
 
 
 # ------------------------------------------------------------------ scoring pose predictions (peclr_amd/pose_eval.py)
-DTYPE_F64 = 3
 POSE_EVAL_DEGENERATE = 4
 _EVAL_DTYPES = {torch.float32: DTYPE_F32, torch.float64: DTYPE_F64}
 
@@ -1710,14 +1556,13 @@ def pose_eval(pred: torch.Tensor, gt: torch.Tensor, dim: int = 3, procrustes: bo
         rot = torch.empty((b, 3, 3), device=dev, dtype=dt)
         scale = torch.empty((b,), device=dev, dtype=dt)
         trans = torch.empty((b, 3), device=dev, dtype=dt)
-    with _timed("pose_eval", 2 * pred.numel() * pred.element_size()):
-        rc = lib().peclr_pose_eval(pred.data_ptr(), gt.data_ptr(), b, _EVAL_DTYPES[dt], int(dim), _ptr(dist, dt, "pose_eval dist"),
-                                   _ptr(aligned, dt), _ptr(rot, dt), _ptr(scale, dt), _ptr(trans, dt),
-                                   _ptr(dist_aligned if procrustes else None, dt, "pose_eval dist_aligned"),
-                                   _ptr(thr, dt, "pose_eval thresholds") if n_thr else None, n_thr,
-                                   _ptr(counts, torch.int64, "pose_eval counts") if n_thr else None,
-                                   _ptr(status, torch.int32, "pose_eval status"),
-                                   cursor.data_ptr() if cursor is not None else None, rows if cursor is not None else 0, _stream())
-    _check(rc, "peclr_pose_eval")
+    _launch("pose_eval", "peclr_pose_eval", pred.data_ptr(), gt.data_ptr(), b, _EVAL_DTYPES[dt], int(dim), _ptr(dist, dt, "pose_eval dist"),
+            _ptr(aligned, dt), _ptr(rot, dt), _ptr(scale, dt), _ptr(trans, dt),
+            _ptr(dist_aligned if procrustes else None, dt, "pose_eval dist_aligned"),
+            _ptr(thr, dt, "pose_eval thresholds") if n_thr else None, n_thr,
+            _ptr(counts, torch.int64, "pose_eval counts") if n_thr else None,
+            _ptr(status, torch.int32, "pose_eval status"),
+            cursor.data_ptr() if cursor is not None else None, rows if cursor is not None else 0, _stream(),
+            nbytes=2 * pred.numel() * pred.element_size())
     return {"dist": dist, "dist_aligned": dist_aligned if procrustes else None, "aligned": aligned, "rot": rot, "scale": scale,
             "trans": trans, "status": status}

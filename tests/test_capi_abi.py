@@ -93,3 +93,75 @@ def test_integration_stub_matches_the_abi():
         assert [kinds[a.strip()] for a in args.split(",")] == _capi.SIGNATURES[name][1], name
     for name in _capi.SIGNATURES:                       # every entry point is documented there
         assert name in text or name in ("peclr_version", "peclr_error_string"), name
+
+
+_CTYPES = {"int": "c_int", "float": "c_float", "double": "c_double", "int64_t": "c_int64", "uint64_t": "c_uint64",
+           "uint32_t": "c_uint32", "long long": "c_longlong"}
+
+
+def _ctype_of(decl, is_return=False):
+    """The ctypes type of one C return or parameter declaration, by the rule the binding's table follows: any pointer, array
+    parameter or peclr_stream_t is a c_void_p (a `const char*` RETURN a c_char_p), a scalar its like-named ctypes type."""
+    decl = " ".join(decl.split())
+    if is_return and decl.replace(" ", "") == "constchar*":
+        return ctypes.c_char_p
+    if "*" in decl or "[" in decl or decl.startswith("peclr_stream_t"):
+        return ctypes.c_void_p
+    words = [w for w in decl.split() if w != "const"]
+    if not is_return:
+        words = words[:-1]                              # drop the parameter's name
+    return getattr(ctypes, _CTYPES[" ".join(words)])
+
+
+def declared_signatures():
+    text = open(os.path.join(ROOT, "include", "peclr_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    out = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][\w \t]*?[\w*])\s*\b(peclr_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
+        args = args.strip()
+        params = [] if args in ("", "void") else [_ctype_of(a) for a in args.split(",")]
+        out[name] = (_ctype_of(ret, is_return=True), params)
+    return out
+
+
+def test_header_types_equal_the_signature_table():
+    """Not only the names: every return and parameter type of include/peclr_hip.h maps to the ctypes type SIGNATURES gives it."""
+    from peclr_amd import _capi
+
+    declared = declared_signatures()
+    assert sorted(declared) == declared_symbols() and len(declared) == len(_capi.SIGNATURES)
+    for name, sig in declared.items():
+        assert sig == (_capi.SIGNATURES[name][0], list(_capi.SIGNATURES[name][1])), name
+
+
+def test_every_entry_point_name_in_the_binding_is_real_and_every_entry_point_is_used():
+    from peclr_amd import _capi
+
+    src = open(os.path.join(ROOT, "peclr_amd", "_capi.py")).read()
+    start = src.index("SIGNATURES = {")
+    body = src[:start] + src[src.index("\n}\n", start):]                # everything outside the table
+    literals = set(re.findall(r"[\"'](peclr_[a-z0-9_]+)[\"']", body))
+    assert literals and literals <= set(_capi.SIGNATURES), literals - set(_capi.SIGNATURES)
+    used = literals | set(re.findall(r"\.(peclr_[a-z0-9_]+)\(", body))
+    assert set(_capi.SIGNATURES) - used <= {"peclr_version"}, set(_capi.SIGNATURES) - used
+
+
+def test_call_and_launch_report_the_entry_point_they_called(monkeypatch):
+    """A refused call raises under the name that was looked up; `_launch` with the event log off never touches torch.cuda."""
+    import torch
+
+    from peclr_amd import _capi
+
+    args = (0, 4, 4, 4, None, 4, None, 4, None, 4, None, 1, None, None)
+    with pytest.raises(_capi.PeclrHipError, match=r"peclr_gemm_f32 failed: .*\(code -1\)"):
+        _capi._call("peclr_gemm_f32", *args)
+
+    class NoCuda:
+        def __getattr__(self, name):
+            raise AssertionError(f"torch.cuda.{name} touched")
+
+    monkeypatch.setattr(_capi, "EVENT_LOG", None)
+    monkeypatch.setattr(torch, "cuda", NoCuda())
+    with pytest.raises(_capi.PeclrHipError, match=r"peclr_gemm_f32 failed: .*\(code -1\)"):
+        _capi._launch("some_tag", "peclr_gemm_f32", *args)

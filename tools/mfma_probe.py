@@ -63,7 +63,7 @@ def main():
                       lambda ga=ga, wb=wb, gd=gd: _capi.gemm_add(_capi.GEMM_NN, ga, wb, gd, tag="conv1x1_dgrad_add")))
         gab, wbt, gdb = ga.bfloat16(), wb.t().contiguous().bfloat16(), gd.bfloat16()
         calls.append((f"conv1x1_dgrad_add_bf16@{r}x{cmid}x{cin}",
-                      lambda gab=gab, wbt=wbt, gdb=gdb: _capi.gemm_add_bf16(gab, wbt, gdb, tag="conv1x1_dgrad_add")))
+                      lambda gab=gab, wbt=wbt, gdb=gdb: _capi.gemm_add_half(gab, wbt, gdb, tag="conv1x1_dgrad_add")))
     # round 3: the six-product GEMM family at ResNet-50's shapes -- 1x1 forward / input gradient (peclr_gemm_x6p_f32, with and
     # without the residual-gradient addend), 3x3 forward (peclr_conv3x3_x6p_f32), weight gradients (peclr_gemm_x6t_f32)
     for r, n, k in ((200704, 128, 512), (200704, 512, 128), (50176, 256, 1024), (50176, 1024, 256), (12544, 512, 2048), (12544, 2048, 512)):
