@@ -456,6 +456,17 @@ int peclr_bn2d_bwd_apply(const void* dy, const void* x, const void* y, const uin
                          int io_dtype, int R, int C, int relu, const float* save_mean,
                          const float* save_invstd, const float* scale_shift, const float* coef,
                          void* dx, void* d_residual, float* absmax_out, peclr_stream_t stream);
+/* Backward of peclr_bn2d_apply_res_bn (with relu): the apply passes of BOTH BatchNorm layers in one.  With d = relu_mask . dy -- the
+ * d_residual peclr_bn2d_bwd_apply would write for the shortcut layer's backward to read back -- dx is peclr_bn2d_bwd_apply's result
+ * for (dy, x, relu_mask) with the tables of the block's last layer, dxs its result for (d, xs, no ReLU) with the s_* tables of the
+ * shortcut's layer, both bit for bit; d itself is never written.  The shortcut layer's sums come from peclr_bn2d_bwd_reduce on
+ * (dy, xs, relu_mask) with its own statistics -- the same partial table as the reduction of d.  relu_mask is required (C % 32 == 0);
+ * absmax_out / s_absmax_out: max |dx| / max |dxs| (nullable, fp32).                                                              */
+int peclr_bn2d_bwd_apply_res_bn(const void* dy, const uint32_t* relu_mask, const void* x, const void* xs, int io_dtype,
+                                int R, int C, const float* save_mean, const float* save_invstd,
+                                const float* scale_shift, const float* coef, const float* s_save_mean,
+                                const float* s_save_invstd, const float* s_scale_shift, const float* s_coef, void* dx,
+                                void* dxs, float* absmax_out, float* s_absmax_out, peclr_stream_t stream);
 
 /* Encoder tail: the last residual block's BatchNorm2d + `out += identity` + ReLU, then
  * AdaptiveAvgPool2d((1,1)) and `.flatten(1)` (features[7][-1].bn*, features[8] and the flatten of

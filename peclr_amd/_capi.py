@@ -65,6 +65,7 @@ SIGNATURES = {
     "peclr_bn2d_bwd_reduce": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P]),
     "peclr_bn2d_bwd_finalize_f32": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "peclr_bn2d_bwd_apply": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "peclr_bn2d_bwd_apply_res_bn": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "peclr_bn2d_apply_avgpool": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
     "peclr_bn2d_bwd_reduce_avgpool": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P]),
     "peclr_bn2d_bwd_apply_avgpool": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -1164,6 +1165,44 @@ def bn2d_bwd(dy, x, y, mask, save, ss, training, relu, want_dres, sync_group=Non
     _launch("bn2d_bwd_apply", "peclr_bn2d_bwd_apply", *head, coef.data_ptr(), dx.data_ptr(), dres.data_ptr() if dres is not None else None,
             _absmax_ptr(absmax, x), _stream(), nbytes=(3 + (1 if want_dres else 0)) * e * r * c + extra)
     return dx, dparams[0], dparams[1], dres
+
+
+def bn2d_bwd_res_bn(dy, x, mask, save, ss, training, xs, save_s, ss_s, training_s, pre=None, absmax=None, absmax_s=None):
+    """Backward of `bn2d_fwd(..., relu=True, residual_bn=(xs, ss_s))`, both BatchNorm layers at once: (dx, dgamma, dbeta, dxs,
+    dgamma_s, dbeta_s).  The gradient that reaches the shortcut's layer is mask . dy; it is not written out: that layer's reduction
+    reads (dy, mask) against xs (the partial table `bn2d_bwd` would sum from the written tensor, n_split included), and ONE apply
+    pass writes dx and dxs (peclr_bn2d_bwd_apply_res_bn) -- bit-identical to `bn2d_bwd(want_dres=True)` followed by the shortcut
+    layer's own `bn2d_bwd`.  pre: as in `bn2d_bwd` (the sums of THIS layer); per-rank statistics only."""
+    n, c, h, w = x.shape
+    r = n * h * w
+    dev = x.device
+    io, e = _IO[x.dtype]
+    if mask is None or c % 32 or tuple(xs.shape) != tuple(x.shape):
+        raise PeclrHipError("bn2d_bwd_res_bn: needs the forward's 1-bit ReLU mask (C % 32 == 0) and a shortcut input of x's shape")
+    dyp, xp, xsp = _nhwc_ptr(dy, "bn2d dy", x.dtype), _nhwc_ptr(x, "bn2d x"), _nhwc_ptr(xs, "bn2d shortcut x", x.dtype)
+    mp = _ptr(mask, torch.int32, "relu mask")
+    mask_bytes = r * c // 8
+    ns = bn2d_n_split(r, c, io)
+    partial_s = torch.empty((2 * ns, c), device=dev, dtype=torch.float32)
+    _launch("bn2d_bwd_reduce", "peclr_bn2d_bwd_reduce", dyp, xsp, None, mp, io, r, c, 1, save_s[0].data_ptr(), save_s[1].data_ptr(),
+            ss_s.data_ptr(), partial_s.data_ptr(), ns, _stream(), nbytes=2 * e * r * c + mask_bytes)
+    dparams_s, coef_s = _bn2d_bwd_finalize(partial_s, ns, r, c, ss_s, training_s, None)
+    if pre is not None:
+        partial, ns = pre
+        if tuple(partial.shape) != (2 * ns, c):
+            raise PeclrHipError(f"bn2d backward: precomputed reduction of shape {tuple(partial.shape)} for C = {c}, n_split = {ns}")
+    else:
+        partial = torch.empty((2 * ns, c), device=dev, dtype=torch.float32)
+        _launch("bn2d_bwd_reduce", "peclr_bn2d_bwd_reduce", dyp, xp, None, mp, io, r, c, 1, save[0].data_ptr(), save[1].data_ptr(),
+                ss.data_ptr(), partial.data_ptr(), ns, _stream(), nbytes=2 * e * r * c + mask_bytes)
+    dparams, coef = _bn2d_bwd_finalize(partial, ns, r, c, ss, training, None)
+    dx = torch.empty_like(x, memory_format=torch.channels_last)
+    dxs = torch.empty_like(x, memory_format=torch.channels_last)
+    _launch("bn2d_bwd_apply", "peclr_bn2d_bwd_apply_res_bn", dyp, mp, xp, xsp, io, r, c, save[0].data_ptr(), save[1].data_ptr(),
+            ss.data_ptr(), coef.data_ptr(), save_s[0].data_ptr(), save_s[1].data_ptr(), ss_s.data_ptr(), coef_s.data_ptr(),
+            dx.data_ptr(), dxs.data_ptr(), _absmax_ptr(absmax, x), _absmax_ptr(absmax_s, x), _stream(),
+            nbytes=5 * e * r * c + mask_bytes)
+    return dx, dparams[0], dparams[1], dxs, dparams_s[0], dparams_s[1]
 
 
 def bn2d_avgpool_fwd(x, residual, gamma, beta, running_mean, running_var, nbt, training, eps, momentum, sync_group=None,

@@ -125,6 +125,9 @@ class Routing:
     bn_bwd_in_gemm: bool = dataclasses.field(default_factory=lambda: _env_flag("PECLR_BN_BWD_IN_GEMM"))       # BatchNorm backward reduction in the dgrad epilogue
     # the shortcut's BatchNorm (conv1x1 -> bn of a layer's first block) applied inside the block's last pass (bn3 + shortcut + ReLU)
     bn_shortcut_in_add: bool = dataclasses.field(default_factory=lambda: _env_flag("PECLR_BN_SHORTCUT_IN_ADD"))
+    # ... and its backward: the shortcut layer's reduction reads (dy, mask) and ONE apply pass writes the gradients of both layers'
+    # inputs (peclr_bn2d_bwd_apply_res_bn) -- the masked gradient is not written out and read back (off: the three-pass form)
+    bn_shortcut_bwd_fused: bool = dataclasses.field(default_factory=lambda: _env_flag("PECLR_BN_SHORTCUT_BWD_FUSED"))
     x6_layer1: bool = dataclasses.field(default_factory=lambda: _env_flag("PECLR_X6_LAYER1"))          # layer1's 64-channel 1x1 convolutions in-tree
     x6_layer1_fork: bool = dataclasses.field(default_factory=lambda: _env_flag("PECLR_X6_LAYER1_FORK"))   # layer1's fused entry gradient (K = 64)
     x6_layer1_wgrad: bool = dataclasses.field(default_factory=lambda: _env_flag("PECLR_X6_LAYER1_WGRAD"))  # layer1's 64-wide weight gradients
@@ -379,9 +382,9 @@ class _BN2dAct(torch.autograd.Function):
         """link: None or an empty list that receives what a consumer's input-gradient GEMM needs to perform this layer's
         backward reduction in its epilogue: [x, save, scale_shift, relu mask or None, relu, token].
         defer: None, or an empty list -- the layer (a shortcut's BatchNorm, no ReLU) only finishes its statistics; the list comes
-        back as [x, scale_shift, relu] and the result is a placeholder (`_deferred_view`) whose consumer -- the block's last
-        BatchNorm pass -- computes the layer on the fly; any other reader materialises it (`_Materialize`).
-        res_deferred: None, or (x_s, scale_shift_s, False) -- `residual` is the placeholder of the shortcut's BatchNorm layer (no
+        back as [x, scale_shift, relu, hand-over record] and the result is a placeholder (`_deferred_view`) whose consumer -- the
+        block's last BatchNorm pass -- computes the layer on the fly; any other reader materialises it (`_Materialize`).
+        res_deferred: None, or (x_s, scale_shift_s, False, record) -- `residual` is the placeholder of the shortcut's BatchNorm layer (no
         ReLU), which left its apply pass to THIS pass: the residual is computed from that layer's input on the fly.
         amax: None, or an empty list that receives the device float holding max |y| (the "pair" GEMMs' operand scale)."""
         training, sync, stat_args, stat_kw = bn._fwd_args(pre)
@@ -394,11 +397,23 @@ class _BN2dAct(torch.autograd.Function):
                                            residual_bn=res_deferred[:2] if res_deferred is not None else None, absmax=slot, **stat_kw)
         if slot is not None:
             amax[:] = [slot]
+        ctx.handover = None
         if defer is not None:
-            defer[:] = [x, ss, relu]
+            # (the fourth entry: what the consumer's backward needs to perform this layer's backward too -- `_dual_backward_ok`)
+            ctx.handover = dict(save=save, training=training, sync=sync, needs_dx=ctx.needs_input_grad[0],
+                                checkpointed=_RECOMPUTING or _FIRST_RUN, materialized=False)
+            defer[:] = [x, ss, relu, ctx.handover]
             y = _deferred_view(x)
         keep = mask if mask is not None else (y if need_mask else None)
-        ctx.save_for_backward(x, save, ss, *([keep] if keep is not None else []))
+        # the shortcut layer's backward in this layer's backward pass (ROUTING.bn_shortcut_bwd_fused): decided here as far as the
+        # forward knows, and again in the backward (`_dual_backward_ok`)
+        ctx.dual = None
+        if (ROUTING.bn_shortcut_bwd_fused and res_deferred is not None and len(res_deferred) > 3 and relu and mask is not None
+                and sync is None and res_deferred[3]["sync"] is None and res_deferred[3]["needs_dx"]
+                and not (_RECOMPUTING or _FIRST_RUN or res_deferred[3]["checkpointed"])):
+            ctx.dual = res_deferred[3]
+        dual_saved = [res_deferred[0], res_deferred[3]["save"], res_deferred[1]] if ctx.dual is not None else []
+        ctx.save_for_backward(x, save, ss, *([keep] if keep is not None else []), *dual_saved)
         ctx.cfg = (training, relu, residual is not None, keep is not None, mask is not None)
         ctx.sync_group = sync
         ctx.token = None
@@ -416,6 +431,17 @@ class _BN2dAct(torch.autograd.Function):
         x, save, ss = ctx.saved_tensors[:3]
         keep = ctx.saved_tensors[3] if has_keep else None
         y, mask = (None, keep) if is_mask else (keep, None)
+        handed = _take_lazy(dy)
+        if handed is not None and handed[0] == "bn":
+            # the consumer's backward (the block's last BatchNorm pass) performed this layer's backward as well: nothing to launch
+            _, dx, dgamma, dbeta, slot, owner = handed
+            if owner is not ctx.handover:
+                raise _capi.PeclrHipError("fused BatchNorm2d: a shortcut layer's gradients arrived at another layer")
+            if slot is not None:
+                _tag_absmax(dx, slot)
+            return dx, dgamma, dbeta, None, None, None, None, None, None, None, None, None
+        if handed is not None:
+            dy = _dense_of(handed, dy.shape)
         dy = dy.to(x.dtype).contiguous(memory_format=torch.channels_last)
         pre = None
         ent = _BN_BWD_STATS.pop(dy.data_ptr(), None) if ctx.token is not None else None
@@ -426,6 +452,17 @@ class _BN2dAct(torch.autograd.Function):
             pre = ent[1:3]
         lazy = ctx.lazy_res and has_res and ctx.needs_input_grad[3] and ROUTING.lazy_residual_grad and not torch.is_anomaly_enabled()
         slot = _new_absmax(x)
+        if _dual_backward_ok(ctx):
+            # first block of a stage: the shortcut layer's reduction on (dy, mask), then both layers' apply passes in one; that
+            # layer's node receives its finished gradients (`_lazy_grad`) and launches nothing
+            xs, save_s, ss_s = ctx.saved_tensors[-3:]
+            slot_s = _new_absmax(xs)
+            dx, dgamma, dbeta, dxs, dgamma_s, dbeta_s = _capi.bn2d_bwd_res_bn(dy, x, mask, save, ss, training, xs, save_s, ss_s,
+                                                                              ctx.dual["training"], pre=pre, absmax=slot, absmax_s=slot_s)
+            if slot is not None:
+                _tag_absmax(dx, slot)
+            dres = _lazy_grad(("bn", dxs, dgamma_s, dbeta_s, slot_s, ctx.dual), xs.shape, xs.device, xs.dtype)
+            return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None, None
         dx, dgamma, dbeta, dres = _capi.bn2d_bwd(dy, x, y, mask, save, ss, training, relu,
                                                  has_res and ctx.needs_input_grad[3] and not lazy, sync_group=ctx.sync_group, pre=pre,
                                                  absmax=slot)
@@ -436,6 +473,16 @@ class _BN2dAct(torch.autograd.Function):
         elif has_res and dres is None and ctx.needs_input_grad[3]:
             dres = dy
         return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None, None
+
+
+def _dual_backward_ok(ctx) -> bool:
+    """May the backward of the block's last BatchNorm pass (`ctx`) perform the shortcut layer's backward as well
+    (peclr_bn2d_bwd_apply_res_bn)?  `ctx.dual` -- the shortcut layer's hand-over record -- is there when the forward found nothing
+    against it (the switch, a 1-bit mask, per-rank statistics, no activation checkpointing, a shortcut input that wants its
+    gradient); the backward adds what only it can know: the switch now, anomaly mode (the hand-over is a NaN view), a second
+    reader for which the placeholder was written out after all (autograd would ADD its gradient to the view)."""
+    return bool(ctx.dual is not None and ROUTING.bn_shortcut_bwd_fused and ctx.needs_input_grad[3] and not ctx.dual["materialized"]
+                and not _NESTED_BACKWARD and not torch.is_anomaly_enabled())
 
 
 _NAN_PLACEHOLDER = {}
@@ -456,7 +503,7 @@ class _Materialize(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, placeholder, deferred, amax=None):
-        x, ss, relu = deferred
+        x, ss, relu = deferred[:3]
         slot = _new_absmax(x) if amax is not None else None
         if slot is not None:
             amax[:] = [slot]
@@ -468,6 +515,8 @@ class _Materialize(torch.autograd.Function):
 
 
 def _materialized(x: Tensor, deferred) -> Tensor:
+    if len(deferred) > 3:
+        deferred[3]["materialized"] = True      # (this reader's gradient comes back dense: `_dual_backward_ok`)
     amax = []
     y = _Materialize.apply(x, deferred, amax)
     if amax:
@@ -924,8 +973,11 @@ def _compact_grad(dc: Tensor, shape) -> Tensor:
 
 
 def _take_lazy(g: Tensor):
-    """The parked payload -- ("s2", compact gradient) or ("mask", dy, bit mask) -- if `g` is one of `_lazy_grad`'s views."""
-    if g is None or g.dim() != 4 or any(g.stride()) or not _COMPACT:
+    """The parked payload -- ("s2", compact gradient), ("mask", dy, bit mask) or ("bn", dx, dgamma, dbeta, absmax slot, hand-over
+    record: a shortcut BatchNorm layer's finished gradients, `_BN2dAct.backward`) -- if `g` is one of `_lazy_grad`'s views."""
+    # (a view expanded from one element: zero strides -- except along dimensions of size 1, which keep the element's own stride:
+    # a [N, C, 1, 1] gradient arrives with strides (0, 0, 1, 1))
+    if g is None or g.dim() != 4 or not _COMPACT or any(st for st, n in zip(g.stride(), g.shape) if n != 1):
         return None
     hit = _COMPACT.get(g.data_ptr())
     if hit is None or hit[1] != tuple(g.shape):
@@ -943,6 +995,9 @@ def _dense_of(payload, shape) -> Tensor:
     """The dense gradient a payload stands for (fallback paths)."""
     if payload[0] == "s2":
         return _expand_compact(payload[1], shape)
+    if payload[0] != "mask":
+        # ("bn": a shortcut BatchNorm layer's finished gradients -- only that layer's own node may take them)
+        raise _capi.PeclrHipError(f"a {payload[0]!r} gradient hand-over reached a consumer that cannot take it")
     _, dy, mask = payload
     n, c, h, w = shape
     bits = (mask.view(n * h * w, c // 32, 1) >> torch.arange(32, device=mask.device, dtype=torch.int32)) & 1
@@ -1399,8 +1454,9 @@ class FusedBatchNormAct2d(nn.BatchNorm2d):
     def forward(self, x: Tensor, residual: Optional[Tensor] = None, relu: Optional[bool] = None, consumer=None) -> Tensor:
         """consumer: the ONLY reader of the result.  For the BatchNorm of a shortcut (conv1x1 -> bn, no ReLU) it is the block's
         last FusedBatchNormAct2d, which adds the shortcut in its own pass (`_takes_deferred_residual`): the layer then only
-        finishes its statistics and returns a placeholder carrying `_peclr_deferred = [x, scale_shift, relu]`: no apply pass, no
-        output tensor.  A residual that is such a placeholder is computed on the fly (or materialised).  (A Conv2d consumer that
+        finishes its statistics and returns a placeholder carrying `_peclr_deferred = [x, scale_shift, relu, hand-over record]`: no
+        apply pass, no output tensor.  A residual that is such a placeholder is computed on the fly (or materialised), and the
+        consumer's backward then performs this layer's backward too (`_dual_backward_ok`).  (A Conv2d consumer that
         applied the layer in its own operand path was built in round 5 and taken out in round 6: docs/history.md E.)"""
         relu = self.default_relu if relu is None else relu
         pool = self.default_pool and relu and residual is None

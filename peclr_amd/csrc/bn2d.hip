@@ -803,6 +803,91 @@ __global__ __launch_bounds__(T) void bn2d_bwd_apply_kernel(const IO* __restrict_
     if constexpr (sizeof(IO) == 4) absmax_commit(absmax, amax);
 }
 
+// First block of a stage, backward of relu(bn3(x) + bn_s(xs)): the apply passes of BOTH BatchNorm layers in one.  The gradient
+// that reaches the shortcut's layer is d = mask . dy -- what bn2d_bwd_apply_kernel<IO, 3, true> writes out as `dres` for
+// bn2d_bwd_apply_kernel<IO, 0, false> to read back: here it stays in registers (one write and one read of a block-output-sized
+// tensor less, and one launch).  dx is that kernel's MASK == 3 expression, dxs its MASK == 0 expression on d, with the same fmaf
+// nesting: both tensors and both maxima are bit-identical to the two launches.  `b` / `s`: the per-channel tables of bn3 / of the
+// shortcut's layer (eval mode: zero coefficients, no special case).
+struct BwdTables {
+    const float *mean, *invstd, *scale_shift, *coef;
+};
+// U: rows in flight per stream.  Three streams of loads (dy, x, xs) instead of two and ten per-channel constants instead of five:
+// with the U = 8 of the other kernels the raw words alone are 96 registers (the entry point fixes U per storage type).
+template <typename IO, int U>
+__global__ __launch_bounds__(T) void bn2d_bwd_apply_res_bn_kernel(const IO* __restrict__ dy, const unsigned* __restrict__ relu_mask,
+                                                                  const IO* __restrict__ x, const IO* __restrict__ xs, Geo g,
+                                                                  BwdTables b, BwdTables s, IO* __restrict__ dx, IO* __restrict__ dxs,
+                                                                  float* __restrict__ absmax, float* __restrict__ absmax_s) {
+    constexpr int W = Word<IO>::W;
+    int col, r0, r1, rl;
+    thread_geo<W>(g, col, r0, r1, rl);
+    float amax = 0.f, amax_s = 0.f;
+    constexpr bool FOLD = sizeof(IO) == 2;          // (as bn2d_bwd_apply_kernel: dx = d' scale + x a + b for 16-bit storage)
+    Fv<W> mean = loadp<W>(b.mean + col), invstd = loadp<W>(b.invstd + col);
+    const Fv<W> sc = loadp<W>(b.scale_shift + col);
+    Fv<W> k2 = loadp<W>(b.coef + col), k3 = loadp<W>(b.coef + g.C + col);
+    Fv<W> mean_s = loadp<W>(s.mean + col), invstd_s = loadp<W>(s.invstd + col);
+    const Fv<W> sc_s = loadp<W>(s.scale_shift + col);
+    Fv<W> k2_s = loadp<W>(s.coef + col), k3_s = loadp<W>(s.coef + g.C + col);
+    if constexpr (FOLD) {
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            k3.v[k] *= invstd.v[k];
+            k2.v[k] = fmaf(-mean.v[k], k3.v[k], k2.v[k]);
+            k3_s.v[k] *= invstd_s.v[k];
+            k2_s.v[k] = fmaf(-mean_s.v[k], k3_s.v[k], k2_s.v[k]);
+        }
+    }
+    auto emit = [&](size_t o, const Fv<W>& d0, const Fv<W>& xv, const Fv<W>& sv, unsigned bits) {
+        const Fv<W> d = masked<W, 3>(d0, xv, xv, bits, sc, sc);
+        Fv<W> t, ts;
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            if constexpr (FOLD) {
+                t.v[k] = fmaf(d.v[k], sc.v[k], fmaf(xv.v[k], k3.v[k], k2.v[k]));
+                ts.v[k] = fmaf(d.v[k], sc_s.v[k], fmaf(sv.v[k], k3_s.v[k], k2_s.v[k]));
+            } else {
+                const float xh = (xv.v[k] - mean.v[k]) * invstd.v[k];
+                t.v[k] = fmaf(d.v[k], sc.v[k], fmaf(xh, k3.v[k], k2.v[k]));
+                const float xh_s = (sv.v[k] - mean_s.v[k]) * invstd_s.v[k];
+                ts.v[k] = fmaf(d.v[k], sc_s.v[k], fmaf(xh_s, k3_s.v[k], k2_s.v[k]));
+            }
+            if constexpr (sizeof(IO) == 4) {
+                amax = fmaxf(amax, fabsf(t.v[k]));
+                amax_s = fmaxf(amax_s, fabsf(ts.v[k]));
+            }
+        }
+        Word<IO>::store(dx + o, t);
+        Word<IO>::store(dxs + o, ts);
+    };
+    typedef typename Word<IO>::Raw Raw;
+    int r = r0 + rl;
+    for (; r + (U - 1) * g.RPP < r1; r += U * g.RPP) {
+        Raw d[U], xv[U], sv[U];
+        unsigned mb[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const size_t o = (size_t)(r + u * g.RPP) * g.C + col;
+            d[u] = Word<IO>::load_raw(dy + o);
+            xv[u] = Word<IO>::load_raw(x + o);
+            sv[u] = Word<IO>::load_raw(xs + o);
+            mb[u] = mask_load<W>(relu_mask, r + u * g.RPP, col, g.C);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            emit((size_t)(r + u * g.RPP) * g.C + col, Word<IO>::expand(d[u]), Word<IO>::expand(xv[u]), Word<IO>::expand(sv[u]), mb[u]);
+    }
+    for (; r < r1; r += g.RPP) {
+        const size_t o = (size_t)r * g.C + col;
+        emit(o, Word<IO>::load(dy + o), Word<IO>::load(x + o), Word<IO>::load(xs + o), mask_load<W>(relu_mask, r, col, g.C));
+    }
+    if constexpr (sizeof(IO) == 4) {
+        absmax_commit(absmax, amax);
+        absmax_commit(absmax_s, amax_s);
+    }
+}
+
 // ------------------------------------------------------------------ host
 
 // ------------------------------------------------------------------ stem: BN + ReLU + 3x3/2 max-pool in one pass
@@ -1316,6 +1401,31 @@ extern "C" int peclr_bn2d_bwd_apply(const void* dy, const void* x, const void* y
     if (relu_mask && C % 32) return PECLR_ERR_SHAPE;
     const int mm = mask_mode(relu, y, relu_mask);
     PECLR_IO_SWITCH(io_dtype, launch_bwd_apply<IO>(p, s, mm, dy, x, y, relu_mask, save_mean, save_invstd, scale_shift, coef, dx, d_residual, absmax_out));
+    return launch_status();
+}
+
+// dx = the MASK == 3 apply of bn3, dxs = the plain apply of the shortcut's layer on mask . dy, in one pass (see the kernel)
+extern "C" int peclr_bn2d_bwd_apply_res_bn(const void* dy, const uint32_t* relu_mask, const void* x, const void* xs, int io_dtype,
+                                           int R, int C, const float* save_mean, const float* save_invstd,
+                                           const float* scale_shift, const float* coef, const float* s_save_mean,
+                                           const float* s_save_invstd, const float* s_scale_shift, const float* s_coef, void* dx,
+                                           void* dxs, float* absmax_out, float* s_absmax_out, peclr_stream_t stream) {
+    if (!dy || !relu_mask || !x || !xs || !save_mean || !save_invstd || !scale_shift || !coef || !s_save_mean || !s_save_invstd ||
+        !s_scale_shift || !s_coef || !dx || !dxs)
+        return PECLR_ERR_NULL;
+    Plan p;
+    if (C % 32 || !plan_for(io_dtype, R, C, 0, p)) return PECLR_ERR_SHAPE;
+    if (dx == dxs || dx == dy || dx == x || dx == xs || dxs == dy || dxs == x || dxs == xs) return PECLR_ERR_SHAPE;   // (no pass in place)
+    if (!all_aligned({dy, x, xs, dx, dxs, save_mean, save_invstd, scale_shift, coef, s_save_mean, s_save_invstd, s_scale_shift, s_coef}))
+        return PECLR_ERR_ALIGN;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const BwdTables b = {save_mean, save_invstd, scale_shift, coef}, t = {s_save_mean, s_save_invstd, s_scale_shift, s_coef};
+    // rows in flight: fp32 two (80 VGPRs, 6 waves per SIMD; four: 102 VGPRs, 4 waves -- one below bn2d_bwd_apply_kernel<float, 3,
+    // true> -- and the same time: 695 against 697 us at 802 816 x 256); 16-bit four (bf16 102, fp16 90 VGPRs; two: 122 / 113).
+    PECLR_IO_SWITCH(io_dtype, hipLaunchKernelGGL((bn2d_bwd_apply_res_bn_kernel<IO, (sizeof(IO) == 4 ? 2 : 4)>), p.grid, dim3(T), 0, s,
+                                                 static_cast<const IO*>(dy), relu_mask, static_cast<const IO*>(x),
+                                                 static_cast<const IO*>(xs), p.g, b, t, static_cast<IO*>(dx), static_cast<IO*>(dxs),
+                                                 absmax_out, s_absmax_out));
     return launch_status();
 }
 
