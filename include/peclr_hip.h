@@ -772,6 +772,34 @@ int peclr_pose_eval(const void* pred, const void* gt, int B, int dtype, int dim,
                     void* trans, void* dist_aligned, const void* thr, int n_thr, long long* counts, int* status, int* cursor,
                     int capacity, peclr_stream_t stream);
 
+/* The label side of a supervised sample (reference src/data_loader/utils.py: convert_to_2_5D, convert_2_5D_to_3D, get_root_depth,
+ * get_zroot_constraint_terms; data_set.py: prepare_supervised_sample), csrc/labels.hip; host side: peclr_amd/supervised.py.
+ * Every tensor is float32 and contiguous except T (float64).  Each entry point is ONE launch on `stream`: no host
+ * synchronisation, no atomics, nothing kept between launches -- safe inside a hipGraph capture.  Every stage is evaluated in
+ * float64 and each output is rounded to float32 once; a sample's outputs are a pure function of that sample (the same bits
+ * alone and at any position of any batch).  Argument errors (B <= 0, a NULL pointer that is not marked nullable) are -1.
+ *
+ * peclr_joints3d_to_25d: K [B][3][3], joints3d [B][21][3] -> joints25d [B][21][3] = ((K p) / z in x and y, (z - z_wrist) /
+ *   scale), scale [B] = |joint 2 - joint 0| (wrist -- index MCP).
+ * peclr_joints25d_to_3d: joints25d, scale, K -> joints3d [B][21][3] = (K^-1 (u, v, 1)) (z + z_root) scale, with K^-1 the
+ *   adjugate over the determinant and z_root [B] (nullable output) the root of the quadratic of arXiv:1804.09534 eq. 6-7,
+ *   with the reference's two clamp(min = 1e-6) (discriminant, leading coefficient).  z_root_calc [B] (nullable): used as the
+ *   root depth of the conversion instead; z_root still receives the quadratic's.
+ * peclr_supervised_labels: K, joints3d, T [B][3][3] float64 (the augmentation's forward matrix), joints_raw [B][21][3]
+ *   (nullable: joints3d then) ->
+ *     t_out = fl32(T);  k_out = fl32(T) @ K;
+ *     use_palm = 0: joints = T applied to (u, v, 1) of joints3d_to_25d(K, joints3d), depth kept; scale of joints3d;
+ *                   joints3d_out = joints3d; joints_raw_out = joints_raw;
+ *     use_palm = 1: joints3d_out / joints_raw_out = the input with joint 0 replaced by the mean of joints 0 and 2;
+ *                   joints, scale = joints3d_to_25d(k_out, joints3d_out);
+ *     joints3d_recreated = joints25d_to_3d(joints, scale, k_out), read as the float32 values written out.           */
+int peclr_joints3d_to_25d(const float* K, const float* joints3d, int B, float* joints25d, float* scale, peclr_stream_t stream);
+int peclr_joints25d_to_3d(const float* joints25d, const float* scale, const float* K, const float* z_root_calc, int B,
+                          float* joints3d, float* z_root, peclr_stream_t stream);
+int peclr_supervised_labels(const float* K, const float* joints3d, const double* T, const float* joints_raw, int B, int use_palm,
+                            float* joints, float* k_out, float* scale, float* joints3d_out, float* joints3d_recreated,
+                            float* joints_raw_out, float* t_out, peclr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,6 +124,9 @@ SIGNATURES = {
     "peclr_pose_head_f32": (c_int, [_P, c_int, c_int, _P, _P, _P, c_float, c_float, _P, c_int, c_float, _P, _P, _P, _P, c_int,
                                     _P, _P, _P, _P]),
     "peclr_pose_eval": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, c_int, _P]),
+    "peclr_joints3d_to_25d": (c_int, [_P, _P, c_int, _P, _P, _P]),
+    "peclr_joints25d_to_3d": (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P]),
+    "peclr_supervised_labels": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 
@@ -1605,3 +1608,70 @@ def pose_eval(pred: torch.Tensor, gt: torch.Tensor, dim: int = 3, procrustes: bo
             nbytes=2 * pred.numel() * pred.element_size())
     return {"dist": dist, "dist_aligned": dist_aligned if procrustes else None, "aligned": aligned, "rot": rot, "scale": scale,
             "trans": trans, "status": status}
+
+
+# ------------------------------------------------------------------ labels of a supervised sample (peclr_amd/supervised.py)
+def _label_ptr(t, shape, what, dtype=torch.float32):
+    """Pointer of a contiguous HIP tensor of exactly `shape` and `dtype` (None stays None)."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
+        raise PeclrHipError(f"{what}: expected a HIP device tensor, got {where} (peclr_amd has no CPU path)")
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise PeclrHipError(f"{what}: must be a contiguous {list(shape)} {dtype} tensor, got {t.dtype} {tuple(t.shape)}")
+    return t.data_ptr()
+
+
+def _label_batch(joints, what):
+    if not isinstance(joints, torch.Tensor) or not joints.is_cuda:
+        where = joints.device if isinstance(joints, torch.Tensor) else type(joints).__name__
+        raise PeclrHipError(f"{what}: expected a HIP device tensor, got {where} (peclr_amd has no CPU path)")
+    if joints.dim() != 3 or tuple(joints.shape[1:]) != (21, 3) or joints.shape[0] < 1:
+        raise PeclrHipError(f"{what}: joints must be [B,21,3] with B >= 1, got {tuple(joints.shape)}")
+    return joints.shape[0]
+
+
+def joints3d_to_25d(K: torch.Tensor, joints3d: torch.Tensor, out: Optional[torch.Tensor] = None,
+                    scale: Optional[torch.Tensor] = None):
+    """K [B,3,3], joints3d [B,21,3] float32 -> (joints25d [B,21,3], scale [B]) float32: the batched convert_to_2_5D.  One launch."""
+    b = _label_batch(joints3d, "joints3d_to_25d")
+    kp, jp = _label_ptr(K, (b, 3, 3), "joints3d_to_25d K"), _label_ptr(joints3d, (b, 21, 3), "joints3d_to_25d joints3d")
+    out = torch.empty((b, 21, 3), device=joints3d.device, dtype=torch.float32) if out is None else out
+    scale = torch.empty((b,), device=joints3d.device, dtype=torch.float32) if scale is None else scale
+    _launch("joints3d_to_25d", "peclr_joints3d_to_25d", kp, jp, b, _label_ptr(out, (b, 21, 3), "joints3d_to_25d out"),
+            _label_ptr(scale, (b,), "joints3d_to_25d scale"), _stream(), nbytes=4 * b * (9 + 63 + 63 + 1))
+    return out, scale
+
+
+def joints25d_to_3d(joints25d: torch.Tensor, scale: torch.Tensor, K: torch.Tensor, z_root_calc: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None, z_root: Optional[torch.Tensor] = None):
+    """joints25d [B,21,3], scale [B], K [B,3,3] float32 (z_root_calc [B]: a root depth to use instead of the quadratic's) ->
+    (joints3d [B,21,3], z_root [B]: the quadratic's root depth) float32: the batched convert_2_5D_to_3D.  One launch; `out`
+    and `z_root` may be buffers the caller owns."""
+    b = _label_batch(joints25d, "joints25d_to_3d")
+    jp, sp = _label_ptr(joints25d, (b, 21, 3), "joints25d_to_3d joints25d"), _label_ptr(scale, (b,), "joints25d_to_3d scale")
+    kp, zp = _label_ptr(K, (b, 3, 3), "joints25d_to_3d K"), _label_ptr(z_root_calc, (b,), "joints25d_to_3d z_root_calc")
+    out = torch.empty((b, 21, 3), device=joints25d.device, dtype=torch.float32) if out is None else out
+    z_root = torch.empty((b,), device=joints25d.device, dtype=torch.float32) if z_root is None else z_root
+    _launch("joints25d_to_3d", "peclr_joints25d_to_3d", jp, sp, kp, zp, b, _label_ptr(out, (b, 21, 3), "joints25d_to_3d out"),
+            _label_ptr(z_root, (b,), "joints25d_to_3d z_root"), _stream(), nbytes=4 * b * (63 + 1 + 9 + 63 + 1))
+    return out, z_root
+
+
+def supervised_labels(K: torch.Tensor, joints3d: torch.Tensor, T: torch.Tensor, use_palm: bool = False,
+                      joints_raw: Optional[torch.Tensor] = None):
+    """K [B,3,3], joints3d [B,21,3] float32, T [B,3,3] float64 forward matrices, joints_raw [B,21,3] float32 or None -> dict of
+    float32 tensors: joints, K (= fl32(T) @ K), scale, joints3D, joints3D_recreated, joints_raw, T.  One launch."""
+    b = _label_batch(joints3d, "supervised_labels")
+    kp, jp = _label_ptr(K, (b, 3, 3), "supervised_labels K"), _label_ptr(joints3d, (b, 21, 3), "supervised_labels joints3d")
+    tp = _label_ptr(T, (b, 3, 3), "supervised_labels T", torch.float64)
+    rp = _label_ptr(joints_raw, (b, 21, 3), "supervised_labels joints_raw")
+    z = dict(device=joints3d.device, dtype=torch.float32)
+    out = {"joints": torch.empty((b, 21, 3), **z), "K": torch.empty((b, 3, 3), **z), "scale": torch.empty((b,), **z),
+           "joints3D": torch.empty((b, 21, 3), **z), "joints3D_recreated": torch.empty((b, 21, 3), **z),
+           "joints_raw": torch.empty((b, 21, 3), **z), "T": torch.empty((b, 3, 3), **z)}
+    _launch("supervised_labels", "peclr_supervised_labels", kp, jp, tp, rp, b, int(bool(use_palm)),
+            *(out[k].data_ptr() for k in ("joints", "K", "scale", "joints3D", "joints3D_recreated", "joints_raw", "T")), _stream(),
+            nbytes=4 * b * (9 + 63 + 18 + 4 * 63 + 1 + 18))
+    return out

@@ -260,12 +260,15 @@ class TwoViewAugmenter:
         origin_y = max(center_y - side + jitter[1], 0)
         return origin_x, origin_y, int(2 * side), center_x - side - origin_x, center_y - side - origin_y
 
-    def sample_view(self, joints25d: Tensor, image_hw: Tuple[int, int]) -> Dict:
+    def sample_view(self, joints25d: Tensor, image_hw: Tuple[int, int], always_crop: bool = True) -> Dict:
+        """always_crop=False is the supervised mode (`transform_sample` without an override jitter): the crop happens only
+        with the `crop` flag; without it the window is the whole image and neither the margin nor the jitter is drawn."""
         f, p, rng = self.flags, self.params, self.rng
         h_img, w_img = image_hw
         joints = joints25d.detach().to("cpu", torch.float32).clone()
         view: Dict = {"angle": None, "h": None, "s": None, "a": None, "b": None, "blur_flag": False, "minv": None,
-                      "sobel": False, "cut_out": None, "sigma": None, "ksize": None, "noise": False, "color_drop": False}
+                      "sobel": False, "cut_out": None, "sigma": None, "ksize": None, "noise": False, "color_drop": False,
+                      "rot": None}
         # augmentations the reference applies first, each decided by one bit drawn only when its flag is on
         if f.get("sobel_filter") and rng.getrandbits(1):
             view["sobel"] = True
@@ -283,7 +286,9 @@ class TwoViewAugmenter:
             hom = joints.double()
             hom[:, -1] = 1.0
             joints[:, :-1] = (hom @ torch.tensor(rot, dtype=torch.float64).T).float()
-            view["angle"], view["minv"] = angle, _invert_affine(rot)
+            view["angle"], view["minv"], view["rot"] = angle, _invert_affine(rot), rot
+        if not always_crop and not f.get("crop"):
+            return self._finish_view(view, jitter_x=0, jitter_y=0, crop_margin_scale=None, origin=None, crop=(0, 0, w_img, h_img))
         # hybrid2 always crops: with the crop flag off it passes a zero jitter (data_set.py:359-364)
         if f.get("random_crop"):
             margin = rng.uniform(p["crop_margin_range"][0], p["crop_margin_range"][1])
@@ -299,7 +304,12 @@ class TwoViewAugmenter:
         if cw <= 0 or ch <= 0:
             raise ValueError(f"empty crop window (origin {ox},{oy}, side {side}) for a {w_img}x{h_img} image: "
                              "the reference's cv2.resize fails on it too")
-        view.update(jitter_x=jx, jitter_y=jy, crop_margin_scale=margin, crop=(x0, y0, cw, ch))
+        return self._finish_view(view, jitter_x=jx, jitter_y=jy, crop_margin_scale=margin, origin=(ox, oy), crop=(x0, y0, cw, ch))
+
+    def _finish_view(self, view: Dict, **window) -> Dict:
+        """The draws that follow the crop window."""
+        f, p, rng = self.flags, self.params, self.rng
+        view.update(window)
         if f.get("color_jitter"):
             view["h"] = rng.uniform(*p["hue_factor_range"])
             view["s"] = rng.uniform(*p["sat_factor_range"])

@@ -1,0 +1,251 @@
+// The label side of a supervised sample (reference src/data_loader/utils.py: convert_to_2_5D, convert_2_5D_to_3D,
+// get_root_depth, get_zroot_constraint_terms; src/data_loader/data_set.py: prepare_supervised_sample, move_wrist_to_palm), for a
+// batch, one launch per entry point.
+//
+//   one wave per sample, LS samples per workgroup; lane j < 21 owns joint j (its three coordinates).  What a sample has once --
+//   the bone scale, the inverse camera matrix, the root depth, K' = T K -- EVERY lane computes for itself from the sample's K
+//   and its joints 0 and 2 (loads that the whole wave shares; a few dozen float64 operations): no lane hands a value to
+//   another, so there is no LDS, no barrier, no shuffle and no atomic.  A sample's outputs depend on that sample alone.
+//
+// Arithmetic: every stage is evaluated in float64 from float32 inputs and each emitted tensor is rounded to float32 once.  A
+// stage that follows reads the ROUNDED tensor, as the reference's chain reads its float32 tensors: the re-creation reads the
+// float32 joints, scale and K'.  Contraction is off: a product and a sum are two roundings, as in the NumPy restatement the
+// tests compare with.
+#include "common.hpp"
+
+#pragma clang fp contract(off)
+
+namespace peclr {
+namespace {
+
+constexpr int LS = 4;  // samples (waves) per workgroup
+constexpr int LT = LS * kWave;
+constexpr int LJ = 21;
+constexpr int kParent = 0, kChild = 2;  // wrist, index MCP (reference data_loader/utils.py:15-16)
+
+__device__ __forceinline__ void load3(const float* __restrict__ p, double out[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[c] = (double)p[c];
+}
+__device__ __forceinline__ void load9(const float* __restrict__ p, double out[9]) {
+#pragma unroll
+    for (int c = 0; c < 9; ++c) out[c] = (double)p[c];
+}
+// torch.clamp(x, min = lo): a NaN stays a NaN
+__device__ __forceinline__ double clamp_min(double x, double lo) { return x < lo ? lo : x; }
+
+// convert_to_2_5D: the length of the wrist -- index-MCP bone
+__device__ __forceinline__ double bone_scale(const double w[3], const double c[3]) {
+    const double d0 = c[0] - w[0], d1 = c[1] - w[1], d2 = c[2] - w[2];
+    return sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+}
+// convert_to_2_5D for one joint p: (K p) / z in x and y, the depth relative to the wrist over the bone length
+__device__ __forceinline__ void to_25d(const double K[9], const double p[3], const double w[3], double scale, double out[3]) {
+    out[0] = (K[0] * p[0] + K[1] * p[1] + K[2] * p[2]) / p[2];
+    out[1] = (K[3] * p[0] + K[4] * p[1] + K[5] * p[2]) / p[2];
+    out[2] = (p[2] - w[2]) / scale;
+}
+// torch.inverse(K) for a general 3 x 3 matrix: adjugate over determinant
+__device__ __forceinline__ void inverse3(const double K[9], double inv[9]) {
+    const double c0 = K[4] * K[8] - K[5] * K[7], c1 = K[3] * K[8] - K[5] * K[6], c2 = K[3] * K[7] - K[4] * K[6];
+    const double det = K[0] * c0 - K[1] * c1 + K[2] * c2;
+    inv[0] = c0 / det;
+    inv[1] = (K[2] * K[7] - K[1] * K[8]) / det;
+    inv[2] = (K[1] * K[5] - K[2] * K[4]) / det;
+    inv[3] = (K[5] * K[6] - K[3] * K[8]) / det;
+    inv[4] = (K[0] * K[8] - K[2] * K[6]) / det;
+    inv[5] = (K[2] * K[3] - K[0] * K[5]) / det;
+    inv[6] = c2 / det;
+    inv[7] = (K[1] * K[6] - K[0] * K[7]) / det;
+    inv[8] = (K[0] * K[4] - K[1] * K[3]) / det;
+}
+// get_root_depth with get_zroot_constraint_terms: n the 2.5D wrist, m the 2.5D index MCP, C = 1
+__device__ __forceinline__ double root_depth(const double inv[9], const double n[3], const double m[3]) {
+    const double xn = inv[0] * n[0] + inv[1] * n[1] + inv[2], yn = inv[3] * n[0] + inv[4] * n[1] + inv[5];
+    const double xm = inv[0] * m[0] + inv[1] * m[1] + inv[2], ym = inv[3] * m[0] + inv[4] * m[1] + inv[5];
+    const double zn = n[2], zm = m[2];
+    const double a = (xn - xm) * (xn - xm) + (yn - ym) * (yn - ym);
+    const double b = 2.0 * (zn * (xn * xn + yn * yn - xn * xm - yn * ym) + zm * (xm * xm + ym * ym - xn * xm - yn * ym));
+    const double c = (xn * zn - xm * zm) * (xn * zn - xm * zm) + (yn * zn - ym * zm) * (yn * zn - ym * zm) +
+                     (zn - zm) * (zn - zm) - 1.0;
+    return 0.5 * (-b + sqrt(clamp_min(b * b - 4.0 * a * c, 1e-6))) / clamp_min(a, 1e-6);
+}
+// convert_2_5D_to_3D for one joint
+__device__ __forceinline__ void to_3d(const double inv[9], const double p[3], double z_root, double scale, double out[3]) {
+    const double z = (p[2] + z_root) * scale;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) out[r] = (inv[3 * r] * p[0] + inv[3 * r + 1] * p[1] + inv[3 * r + 2]) * z;
+}
+__device__ __forceinline__ void store3(float* __restrict__ p, const double v[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) p[c] = (float)v[c];
+}
+// what a later stage reads of an emitted tensor: the float32 value
+__device__ __forceinline__ void round3(double v[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = (double)(float)v[c];
+}
+
+__global__ __launch_bounds__(LT) void joints3d_to_25d_kernel(const float* __restrict__ K, const float* __restrict__ j3d, int B,
+                                                             float* __restrict__ j25d, float* __restrict__ scale) {
+    const int lane = threadIdx.x % kWave;
+    const int b = blockIdx.x * LS + threadIdx.x / kWave;
+    if (b >= B || lane >= LJ) return;
+    const float* J = j3d + (size_t)b * LJ * 3;
+    double k[9], p[3], w[3], c[3], out[3];
+    load9(K + (size_t)b * 9, k);
+    load3(J + lane * 3, p);
+    load3(J + kParent * 3, w);
+    load3(J + kChild * 3, c);
+    const double s = bone_scale(w, c);
+    to_25d(k, p, w, s, out);
+    store3(j25d + ((size_t)b * LJ + lane) * 3, out);
+    if (lane == 0) scale[b] = (float)s;
+}
+
+__global__ __launch_bounds__(LT) void joints25d_to_3d_kernel(const float* __restrict__ j25d, const float* __restrict__ scale,
+                                                             const float* __restrict__ K, const float* __restrict__ z_root_calc,
+                                                             int B, float* __restrict__ j3d, float* __restrict__ z_root) {
+    const int lane = threadIdx.x % kWave;
+    const int b = blockIdx.x * LS + threadIdx.x / kWave;
+    if (b >= B || lane >= LJ) return;
+    const float* J = j25d + (size_t)b * LJ * 3;
+    double k[9], inv[9], p[3], n[3], m[3], out[3];
+    load9(K + (size_t)b * 9, k);
+    load3(J + lane * 3, p);
+    load3(J + kParent * 3, n);
+    load3(J + kChild * 3, m);
+    inverse3(k, inv);
+    const double zr = root_depth(inv, n, m);
+    to_3d(inv, p, z_root_calc ? (double)z_root_calc[b] : zr, (double)scale[b], out);
+    store3(j3d + ((size_t)b * LJ + lane) * 3, out);
+    if (lane == 0 && z_root) z_root[b] = (float)zr;
+}
+
+// T applied to (u, v, 1); the depth stays
+__device__ __forceinline__ void apply_t(const double T[9], double p[3]) {
+    const double u = T[0] * p[0] + T[1] * p[1] + T[2], v = T[3] * p[0] + T[4] * p[1] + T[5];
+    p[0] = u;
+    p[1] = v;
+}
+
+__global__ __launch_bounds__(LT) void supervised_labels_kernel(const float* __restrict__ K, const float* __restrict__ j3d,
+                                                               const double* __restrict__ T, const float* __restrict__ raw_in,
+                                                               int B, int use_palm, float* __restrict__ joints,
+                                                               float* __restrict__ k_out, float* __restrict__ scale_out,
+                                                               float* __restrict__ j3d_out, float* __restrict__ recreated,
+                                                               float* __restrict__ raw_out, float* __restrict__ t_out) {
+    const int lane = threadIdx.x % kWave;
+    const int b = blockIdx.x * LS + threadIdx.x / kWave;
+    if (b >= B || lane >= LJ) return;
+    const size_t at = ((size_t)b * LJ + lane) * 3;
+    const float* J = j3d + (size_t)b * LJ * 3;
+    const float* R = raw_in ? raw_in + (size_t)b * LJ * 3 : J;
+    double k[9], t[9], tf[9], kp[9];
+    load9(K + (size_t)b * 9, k);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        t[i] = T[(size_t)b * 9 + i];
+        tf[i] = (double)(float)t[i];  // torch.Tensor(transformation_matrix)
+    }
+    // K' = fl32(T) @ K, rounded: what the stages below read
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            kp[3 * r + c] = (double)(float)(tf[3 * r] * k[c] + tf[3 * r + 1] * k[3 + c] + tf[3 * r + 2] * k[6 + c]);
+
+    double p[3], w[3], c[3], raw[3];
+    load3(J + lane * 3, p);
+    load3(J + kParent * 3, w);
+    load3(J + kChild * 3, c);
+    load3(R + lane * 3, raw);
+
+    // joints of this lane's joint, of the wrist and of the index MCP (the root depth needs the last two), and the scale
+    double mine[3], n[3], m[3], s;
+    if (use_palm) {
+        // move_wrist_to_palm, then convert_to_2_5D on the moved (float32) joints with K'
+        double r0[3], r2[3];
+        load3(R + kParent * 3, r0);
+        load3(R + kChild * 3, r2);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            w[i] = (double)(float)((w[i] + c[i]) / 2.0);
+            if (lane == kParent) {
+                p[i] = w[i];
+                raw[i] = (r0[i] + r2[i]) / 2.0;
+            }
+        }
+        s = bone_scale(w, c);
+        to_25d(kp, p, w, s, mine);
+        to_25d(kp, w, w, s, n);
+        to_25d(kp, c, w, s, m);
+    } else {
+        // convert_to_2_5D with K, then the augmentation matrix
+        s = bone_scale(w, c);
+        to_25d(k, p, w, s, mine);
+        to_25d(k, w, w, s, n);
+        to_25d(k, c, w, s, m);
+        apply_t(t, mine);
+        apply_t(t, n);
+        apply_t(t, m);
+    }
+    store3(joints + at, mine);
+    store3(j3d_out + at, p);
+    store3(raw_out + at, raw);
+    if (lane == 0) scale_out[b] = (float)s;
+    if (lane < 9) {
+        double k_lane = 0.0, t_lane = 0.0;  // (selected by compares: a lane-indexed read would put the matrices in scratch memory)
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            k_lane = lane == i ? kp[i] : k_lane;
+            t_lane = lane == i ? tf[i] : t_lane;
+        }
+        k_out[(size_t)b * 9 + lane] = (float)k_lane;
+        t_out[(size_t)b * 9 + lane] = (float)t_lane;
+    }
+
+    // convert_2_5D_to_3D on the emitted joints, scale and K'
+    round3(mine);
+    round3(n);
+    round3(m);
+    s = (double)(float)s;
+    double inv[9], out[3];
+    inverse3(kp, inv);
+    to_3d(inv, mine, root_depth(inv, n, m), s, out);
+    store3(recreated + at, out);
+}
+
+inline int grid_of(int B) { return (B + LS - 1) / LS; }
+
+}  // namespace
+}  // namespace peclr
+
+using namespace peclr;
+
+extern "C" int peclr_joints3d_to_25d(const float* K, const float* joints3d, int B, float* joints25d, float* scale,
+                                     peclr_stream_t stream) {
+    if (B <= 0 || !K || !joints3d || !joints25d || !scale) return PECLR_ERR_NULL;
+    hipLaunchKernelGGL(joints3d_to_25d_kernel, dim3(grid_of(B)), dim3(LT), 0, static_cast<hipStream_t>(stream), K, joints3d, B,
+                       joints25d, scale);
+    return launch_status();
+}
+
+extern "C" int peclr_joints25d_to_3d(const float* joints25d, const float* scale, const float* K, const float* z_root_calc, int B,
+                                     float* joints3d, float* z_root, peclr_stream_t stream) {
+    if (B <= 0 || !joints25d || !scale || !K || !joints3d) return PECLR_ERR_NULL;
+    hipLaunchKernelGGL(joints25d_to_3d_kernel, dim3(grid_of(B)), dim3(LT), 0, static_cast<hipStream_t>(stream), joints25d, scale, K,
+                       z_root_calc, B, joints3d, z_root);
+    return launch_status();
+}
+
+extern "C" int peclr_supervised_labels(const float* K, const float* joints3d, const double* T, const float* joints_raw, int B,
+                                       int use_palm, float* joints, float* k_out, float* scale, float* joints3d_out,
+                                       float* joints3d_recreated, float* joints_raw_out, float* t_out, peclr_stream_t stream) {
+    if (B <= 0 || !K || !joints3d || !T) return PECLR_ERR_NULL;
+    if (!joints || !k_out || !scale || !joints3d_out || !joints3d_recreated || !joints_raw_out || !t_out) return PECLR_ERR_NULL;
+    hipLaunchKernelGGL(supervised_labels_kernel, dim3(grid_of(B)), dim3(LT), 0, static_cast<hipStream_t>(stream), K, joints3d, T,
+                       joints_raw, B, use_palm ? 1 : 0, joints, k_out, scale, joints3d_out, joints3d_recreated, joints_raw_out,
+                       t_out);
+    return launch_status();
+}

@@ -174,6 +174,7 @@ class PoseEvaluator:
         self._cursor = torch.zeros((2, 2), dtype=torch.int32, **z)            # per stream {rows filled, ticket}
         self._counts = torch.zeros((2, NUM_JOINTS, len(self.thresholds)), dtype=torch.int64, **z)
         self._asked = [0, 0]
+        self._lifted = {}                         # update_25d's 3D predictions and root depths, per batch size
 
     def reset(self) -> "PoseEvaluator":
         """Forget everything fed so far (stream-ordered fills, no synchronisation)."""
@@ -198,6 +199,23 @@ class PoseEvaluator:
                         status=self._status[0], dist=self._dist, dist_aligned=self._dist_al, cursor=self._cursor[0],
                         want_transform=False)
         self._asked[0] += pred.shape[0]          # only once the launch is enqueued: a refused call asks for nothing
+
+    def update_25d(self, pred25d: Tensor, scale: Tensor, K: Tensor, gt3d: Tensor) -> None:
+        """Score one batch of 2.5D predictions, as the reference's evaluate() does: pred25d [B,21,3], scale [B], K [B,3,3]
+        float32 HIP tensors are lifted with convert_2_5D_to_3D (`peclr_joints25d_to_3d`: one launch into a buffer this
+        evaluator owns, one per batch size) and the result is scored against gt3d [B,21,3] by update()'s launch.  Same
+        guarantees and exceptions as update(): no host synchronisation, capturable into a hipGraph, a refused call leaves
+        the evaluator as it was."""
+        for t, what in ((pred25d, "pred25d"), (scale, "scale"), (K, "K"), (gt3d, "gt3d")):
+            _need_hip(t, f"PoseEvaluator.update_25d {what}")
+        b = pred25d.shape[0]
+        self._room(0, b)
+        if b not in self._lifted:
+            self._lifted[b] = (torch.empty((b, NUM_JOINTS, 3), dtype=torch.float32, device=self.device),
+                               torch.empty((b,), dtype=torch.float32, device=self.device))
+        out, z_root = self._lifted[b]
+        _capi.joints25d_to_3d(pred25d, scale, K, out=out, z_root=z_root)
+        self.update(out, gt3d)
 
     def update_2d(self, kp2d_pred: Tensor, kp2d_gt: Tensor) -> None:
         """The optional 2D stream: kp2d_pred, kp2d_gt [B,21,2] (or [B,21,3], z ignored) feed Mean_EPE_2D / Median_EPE_2D through
