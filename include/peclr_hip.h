@@ -800,6 +800,48 @@ int peclr_supervised_labels(const float* K, const float* joints3d, const double*
                             float* joints, float* k_out, float* scale, float* joints3d_out, float* joints3d_recreated,
                             float* joints_raw_out, float* t_out, peclr_stream_t stream);
 
+/* The supervised losses of the 2.5D pose model with their gradients (reference src/models/utils.py: cal_l1_loss, cal_3d_loss,
+ * through convert_2_5D_to_3D / get_root_depth), csrc/pose_loss.hip; host side: peclr_amd/pose_loss.py.  Inputs and emitted
+ * losses / gradients are float32 and contiguous; the workspaces between forward and backward are float64.  No host
+ * synchronisation, no atomics, nothing kept in the library between calls -- safe inside a hipGraph capture.  Everything is
+ * evaluated in float64 and each float32 output is rounded once; sums run in a fixed order (a butterfly over a wave per sample,
+ * then one workgroup over the samples), so the result depends on nothing but the inputs.  Argument errors (B <= 0, a NULL
+ * pointer that is not marked nullable) are -1.
+ *
+ * peclr_pose_loss -- TWO launches on `stream` (per-sample partial sums and gradients; the fold):
+ *   in   pred [B][21][3]        the 2.5D prediction (u, v, root-relative scale-normalised depth)
+ *        joints [B][21][3]      the true 2.5D joints;  joints3d [B][21][3] the true 3D joints
+ *        scale [B], K [B][3][3] bone scale and camera matrix of the sample
+ *                               (one of joints / joints3d may be NULL, K with joints3d: the three L1 losses, or the 3D loss, are
+ *                               then left out -- nothing is read for them, their losses and gradients are 0)
+ *        joints_valid [B][21]   (nullable: ones) weight of a joint, 0 / 1 in the reference
+ *        z_root_calc [B]        (nullable) a root depth to lift with instead of the closed form of pred's joints 0 and 2
+ *   out  losses [4]             loss_2d   = sum valid (|du| + |dv|) / (2 sum valid)
+ *                               loss_z    = sum valid |dz| / sum valid
+ *                               loss_z_unscaled = sum scale[b] valid |dz| / sum valid
+ *                               loss_3d   = sum valid |joints25d_to_3d(pred, scale, K, z_root_calc) - joints3d|_1 / (3 sum valid)
+ *                               (sum valid = 0: NaN, the reference's 0 / 0)
+ *        inv_valid [1] float64  1 / sum valid
+ *   workspaces, float64, read by peclr_pose_loss_bwd:
+ *        partials [B][5]        per sample: sum valid, sum valid |d uv|, sum valid |dz|, scale x the third, sum valid |d 3D|
+ *        g_l1 [B][21][3]        valid x sign(pred - joints), sign(0) = 0
+ *        g_3d [B][21][3]        d (sum valid |d 3D|) / d pred: through the lift of the joint itself and, without z_root_calc,
+ *                               through the root depth of joints 0 and 2.  torch.clamp's backward at both clamp(min = 1e-6):
+ *                               no gradient through a clamped leading coefficient or discriminant (a value AT the minimum
+ *                               passes it), while -b / (2 clamp(a)) keeps its gradient with respect to b
+ *        g_zroot [B]            (nullable; written only with z_root_calc) d (sum valid |d 3D|) / d z_root_calc
+ * peclr_pose_loss_bwd -- ONE launch:
+ *   in   grad_losses [4]        upstream gradients of the four losses, on the device
+ *        g_l1, g_3d, g_zroot (nullable unless grad_z_root_calc is given), scale, inv_valid: as above
+ *   out  grad_pred [B][21][3]   = (grad_losses[0] / 2 on u, v; grad_losses[1] + grad_losses[2] scale[b] on z) g_l1 / sum valid
+ *                                 + grad_losses[3] / 3 g_3d / sum valid
+ *        grad_z_root_calc [B]   (nullable) = grad_losses[3] / 3 g_zroot / sum valid                                          */
+int peclr_pose_loss(const float* pred, const float* joints, const float* joints3d, const float* scale, const float* K,
+                    const float* joints_valid, const float* z_root_calc, int B, double* partials, double* g_l1, double* g_3d,
+                    double* g_zroot, float* losses, double* inv_valid, peclr_stream_t stream);
+int peclr_pose_loss_bwd(const float* grad_losses, const double* g_l1, const double* g_3d, const double* g_zroot, const float* scale,
+                        const double* inv_valid, int B, float* grad_pred, float* grad_z_root_calc, peclr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

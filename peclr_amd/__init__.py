@@ -8,6 +8,7 @@ from .augment import RaggedImages, TwoViewAugmenter
 from .config import Config, hybrid2_config
 from .module import BaseModel, Hybrid2Model, SimCLR, get_model
 from .pose_eval import PoseEvaluator, auc_joints, epe_statistics, pck_curves, procrustes_transform
+from .pose_loss import PoseLoss, l1_loss, loss_3d, pose_losses
 from .port import (get_encoder_state_dict, get_latest_checkpoint, peclr_to_torchvision, restore_model,
                    save_checkpoint)
 from .supervised import SupervisedAugmenter, joints3d_to_25d, joints25d_to_3d, root_depth
@@ -16,4 +17,5 @@ from .trainer import Trainer
 __all__ = ["Config", "hybrid2_config", "BaseModel", "SimCLR", "Hybrid2Model", "get_model",
            "peclr_to_torchvision", "get_encoder_state_dict", "get_latest_checkpoint", "save_checkpoint", "restore_model",
            "Trainer", "TwoViewAugmenter", "RaggedImages", "epe_statistics", "procrustes_transform", "pck_curves", "auc_joints",
-           "PoseEvaluator", "SupervisedAugmenter", "joints3d_to_25d", "joints25d_to_3d", "root_depth"]
+           "PoseEvaluator", "SupervisedAugmenter", "joints3d_to_25d", "joints25d_to_3d", "root_depth",
+           "pose_losses", "l1_loss", "loss_3d", "PoseLoss"]

@@ -127,6 +127,8 @@ SIGNATURES = {
     "peclr_joints3d_to_25d": (c_int, [_P, _P, c_int, _P, _P, _P]),
     "peclr_joints25d_to_3d": (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P]),
     "peclr_supervised_labels": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "peclr_pose_loss": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "peclr_pose_loss_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, _P, _P, _P]),
 }
 
 
@@ -1675,3 +1677,48 @@ def supervised_labels(K: torch.Tensor, joints3d: torch.Tensor, T: torch.Tensor, 
             *(out[k].data_ptr() for k in ("joints", "K", "scale", "joints3D", "joints3D_recreated", "joints_raw", "T")), _stream(),
             nbytes=4 * b * (9 + 63 + 18 + 4 * 63 + 1 + 18))
     return out
+
+
+# ------------------------------------------------------------------ supervised pose losses (peclr_amd/pose_loss.py)
+def pose_loss(pred: torch.Tensor, joints: Optional[torch.Tensor], joints3d: Optional[torch.Tensor], scale: torch.Tensor,
+              K: Optional[torch.Tensor], joints_valid: Optional[torch.Tensor] = None, z_root_calc: Optional[torch.Tensor] = None):
+    """pred, joints, joints3d [B,21,3], scale [B], K [B,3,3] float32 (joints_valid [B,21,1] or None for ones; z_root_calc [B]
+    or None for the closed-form root depth) -> (losses [4] float32: loss_2d, loss_z, loss_z_unscaled, loss_3d; the float64
+    workspaces `pose_loss_bwd` reads: g_l1, g_3d [B,21,3], g_zroot [B] or None, inv_valid [1]).  The forward launch pair.
+    joints = None leaves the three L1 losses out (they are 0), joints3d = K = None the 3D loss."""
+    b = _label_batch(pred, "pose_loss")
+    if (joints is None and joints3d is None) or (joints3d is None) != (K is None) or (joints3d is None and z_root_calc is not None):
+        raise PeclrHipError("pose_loss: needs joints, or joints3d with K (z_root_calc only with them)")
+    pp, jp = _label_ptr(pred, (b, 21, 3), "pose_loss pred"), _label_ptr(joints, (b, 21, 3), "pose_loss joints")
+    j3p, sp = _label_ptr(joints3d, (b, 21, 3), "pose_loss joints3d"), _label_ptr(scale, (b,), "pose_loss scale")
+    kp, vp = _label_ptr(K, (b, 3, 3), "pose_loss K"), _label_ptr(joints_valid, (b, 21, 1), "pose_loss joints_valid")
+    zp = _label_ptr(z_root_calc, (b,), "pose_loss z_root_calc")
+    z = dict(device=pred.device, dtype=torch.float64)
+    partials, g_l1, g_3d = torch.empty((b, 5), **z), torch.empty((b, 21, 3), **z), torch.empty((b, 21, 3), **z)
+    g_zroot = torch.empty((b,), **z) if z_root_calc is not None else None
+    inv_valid = torch.empty((1,), **z)
+    losses = torch.empty((4,), device=pred.device, dtype=torch.float32)
+    _launch("pose_loss", "peclr_pose_loss", pp, jp, j3p, sp, kp, vp, zp, b, partials.data_ptr(), g_l1.data_ptr(), g_3d.data_ptr(),
+            None if g_zroot is None else g_zroot.data_ptr(), losses.data_ptr(), inv_valid.data_ptr(), _stream(),
+            nbytes=4 * b * (3 * 63 + 1 + 9 + 21 + 1) + 8 * b * (2 * 5 + 2 * 63 + 1))
+    return losses, g_l1, g_3d, g_zroot, inv_valid
+
+
+def pose_loss_bwd(grad_losses: torch.Tensor, g_l1: torch.Tensor, g_3d: torch.Tensor, g_zroot: Optional[torch.Tensor],
+                  scale: torch.Tensor, inv_valid: torch.Tensor, want_z_root: bool = False):
+    """grad_losses [4] float32 on the device and what `pose_loss` left -> (grad_pred [B,21,3] float32, grad_z_root_calc [B]
+    float32 or None).  One launch, no host read."""
+    b = _label_batch(g_l1, "pose_loss_bwd")
+    up = _label_ptr(grad_losses, (4,), "pose_loss_bwd grad_losses")
+    lp = _label_ptr(g_l1, (b, 21, 3), "pose_loss_bwd g_l1", torch.float64)
+    tp = _label_ptr(g_3d, (b, 21, 3), "pose_loss_bwd g_3d", torch.float64)
+    zp = _label_ptr(g_zroot, (b,), "pose_loss_bwd g_zroot", torch.float64)
+    sp = _label_ptr(scale, (b,), "pose_loss_bwd scale")
+    ip = _label_ptr(inv_valid, (1,), "pose_loss_bwd inv_valid", torch.float64)
+    if want_z_root and g_zroot is None:
+        raise PeclrHipError("pose_loss_bwd: the gradient of z_root_calc needs the forward's g_zroot")
+    grad_pred = torch.empty((b, 21, 3), device=g_l1.device, dtype=torch.float32)
+    grad_z = torch.empty((b,), device=g_l1.device, dtype=torch.float32) if want_z_root else None
+    _launch("pose_loss_bwd", "peclr_pose_loss_bwd", up, lp, tp, zp, sp, ip, b, grad_pred.data_ptr(),
+            None if grad_z is None else grad_z.data_ptr(), _stream(), nbytes=4 * b * (63 + 2) + 8 * b * (2 * 63 + 1))
+    return grad_pred, grad_z
