@@ -739,6 +739,42 @@ int peclr_pose_head_f32(const float* feat, int B, int n_feat, const float* fc_w,
                         const double* T1, double* T2, int S, const double* scale, double* fh, int* status,
                         peclr_stream_t stream);
 
+/* The same head in train mode -- BatchNorm1d on batch statistics, running statistics updated on the device -- and its exact
+ * backward (csrc/pose_train.hip; host side: peclr_amd/pose.py, PoseHeadTrain).  fp32 with the batch reductions of BatchNorm
+ * in float64, every reduction in a fixed order, no
+ * atomics, no host synchronisation; 2 <= B <= PECLR_POSE_TRAIN_MAX_BATCH, anything else is PECLR_ERR_SHAPE before a launch.
+ * feat, fc_w, fc_b, mlp (here the running statistics are written), K, k_per_sample, eps, out64, kp3d as peclr_pose_head_f32.
+ *
+ * peclr_pose_head_train_fwd_f32 -- FOUR launches on `stream`: fc + geometry + the detached closed-form root depth per sample;
+ *   Linear + BatchNorm + LeakyReLU twice, each workgroup owning 4 hidden units over all B rows; Linear(128, 1) + kp3d per sample.
+ *   momentum1 / momentum2: running = (1 - momentum) running + momentum batch (the variance unbiased); nbt1 / nbt2: the two
+ *   num_batches_tracked (int64, += 1).  Out: out64 [B][64], kp3d [B][21][3], zroot [B] (the refined root depth) and
+ *   save [PECLR_POSE_TRAIN_SAVE_FLOATS(B)], 16-byte aligned, which the backward reads: x [B][64] (the MLP input), p1, h1, p2,
+ *   h2 [B][128] each (the Linear outputs and the activations), per BatchNorm mean [128] and invstd [128] in float64 (the backward
+ *   forms xhat from p without another rounding), ku [B][21][3] (kp3d_unnorm).
+ * peclr_pose_head_train_bwd_f32 -- SIX launches (five when d_feat is NULL): dzroot per sample; the two column-owning blocks in
+ *   reverse (LeakyReLU by the sign of its input, 0 on the slope side; BatchNorm train backward; dW, db, dgamma, dbeta); the
+ *   geometry back to the fc output; dWfc / dbfc by slices of 64 columns over all rows; dfeat.  g_kp3d [B][21][3], g_out64 [B][64],
+ *   g_zroot [B]: the upstream gradients, each may be NULL (zeros).  ws [PECLR_POSE_TRAIN_WS_FLOATS(B)], 16-byte aligned: dp2, dp1
+ *   [B][128] (gradients at the two Linear outputs), do [B][64] (gradient at the fc output), dzroot [B].  Out: d_feat [B][2048]
+ *   or NULL, d_fc_w [64][2048], d_fc_b [64], d_mlp: host array of PECLR_POSE_MLP_GRADS device pointers, the gradients of
+ *   zroot_ref.zroot_ref.{0.weight, 0.bias, 1.weight, 1.bias, 3.weight, 3.bias, 4.weight, 4.bias, 6.weight, 6.bias} (the two
+ *   biases in front of a BatchNorm get 0, which the sum of dp over the batch is exactly).  K gets no gradient.
+ * peclr_pose_head_train_launches: the number of launches of the forward (backward = 0) or of the backward. */
+#define PECLR_POSE_TRAIN_MAX_BATCH 1024
+#define PECLR_POSE_MLP_GRADS 10
+#define PECLR_POSE_TRAIN_SAVE_FLOATS(B) ((size_t)(B) * 639 + 1024)
+#define PECLR_POSE_TRAIN_WS_FLOATS(B) ((size_t)(B) * 321)
+int peclr_pose_head_train_fwd_f32(const float* feat, int B, int n_feat, const float* fc_w, const float* fc_b, float* const* mlp,
+                                  float bn_eps1, float bn_eps2, float momentum1, float momentum2, int64_t* nbt1, int64_t* nbt2,
+                                  const float* K, int k_per_sample, float eps, float* out64, float* kp3d, float* zroot, float* save,
+                                  peclr_stream_t stream);
+int peclr_pose_head_train_bwd_f32(const float* feat, int B, int n_feat, const float* fc_w, const float* const* mlp, const float* K,
+                                  int k_per_sample, const float* out64, const float* zroot, const float* save, const float* g_kp3d,
+                                  const float* g_out64, const float* g_zroot, float* ws, float* d_feat, float* d_fc_w, float* d_fc_b,
+                                  float* const* d_mlp, peclr_stream_t stream);
+int peclr_pose_head_train_launches(int backward, int want_d_feat);
+
 /* Scoring pose predictions (reference src/experiments/evaluation_utils.py: calculate_epe_statistics, calc_procrustes_transform,
  * get_pck_curves), csrc/pose_eval.hip; host side: peclr_amd/pose_eval.py.  One launch for a batch.
  *

@@ -123,6 +123,10 @@ SIGNATURES = {
     "peclr_pose_crop_u8": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P]),
     "peclr_pose_head_f32": (c_int, [_P, c_int, c_int, _P, _P, _P, c_float, c_float, _P, c_int, c_float, _P, _P, _P, _P, c_int,
                                     _P, _P, _P, _P]),
+    "peclr_pose_head_train_fwd_f32": (c_int, [_P, c_int, c_int, _P, _P, _P, c_float, c_float, c_float, c_float, _P, _P, _P, c_int,
+                                              c_float, _P, _P, _P, _P, _P]),
+    "peclr_pose_head_train_bwd_f32": (c_int, [_P, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "peclr_pose_head_train_launches": (c_int, [c_int, c_int]),
     "peclr_pose_eval": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, c_int, _P]),
     "peclr_joints3d_to_25d": (c_int, [_P, _P, c_int, _P, _P, _P]),
     "peclr_joints25d_to_3d": (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P]),
@@ -1546,6 +1550,83 @@ def pose_head(feat: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, mlp, b
             _ptr(scale, torch.float64, "pose_head scale"), fh.data_ptr() if fh is not None else None,
             _ptr(status, torch.int32, "pose_head status"), _stream(), nbytes=4 * b * (nf + 64 + 63 + 64) + 4 * 64 * nf)
     return out64, kp3d, T2, fh, status
+
+
+# ------------------------------------------------------------------ the same head in train mode, with its backward
+POSE_TRAIN_MAX_BATCH = 1024
+POSE_MLP_GRADS = 10   # zroot_ref.zroot_ref.{0.weight, 0.bias, 1.weight, 1.bias, 3.weight, 3.bias, 4.weight, 4.bias, 6.weight, 6.bias}
+_POSE_MLP_GRAD_OF = (0, 1, 2, 3, 6, 7, 8, 9, 12, 13)    # their positions among the 14 MLP tensors
+
+
+def pose_head_train_launches(backward: bool, want_d_feat: bool = True) -> int:
+    return lib().peclr_pose_head_train_launches(int(bool(backward)), int(bool(want_d_feat)))
+
+
+def _pose_train_args(what, feat, K, mlp):
+    if feat.dim() != 2:
+        raise PeclrHipError(f"{what}: features must be [B,2048], got {tuple(feat.shape)}")
+    b, nf = feat.shape
+    if b == 1:
+        raise ValueError(f"{what}: expected more than 1 value per channel when training, got input size {tuple(feat.shape)}")
+    if b > POSE_TRAIN_MAX_BATCH:
+        raise PeclrHipError(f"{what}: at most {POSE_TRAIN_MAX_BATCH} samples per call, got {b}")
+    if len(mlp) != POSE_MLP_TENSORS:
+        raise PeclrHipError(f"{what}: {POSE_MLP_TENSORS} MLP tensors expected, got {len(mlp)}")
+    fp = _ptr(feat, what=f"{what} features")
+    kp = _mat_ptr(K, b, torch.float32, "K", broadcast=True)
+    mlp_arr = (c_void_p * POSE_MLP_TENSORS)(*[_ptr(t, what=f"{what} MLP tensor") for t in mlp])
+    return b, nf, fp, kp, int(K.shape[0] != 1), mlp_arr
+
+
+def pose_head_train_fwd(feat: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, mlp, bn_eps, momentum, nbt, K: torch.Tensor,
+                        eps: float):
+    """The head in train mode: pooled features [B,2048], 2 <= B <= 1024 -> (out64 [B,64], kp3d [B,21,3], zroot [B], save: the
+    float32 workspace `pose_head_train_bwd` reads).  mlp, K, eps as `pose_head`; the running statistics among `mlp` and the
+    two int64 `nbt` (num_batches_tracked) are updated in place with `momentum` (one per BatchNorm1d).  Four launches, logged
+    as one EVENT_LOG entry whose `kernel` field says so."""
+    b, nf, fp, kp, per_sample, mlp_arr = _pose_train_args("pose_head_train_fwd", feat, K, mlp)
+    dev = feat.device
+    out64 = torch.empty((b, 64), device=dev, dtype=torch.float32)
+    kp3d = torch.empty((b, 21, 3), device=dev, dtype=torch.float32)
+    zroot = torch.empty((b,), device=dev, dtype=torch.float32)
+    save = torch.empty((b * 639 + 1024,), device=dev, dtype=torch.float32)
+    n = pose_head_train_launches(False)
+    _launch("pose_head_train_fwd", "peclr_pose_head_train_fwd_f32", fp, b, nf, _ptr(fc_w, what="pose_head_train_fwd fc weight"),
+            _ptr(fc_b, what="pose_head_train_fwd fc bias"), ctypes.cast(mlp_arr, c_void_p), float(bn_eps[0]), float(bn_eps[1]),
+            float(momentum[0]), float(momentum[1]), _ptr(nbt[0], torch.int64, "pose_head_train_fwd num_batches_tracked"),
+            _ptr(nbt[1], torch.int64, "pose_head_train_fwd num_batches_tracked"), kp, per_sample, float(eps), out64.data_ptr(),
+            kp3d.data_ptr(), zroot.data_ptr(), save.data_ptr(), _stream(), nbytes=4 * b * (nf + 64 + 63 + 1 + 2 * 639) + 4 * 64 * nf,
+            kernel=f"{n} launches")
+    return out64, kp3d, zroot, save
+
+
+def pose_head_train_bwd(feat: torch.Tensor, fc_w: torch.Tensor, mlp, K: torch.Tensor, out64: torch.Tensor, zroot: torch.Tensor,
+                        save: torch.Tensor, g_kp3d: Optional[torch.Tensor] = None, g_out64: Optional[torch.Tensor] = None,
+                        g_zroot: Optional[torch.Tensor] = None, want_d_feat: bool = True):
+    """Backward of `pose_head_train_fwd` from its inputs and outputs: upstream gradients g_kp3d [B,21,3], g_out64 [B,64],
+    g_zroot [B] (None = zeros) -> (d_feat [B,2048] or None, d_fc_w [64,2048], d_fc_b [64], the POSE_MLP_GRADS parameter
+    gradients in state_dict order, d_out [B,64]: the gradient at the fc output).  Six launches, five without d_feat, logged
+    as one EVENT_LOG entry whose `kernel` field says so."""
+    b, nf, fp, kp, per_sample, mlp_arr = _pose_train_args("pose_head_train_bwd", feat, K, mlp)
+    dev = feat.device
+    if tuple(save.shape) != (b * 639 + 1024,):
+        raise PeclrHipError(f"pose_head_train_bwd: save must be what pose_head_train_fwd returned for {b} samples")
+    z = dict(device=dev, dtype=torch.float32)
+    ws = torch.empty((b * 321,), **z)
+    d_feat = torch.empty((b, nf), **z) if want_d_feat else None
+    d_fc_w, d_fc_b = torch.empty((64, nf), **z), torch.empty((64,), **z)
+    d_mlp = [torch.empty_like(mlp[i]) for i in _POSE_MLP_GRAD_OF]
+    d_arr = (c_void_p * POSE_MLP_GRADS)(*[t.data_ptr() for t in d_mlp])
+    n = pose_head_train_launches(True, want_d_feat)
+    _launch("pose_head_train_bwd", "peclr_pose_head_train_bwd_f32", fp, b, nf, _ptr(fc_w, what="pose_head_train_bwd fc weight"),
+            ctypes.cast(mlp_arr, c_void_p), kp, per_sample, _label_ptr(out64, (b, 64), "pose_head_train_bwd out64"),
+            _label_ptr(zroot, (b,), "pose_head_train_bwd zroot"), _ptr(save, what="pose_head_train_bwd save"),
+            _label_ptr(g_kp3d, (b, 21, 3), "pose_head_train_bwd g_kp3d"), _label_ptr(g_out64, (b, 64), "pose_head_train_bwd g_out64"),
+            _label_ptr(g_zroot, (b,), "pose_head_train_bwd g_zroot"), ws.data_ptr(), None if d_feat is None else d_feat.data_ptr(),
+            d_fc_w.data_ptr(), d_fc_b.data_ptr(), ctypes.cast(d_arr, c_void_p), _stream(),
+            nbytes=4 * b * (nf * (2 if want_d_feat else 1) + 639 + 2 * 321 + 3 * 64) + 4 * 64 * nf * (3 if want_d_feat else 2),
+            kernel=f"{n} launches")
+    return d_feat, d_fc_w, d_fc_b, d_mlp, ws[b * 256:b * 320].view(b, 64)
 
 
 # ------------------------------------------------------------------ scoring pose predictions (peclr_amd/pose_eval.py)

@@ -12,12 +12,14 @@
 // The work is small (the head is ~0.13 MFLOP per image); the point is one launch per stage, no intermediate tensors and no
 // host round trip between the two passes.
 #include "common.hpp"
+#include "pose_head.hpp"
 #include "warp_u8.hpp"
 
 #pragma clang fp contract(off)  // products and sums round separately, as the host restatements do
 
 namespace peclr {
 namespace {
+using namespace pose_head;  // the stages shared with the training head (pose_train.hip)
 
 constexpr int CX = 64, CY = 4;  // crop: one thread per output pixel, consecutive lanes = consecutive x
 
@@ -58,13 +60,7 @@ __global__ __launch_bounds__(CX* CY) void pose_crop_kernel(const uint8_t* __rest
     o[0] = tab[px[0]], o[1] = tab[256 + px[1]], o[2] = tab[512 + px[2]];
 }
 
-// ---- head
-constexpr int HS = 4;          // samples per workgroup: one wave each for the per-sample stages
-constexpr int HT = HS * kWave;
-constexpr int NF = 2048, NO = 64, NH = 128, NJ = 21;
-constexpr int FC_PER_WAVE = NO / HS;  // fc outputs per wave
-constexpr int KV = NF / (4 * kWave);  // float4 loads per lane per feature row
-
+// ---- head (HS samples per workgroup and the sizes: pose_head.hpp)
 struct MlpParams {
     const float *w0, *b0, *g1, *be1, *rm1, *rv1, *w3, *b3, *g4, *be4, *rm4, *rv4, *w6, *b6;
     float eps1, eps4;
@@ -82,9 +78,6 @@ struct HeadSmem {
     float h1[HS][NH], h2[HS][NH];
     float zroot[HS];
 };
-
-__device__ __forceinline__ float max_nan(float eps, float v) { return v != v ? v : (v > eps ? v : eps); }  // torch.max: NaN wins
-__device__ __forceinline__ float leaky(float v) { return v > 0.f ? v : v * 0.01f; }
 
 // the eval-mode BatchNorm1d of torch's CPU kernel: invstd = 1 / sqrt(var + eps), alpha = invstd * weight, beta = bias - mean * alpha
 __device__ __forceinline__ void bn_coef(const float* g, const float* be, const float* rm, const float* rv, float eps, int i,
@@ -125,36 +118,7 @@ __global__ __launch_bounds__(HT) void pose_head_kernel(const float* __restrict__
         bn_coef(p.g4, p.be4, p.rm4, p.rv4, p.eps4, tid, sm.a4[tid], sm.c4[tid]);
     }
 
-    // fc: wave w owns outputs [16 w, 16 w + 16); lane l holds features 4 l + 256 j (j < 8) of every sample in registers
-    float4 f[HS][KV];
-#pragma unroll
-    for (int s = 0; s < HS; ++s) {
-        const bool ok = b0 + s < B;
-        const float4* row = reinterpret_cast<const float4*>(feat + (size_t)(ok ? b0 + s : 0) * NF);
-#pragma unroll
-        for (int j = 0; j < KV; ++j) f[s][j] = ok ? row[lane + kWave * j] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    for (int oo = 0; oo < FC_PER_WAVE; ++oo) {
-        const int o = wave * FC_PER_WAVE + oo;
-        const float4* wr = reinterpret_cast<const float4*>(fc_w + (size_t)o * NF);
-        float acc[HS] = {};
-#pragma unroll
-        for (int j = 0; j < KV; ++j) {
-            const float4 w = wr[lane + kWave * j];
-#pragma unroll
-            for (int s = 0; s < HS; ++s) {
-                acc[s] = fmaf(w.x, f[s][j].x, acc[s]);
-                acc[s] = fmaf(w.y, f[s][j].y, acc[s]);
-                acc[s] = fmaf(w.z, f[s][j].z, acc[s]);
-                acc[s] = fmaf(w.w, f[s][j].w, acc[s]);
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < HS; ++s) {
-            const float v = wave_sum(acc[s]);
-            if (lane == 0) sm.fc[s][o] = v + fc_b[o];
-        }
-    }
+    fc_stage(feat, B, b0, fc_w, fc_b, sm.fc, wave, lane);
     __syncthreads();
 
     // per sample (wave s, lanes = joints): root zrel, K'^-1, kp3d_unnorm, MLP input
@@ -162,17 +126,8 @@ __global__ __launch_bounds__(HT) void pose_head_kernel(const float* __restrict__
     const bool live = b < B;
     if (live) {
         if (lane == 0) sm.fc[s][2] = 0.f;  // zrel[:, 0] = 0, in place: kp25d sees it
-        // K'^-1 by the adjugate in float64, rounded to float32
-        const float* kk = K + (size_t)b * k_stride;
-        double k[9];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) k[i] = kk[i];
-        const double c00 = k[4] * k[8] - k[5] * k[7], c01 = k[5] * k[6] - k[3] * k[8], c02 = k[3] * k[7] - k[4] * k[6];
-        const double det = k[0] * c00 + k[1] * c01 + k[2] * c02;
         float ki[9];
-        ki[0] = (float)(c00 / det), ki[1] = (float)((k[2] * k[7] - k[1] * k[8]) / det), ki[2] = (float)((k[1] * k[5] - k[2] * k[4]) / det);
-        ki[3] = (float)(c01 / det), ki[4] = (float)((k[0] * k[8] - k[2] * k[6]) / det), ki[5] = (float)((k[2] * k[3] - k[0] * k[5]) / det);
-        ki[6] = (float)(c02 / det), ki[7] = (float)((k[1] * k[6] - k[0] * k[7]) / det), ki[8] = (float)((k[0] * k[4] - k[1] * k[3]) / det);
+        k_inverse(K + (size_t)b * k_stride, ki);
         if (lane < NJ) {
             const float u = sm.fc[s][3 * lane], v = sm.fc[s][3 * lane + 1];
             const float z = lane == 0 ? 0.f : sm.fc[s][3 * lane + 2];
@@ -186,18 +141,8 @@ __global__ __launch_bounds__(HT) void pose_head_kernel(const float* __restrict__
     __syncthreads();
     if (live && lane == 0) {
         // Eq. (6) / (7) on bones 3 and 8, the eps clamps, clamp(4, 50)
-        const float xm = sm.ku[s][3][0], ym = sm.ku[s][3][1], xn = sm.ku[s][8][0], yn = sm.ku[s][8][1];
-        const float zm = sm.fc[s][3 * 3 + 2], zn = sm.fc[s][3 * 8 + 2];
-        const float dx = xn - xm, dy = yn - ym;
-        float a = dx * dx + dy * dy;
-        const float bq = 2.f * (zn * (xn * xn + yn * yn - xn * xm - yn * ym) + zm * (xm * xm + ym * ym - xn * xm - yn * ym));
-        const float ex = xn * zn - xm * zm, ey = yn * zn - ym * zm, ez = zn - zm;
-        const float c = ex * ex + ey * ey + ez * ez - 1.f;
-        float d = bq * bq - 4.f * a * c;
-        a = max_nan(eps, a);
-        d = max_nan(eps, d);
-        float zr = (-bq + sqrtf(d)) / (2.f * a);
-        zr = zr != zr ? zr : fminf(fmaxf(zr, 4.f), 50.f);
+        const float zr = closed_form_zroot(sm.ku[s][3][0], sm.ku[s][3][1], sm.ku[s][8][0], sm.ku[s][8][1], sm.fc[s][3 * 3 + 2],
+                                           sm.fc[s][3 * 8 + 2], eps);
         sm.zroot[s] = zr;
         sm.in[s][NO - 1] = zr;
     }

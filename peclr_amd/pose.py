@@ -5,8 +5,10 @@ helpers of testing/fh_utils.py and the two-pass crop -> predict -> re-crop loop 
 is the reference's, key for key and in its order (`backend_model.<torchvision keys>`, then `zroot_ref.zroot_ref.*`), so
 the published `rn{50,152}_peclr_yt3d-fh_pt_fh_ft.pth` files load unchanged.
 
-Two paths:
+Three paths:
 - stock (CPU, HIP BatchNorm off, train mode or grad enabled): plain torch ops in the reference's order;
+- HIP training (train mode after `enable_hip_training()`, a HIP tensor, HIP BatchNorm on): the backbone on the in-tree
+  kernels and the head, forward and backward, on `peclr_pose_head_train_{fwd,bwd}_f32` (`PoseHeadTrain`);
 - HIP (eval, a HIP tensor, `enable_hip()` / `enable_hip_batchnorm(model.backend_model)`, no grad): the backbone's last
   BatchNorm also average-pools, and one `peclr_pose_head_f32` launch takes the pooled features to every output.
 
@@ -24,6 +26,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 from torch import Tensor, nn
+from torch.autograd.function import once_differentiable
 
 from . import _capi
 from . import resnet as _resnet
@@ -70,6 +73,37 @@ class ZrootMLPRef(nn.Module):
         return zroot + self.zroot_ref(mlp_in).reshape(zroot.shape)
 
 
+class PoseHeadTrain(torch.autograd.Function):
+    """The head in train mode on the HIP kernels (csrc/pose_train.hip): four launches forward, six backward (five when the
+    features need no gradient), every reduction in a fixed order.
+
+    apply(feat [B,2048], K [B or 1,3,3], fc_w, fc_b, *the 14 MLP tensors of `peclr_pose_head_f32`, nbt1, nbt2, bn_eps (2),
+    momentum (2), eps) -> (out64 [B,64], kp3d [B,21,3], zroot [B]); kp25d = out64[:, :63].  The running statistics and the two
+    num_batches_tracked are updated in place.  Differentiable once with respect to the features, fc and the ten MLP
+    parameters; K gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, feat, K, fc_w, fc_b, *rest):
+        mlp, (nbt1, nbt2, bn_eps, momentum, eps) = list(rest[:_capi.POSE_MLP_TENSORS]), rest[_capi.POSE_MLP_TENSORS:]
+        feat, K = feat.contiguous(), K.float().contiguous()
+        out64, kp3d, zroot, save = _capi.pose_head_train_fwd(feat, fc_w, fc_b, mlp, bn_eps, momentum, (nbt1, nbt2), K, eps)
+        ctx.save_for_backward(feat, K, fc_w, out64, zroot, save, *mlp)
+        ctx.set_materialize_grads(False)
+        return out64, kp3d, zroot
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out64, g_kp3d, g_zroot):
+        feat, K, fc_w, out64, zroot, save, *mlp = ctx.saved_tensors
+        g_out64, g_kp3d, g_zroot = (None if g is None else g.float().contiguous() for g in (g_out64, g_kp3d, g_zroot))
+        d_feat, d_fc_w, d_fc_b, d_mlp, _ = _capi.pose_head_train_bwd(feat, fc_w, mlp, K, out64, zroot, save, g_kp3d, g_out64, g_zroot,
+                                                                     want_d_feat=ctx.needs_input_grad[0])
+        grads = [None] * _capi.POSE_MLP_TENSORS
+        for i, g in zip(_capi._POSE_MLP_GRAD_OF, d_mlp):
+            grads[i] = g
+        return (d_feat, None, d_fc_w, d_fc_b, *grads, None, None, None, None, None)
+
+
 def _backbone(name: str) -> _resnet.ResNet:
     model = {"rn50": _resnet.resnet50, "rn152": _resnet.resnet152}[name](norm_layer=FusedBatchNormAct2d)
     model.fc = nn.Linear(model.fc.in_features, 3 * NUM_JOINTS + 1)   # 2D + zrel for 21 joints (+1 unused)
@@ -93,6 +127,7 @@ class RN25DwMLPref(nn.Module):
         self.backend_model = _backbone(backend_model)
         self.zroot_ref = ZrootMLPRef()
         self.register_buffer("K_default", torch.tensor(K_DEFAULT, dtype=torch.float32).reshape(1, 3, 3), persistent=False)
+        self.hip_training = False
 
     # ---- paths
     def enable_hip(self, enabled: bool = True) -> "RN25DwMLPref":
@@ -101,6 +136,26 @@ class RN25DwMLPref(nn.Module):
             self.backend_model.to(memory_format=torch.channels_last)
         enable_hip_batchnorm(self.backend_model, enabled)
         return self
+
+    def enable_hip_training(self, enabled: bool = True) -> "RN25DwMLPref":
+        """Opt in: in train mode, on a HIP tensor and with the HIP BatchNorm on, `head()` and `forward()` run the head on the
+        training kernels (`PoseHeadTrain`) and return `zroot` [B], the refined root depth, next to the four usual keys.
+        Without it train mode stays on stock torch ops.  Call after .to(device)."""
+        if enabled:
+            if not self.backend_model.fc.weight.is_cuda:
+                raise _capi.PeclrHipError("enable_hip_training: the model must be on a HIP device (peclr_amd has no CPU path)")
+            self._check_hip_training()
+        self.hip_training = bool(enabled)
+        return self
+
+    def _check_hip_training(self):
+        for bn in (self.zroot_ref.zroot_ref[1], self.zroot_ref.zroot_ref[4]):
+            if bn.momentum is None or not bn.track_running_stats:
+                raise _capi.PeclrHipError("the HIP training head needs BatchNorm1d with a numeric momentum and "
+                                          "track_running_stats=True (momentum=None and track_running_stats=False are not supported)")
+
+    def hip_train_path(self, x: Tensor) -> bool:
+        return self.hip_training and self.training and x.is_cuda and self.backend_model.bn1.hip
 
     def hip_path(self, x: Tensor) -> bool:
         return (not self.training and x.is_cuda and not torch.is_grad_enabled() and self.backend_model.bn1.hip
@@ -130,6 +185,16 @@ class RN25DwMLPref(nn.Module):
         out = {"kp3d": kp3d, "zrel": kp25d[..., 2:3], "kp2d": kp25d[..., :2], "kp25d": kp25d}
         return out, T2, fh, status
 
+    def _head_train(self, feat: Tensor, K: Tensor) -> Dict[str, Tensor]:
+        self._check_hip_training()
+        s = self.zroot_ref.zroot_ref
+        fc = self.backend_model.fc
+        out64, kp3d, zroot = PoseHeadTrain.apply(feat, K, fc.weight, fc.bias, *self._mlp_tensors(), s[1].num_batches_tracked,
+                                                 s[4].num_batches_tracked, (s[1].eps, s[4].eps), (s[1].momentum, s[4].momentum),
+                                                 self.zroot_ref.eps_value)
+        kp25d = out64[:, :-1].contiguous().view(-1, NUM_JOINTS, 3)      # a copy: `PoseLoss` takes a contiguous prediction
+        return {"kp3d": kp3d, "zrel": kp25d[..., 2:3], "kp2d": kp25d[..., :2], "kp25d": kp25d, "zroot": zroot}
+
     def _head_stock(self, out: Tensor, K: Tensor) -> Dict[str, Tensor]:
         kp25d = out[:, :-1].view(-1, NUM_JOINTS, 3)
         kp2d, zrel = kp25d[..., :2], kp25d[..., 2:3]
@@ -142,12 +207,16 @@ class RN25DwMLPref(nn.Module):
     def head(self, features: Tensor, K: Optional[Tensor] = None) -> Dict[str, Tensor]:
         """Pooled [B, 2048] features -> {"kp3d", "zrel", "kp2d", "kp25d"}."""
         K = self.K_default if K is None else K
+        if self.hip_train_path(features):
+            return self._head_train(features, K)
         if self.hip_path(features):
             return self._head_hip(features, K)[0]
         return self._head_stock(self.backend_model.fc(features), K)
 
     def forward(self, img: Tensor, K: Optional[Tensor] = None) -> Dict[str, Tensor]:
         K = self.K_default if K is None else K
+        if self.hip_train_path(img):
+            return self._head_train(self.features(img), K)
         if self.hip_path(img):
             return self._head_hip(self.features(img), K)[0]
         return self._head_stock(self.backend_model(img), K)
