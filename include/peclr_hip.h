@@ -878,6 +878,22 @@ int peclr_pose_loss(const float* pred, const float* joints, const float* joints3
 int peclr_pose_loss_bwd(const float* grad_losses, const double* g_l1, const double* g_3d, const double* g_zroot, const float* scale,
                         const double* inv_valid, int B, float* grad_pred, float* grad_z_root_calc, peclr_stream_t stream);
 
+/* ---- the metrics of a supervised step (reference src/models/utils.py: calculate_metrics), csrc/pose_metrics.hip; host side:
+ * peclr_amd/pose_metrics.py.  ONE launch on `stream`, one workgroup per pair; no atomics, no host synchronisation, nothing kept
+ * in the library between calls -- safe inside a hipGraph capture, and the same bits on every run.
+ *   in   pred, truth [B][21][3]    float32, contiguous; 1 <= B <= PECLR_POSE_METRICS_MAX_BATCH (else PECLR_ERR_SHAPE)
+ *        pred2, truth2 [B][21][3]  (nullable, both or neither) a second pair, e.g. the 3D joints next to the 2.5D ones
+ *        workspace                 at least 2 x 21 x B x 4 bytes (half of it without the second pair): the distances' bit patterns
+ *   out  out [4] float32           {mean, median} of the first pair, then of the second (out[2], out[3] are not written without it).
+ *                                  The distances |pred - truth|_2 of all n = 21 B joints are float64 from the float32 inputs; the
+ *                                  mean is their fixed-order float64 sum / n, rounded once; the median is torch.median's LOWER
+ *                                  median -- element (n - 1) / 2 of the ascending float32-rounded distances, found by an exact radix
+ *                                  select over their bit patterns (rounding is monotone: it equals the rounded float64 median).
+ *                                  A NaN distance makes both values of its pair NaN; +inf orders last; pred == truth gives +0.   */
+#define PECLR_POSE_METRICS_MAX_BATCH 1024
+int peclr_pose_step_metrics_f32(const float* pred, const float* truth, const float* pred2, const float* truth2, int B,
+                                void* workspace, float* out, peclr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,7 @@ SIGNATURES = {
     "peclr_supervised_labels": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "peclr_pose_loss": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P]),
     "peclr_pose_loss_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, _P, _P, _P]),
+    "peclr_pose_step_metrics_f32": (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P]),
 }
 
 
@@ -1803,3 +1804,33 @@ def pose_loss_bwd(grad_losses: torch.Tensor, g_l1: torch.Tensor, g_3d: torch.Ten
     _launch("pose_loss_bwd", "peclr_pose_loss_bwd", up, lp, tp, zp, sp, ip, b, grad_pred.data_ptr(),
             None if grad_z is None else grad_z.data_ptr(), _stream(), nbytes=4 * b * (63 + 2) + 8 * b * (2 * 63 + 1))
     return grad_pred, grad_z
+
+
+# ------------------------------------------------------------------ metrics of a supervised step (peclr_amd/pose_metrics.py)
+POSE_METRICS_MAX_BATCH = 1024
+
+
+def pose_step_metrics(pred: torch.Tensor, truth: torch.Tensor, pred2: Optional[torch.Tensor] = None,
+                      truth2: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                      workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pred, truth [B,21,3] float32, 1 <= B <= 1024 (pred2, truth2: an optional second pair of the same shape) -> out [4]
+    float32: the mean and torch's lower median of the per-joint Euclidean distances of the first pair, then of the second
+    (out[2:4] is left as it is without one).  `workspace`: int32 [2 * 21 * B] (half without the second pair), from torch's
+    allocator when not given.  One launch, logged as one EVENT_LOG entry whose `kernel` field says so; no host read."""
+    b = _label_batch(pred, "pose_step_metrics")
+    if b > POSE_METRICS_MAX_BATCH:
+        raise PeclrHipError(f"pose_step_metrics: at most {POSE_METRICS_MAX_BATCH} samples per call, got {b}")
+    if (pred2 is None) != (truth2 is None):
+        raise PeclrHipError("pose_step_metrics: the second pair needs both its prediction and its truth")
+    pairs = 1 if pred2 is None else 2
+    pp, tp = _label_ptr(pred, (b, 21, 3), "pose_step_metrics pred"), _label_ptr(truth, (b, 21, 3), "pose_step_metrics truth")
+    p2, t2 = _label_ptr(pred2, (b, 21, 3), "pose_step_metrics pred2"), _label_ptr(truth2, (b, 21, 3), "pose_step_metrics truth2")
+    out = torch.empty((4,), device=pred.device, dtype=torch.float32) if out is None else out
+    if workspace is None:
+        workspace = torch.empty((pairs * 21 * b,), device=pred.device, dtype=torch.int32)
+    elif not workspace.is_cuda or workspace.dtype != torch.int32 or not workspace.is_contiguous() or workspace.numel() < pairs * 21 * b:
+        raise PeclrHipError(f"pose_step_metrics workspace: a contiguous int32 HIP tensor of at least {pairs * 21 * b} elements")
+    _launch("pose_step_metrics", "peclr_pose_step_metrics_f32", pp, tp, p2, t2, b, workspace.data_ptr(),
+            _label_ptr(out, (4,), "pose_step_metrics out"), _stream(), nbytes=pairs * 21 * b * (6 * 4 + 5 * 2 * 4) + 8 * pairs,
+            kernel="1 launch")
+    return out

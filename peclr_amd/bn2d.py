@@ -798,6 +798,32 @@ def _conv1x1_fwd(x: Tensor, weight: Tensor, conv, planes, stats, amax) -> Tensor
     return _nchw(_with_stats(stats, cout, launch), n, h, w)          # channels_last NCHW view of the NHWC result
 
 
+def _wgrad_narrow_x6(gy: Tensor, x: Tensor, weight: Tensor, param=None, stride: int = 1, taps: int = 9):
+    """d(weight) of the convolutions `_wgrad_3x3_x6` takes, for feature maps narrower than the 6 columns its padded pixel space
+    needs (layer3 / layer4 of small crops): the pixels every tap points at are gathered into one [rows, taps * Cin] matrix --
+    plain copies -- and dY^T X runs as ONE taps = 1 product on peclr_gemm_x6t_f32, so the result is fixed-order and
+    bit-identical run to run like the wide route's.  The gather costs taps x the input, which is why this is the route of
+    `routing(force=True)` only: at these sizes MIOpen's kernels are faster, but do not give the same bits on every run."""
+    n, cin, h, w = x.shape
+    cout, ho, wo = gy.shape[1:]
+
+    def run():
+        xn = x.permute(0, 2, 3, 1)                                      # the NHWC storage as it lies
+        if taps == 9:
+            xp = F.pad(xn, (0, 0, 1, 1, 1, 1))
+            cols = torch.stack([xp[:, ky:ky + stride * ho:stride, kx:kx + stride * wo:stride] for ky in range(3) for kx in range(3)], dim=3)
+        else:
+            cols = xn[:, ::stride, ::stride]
+        # (.contiguous(): a no-op except where a one-pixel-wide slice kept the input's row stride)
+        dw = _capi.gemm_x6t(_rows(gy).contiguous(), cols.reshape(n * ho * wo, taps * cin).contiguous(), tag="conv3x3_wgrad" if taps == 9 else "conv1x1_wgrad")
+        if taps == 9:
+            return dw.view(cout, 3, 3, cin).permute(0, 3, 1, 2)      # = a channels_last [Cout, Cin, 3, 3] tensor
+        ref = param if param is not None else weight
+        return dw.as_strided(ref.shape, ref.stride())
+
+    return _on_side_stream(param, (gy, x), run)
+
+
 class _Conv1x1Gemm(torch.autograd.Function):
     """1x1 / stride-1 convolution of an NHWC fp32 tensor as the GEMM it is, on the bf16 matrix cores at fp32 accuracy:
     forward y[R, Cout] = x[R, Cin] . W^T and / or the input gradient dx[R, Cin] = dy[R, Cout] . W, each where `_x6_pays`
@@ -872,9 +898,14 @@ class _Conv3x3Gemm(torch.autograd.Function):
         dw = None
         if ctx.needs_input_grad[1]:
             in_tree = (ROUTING.gemm_x6t and ROUTING.conv3x3_wgrad_x6 and weight.is_contiguous(memory_format=torch.channels_last)
-                       and x.shape[3] >= 6 and x.shape[1] % 4 == 0 and gy.shape[1] % 4 == 0
+                       and x.shape[1] % 4 == 0 and gy.shape[1] % 4 == 0
                        and gy.shape[1] >= (64 if ROUTING.x6_layer1_wgrad else 128))   # (64 output channels: the 64 x 64 block with two tap halves)
-            dw = _wgrad_3x3_x6(gy, x, weight, conv.weight) if in_tree else _conv_wgrad(gy, x, weight, (1, 1), (1, 1), conv.weight)
+            if in_tree and x.shape[3] >= 6:
+                dw = _wgrad_3x3_x6(gy, x, weight, conv.weight)
+            elif in_tree and ROUTING.force:          # fewer than 6 columns: the gathered, still fixed-order form
+                dw = _wgrad_narrow_x6(gy, x, weight, conv.weight)
+            else:
+                dw = _conv_wgrad(gy, x, weight, (1, 1), (1, 1), conv.weight)
         dx = None
         if ctx.needs_input_grad[0]:
             def launch(**kw):
@@ -916,10 +947,14 @@ class _ConvS2Gemm(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             taps = weight.shape[2] * weight.shape[3]
             in_tree = (ROUTING.gemm_x6t and ROUTING.conv_s2_wgrad_x6 and weight.is_contiguous(memory_format=torch.channels_last)
-                       and x.shape[2] == 2 * gy.shape[2] and x.shape[3] == 2 * gy.shape[3] and gy.shape[3] >= 6
+                       and x.shape[2] == 2 * gy.shape[2] and x.shape[3] == 2 * gy.shape[3]
                        and x.shape[1] % 4 == 0 and gy.shape[1] % 4 == 0 and gy.shape[1] >= 64 and x.shape[1] >= 64)
-            dw = (_wgrad_3x3_x6(gy, x, weight, conv.weight, stride=2, taps=taps) if in_tree
-                  else _conv_wgrad(gy, x, weight, (2, 2), pad, conv.weight))
+            if in_tree and gy.shape[3] >= 6:
+                dw = _wgrad_3x3_x6(gy, x, weight, conv.weight, stride=2, taps=taps)
+            elif in_tree and ROUTING.force:          # fewer than 6 output columns: the gathered, still fixed-order form
+                dw = _wgrad_narrow_x6(gy, x, weight, conv.weight, stride=2, taps=taps)
+            else:
+                dw = _conv_wgrad(gy, x, weight, (2, 2), pad, conv.weight)
         dx = None
         if ctx.needs_input_grad[0]:
             if weight.shape[2] == 1 and x.shape[2] == 2 * gy.shape[2] and x.shape[3] == 2 * gy.shape[3]:

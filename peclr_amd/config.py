@@ -52,3 +52,21 @@ def hybrid2_config(**overrides) -> Config:
     for k, v in overrides.items():
         cfg[k] = v
     return cfg
+
+
+# the supervised fine-tuning module (peclr_amd/finetune.py).  The reference ships no supervised config file (its supervised model
+# classes are commented out): optimiser values as hybrid2_config.json's, plain Adam, FreiHAND's training set as the sample count.
+# No `resnet_size`: `BaseModel` builds no `encoder`, the network is the pose model itself.
+SUPERVISED_DEFAULTS = {
+    "backend_model": "rn50", "lr": 1e-4, "optimizer": "adam", "opt_weight_decay": 1e-6, "warmup_epochs": 10, "batch_size": 128,
+    "num_of_mini_batch": 1, "num_samples": 32560, "lr_max_epochs": None,
+    "loss_weights": {"loss_2d": 1.0, "loss_z": 1.0, "loss_z_unscaled": 0.0, "loss_3d": 1.0},
+}
+
+
+def supervised_config(**overrides) -> Config:
+    """The configuration of `peclr_amd.SupervisedPose`: SUPERVISED_DEFAULTS with `overrides` on top."""
+    cfg = Config(SUPERVISED_DEFAULTS)
+    for k, v in overrides.items():
+        cfg[k] = v
+    return cfg

@@ -74,6 +74,13 @@ def get_encoder_state_dict(saved_model_path: str, checkpoint: str, map_location=
     return {key[len("encoder."):]: value for key, value in state.items() if "encoder" in key}
 
 
+def encoder_entries(checkpoint_path: str) -> dict:
+    """The entries of a checkpoint FILE whose key starts with "encoder.", without that prefix, on the CPU (`get_encoder_state_dict`
+    keeps the reference's substring test; a key that merely contains the word is not an encoder entry here)."""
+    state = torch.load(checkpoint_path, map_location="cpu")["state_dict"]
+    return {key[len("encoder."):]: value for key, value in state.items() if key.startswith("encoder.")}
+
+
 def restore_model(model: torch.nn.Module, experiment_key: str, checkpoint: str = ""):
     """experiments/utils.py:535-546: load the newest (or the named) checkpoint of an experiment."""
     path = get_latest_checkpoint(experiment_key, checkpoint)

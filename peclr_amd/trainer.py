@@ -15,6 +15,7 @@ from typing import Callable, Dict, Iterable, List, Optional
 
 import torch
 
+from . import _capi
 from . import dist as pdist
 from .port import save_checkpoint
 
@@ -134,7 +135,7 @@ class Trainer:
         if self.activation_checkpointing:
             from .resnet import set_activation_checkpointing
 
-            if set_activation_checkpointing(model.encoder, True) == 0:
+            if getattr(model, "encoder", None) is None or set_activation_checkpointing(model.encoder, True) == 0:
                 raise RuntimeError("activation_checkpointing: the encoder has no peclr_amd.resnet blocks")
         if self.overlap_wgrad:
             from . import bn2d as _bn2d
@@ -385,6 +386,9 @@ class Trainer:
             self._load_static(self._static_batch, batch)
         self.optimizer.prepare_step()
         self._graph.replay()
+        # the replayed optimiser launch wrote the parameters through raw pointers, as an eager one does: an eager forward
+        # pass after this replay (validation, a ragged last batch) must re-pack its weight planes
+        _capi.WEIGHTS_EPOCH += 1
         self.scheduler.step()
         self.global_step += 1
         return self._static_out

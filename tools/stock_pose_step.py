@@ -1,0 +1,67 @@
+"""The supervised step of the 2.5D pose model written with stock torch operators only -- the comparison arm of
+tools/finetune_synthetic.py and tools/pose_finetune_timing.py: the model's stock forward (no `enable_hip*`), cal_l1_loss and
+cal_3d_loss over convert_2_5D_to_3D with `torch.inverse`, and calculate_metrics, each from its formula.  `StockPose` is
+`SupervisedPose` with that composition as its `training_step` / `validation_step`; everything else (optimiser, schedule,
+hooks) is inherited, so the two arms differ in the kernels of the step alone."""
+import torch
+
+from peclr_amd import SupervisedPose
+from peclr_amd.finetune import METRIC_NAMES
+from peclr_amd.pose_loss import LOSS_NAMES
+
+
+def lift(pred, scale, K, z_root=None):
+    """convert_2_5D_to_3D for a batch; z_root None: get_root_depth's closed form with its two clamp(min=1e-6)."""
+    inv = torch.inverse(K)
+    rays = torch.cat((pred[..., :2], torch.ones_like(pred[..., 2:])), 2) @ inv.transpose(1, 2)
+    if z_root is None:
+        (xn, yn), (xm, ym) = (rays[:, 0, 0], rays[:, 0, 1]), (rays[:, 2, 0], rays[:, 2, 1])
+        zn, zm = pred[:, 0, 2], pred[:, 2, 2]
+        a = (xn - xm) ** 2 + (yn - ym) ** 2
+        b = 2 * (zn * (xn ** 2 + yn ** 2 - xn * xm - yn * ym) + zm * (xm ** 2 + ym ** 2 - xn * xm - yn * ym))
+        c = (xn * zn - xm * zm) ** 2 + (yn * zn - ym * zm) ** 2 + (zn - zm) ** 2 - 1
+        z_root = 0.5 * (-b + torch.clamp(b ** 2 - 4 * a * c, min=1e-6) ** 0.5) / torch.clamp(a, min=1e-6)
+    return rays * ((pred[..., 2:] + z_root.view(-1, 1, 1)) * scale.view(-1, 1, 1))
+
+
+def losses(pred, batch, z_root=None):
+    valid = batch["joints_valid"]
+    weight = valid / valid.sum()
+    dz = (pred[..., 2:] - batch["joints"][..., 2:]).abs() * weight
+    return {"loss_2d": ((pred[..., :2] - batch["joints"][..., :2]).abs() * weight).sum() / 2, "loss_z": dz.sum(),
+            "loss_z_unscaled": (dz * batch["scale"].view(-1, 1, 1)).sum(),
+            "loss_3d": ((lift(pred, batch["scale"], batch["K"], z_root) - batch["joints3D"]).abs() * weight).sum() / 3}
+
+
+def metrics(pred, truth, pred2, truth2):
+    """calculate_metrics for two pairs -> [mean, median, mean, median]."""
+    out = []
+    for p, t in ((pred, truth), (pred2, truth2)):
+        d = torch.sum((p - t) ** 2, 2) ** 0.5
+        out += [torch.mean(d), torch.median(d)]
+    return out
+
+
+class StockPose(SupervisedPose):
+    def _values(self, out, batch, z_root, kp3d, suffix):
+        ls = losses(out["kp25d"], batch, z_root)
+        with torch.no_grad():
+            ms = metrics(out["kp25d"], batch["joints"], kp3d, batch["joints3D"])
+        total = sum(w * ls[n] for n, w in self.loss.weights.items() if w != 0.0)
+        loss_names = [n + ("_val" if suffix == "val" else "") for n in LOSS_NAMES]
+        return {**{k: ls[n].detach() for k, n in zip(loss_names, LOSS_NAMES)},
+                **{f"{n}_{suffix}": m for n, m in zip(METRIC_NAMES, ms)}, "loss": total}
+
+    def training_step(self, batch, batch_idx):
+        out = self.model(batch["image"], batch["K"])
+        # the refined root depth: zrel of the wrist is 0 and the third component of its ray is 1
+        self.train_metrics = self._values(out, batch, out["kp3d"][:, 0, 2], out["kp3d"].detach(), "train")
+        return self.train_metrics
+
+    def validation_step(self, batch, batch_idx):
+        with torch.no_grad():
+            out = self.model(batch["image"], batch["K"])
+            kp3d = lift(out["kp25d"], batch["scale"], batch["K"])
+            if self.evaluator is not None:
+                self.evaluator.update_25d(out["kp25d"].contiguous(), batch["scale"], batch["K"], batch["joints3D"])
+            return self._values(out, batch, None, kp3d, "val")
