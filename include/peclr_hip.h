@@ -420,6 +420,12 @@ int peclr_bn2d_finalize_f32(float* partial, int n_split, int R, int C, int train
                             float* scale_shift, peclr_stream_t stream);
 int peclr_bn2d_combine_f64(const float* partial, int n_split, int C, double* totals,
                            peclr_stream_t stream);
+/* The eval-mode scale / shift tables of MANY BatchNorm2d layers in one launch (what an eval-mode peclr_bn2d_finalize_f32 writes
+ * per layer, bit for bit: invstd = 1 / sqrtf(running_var + eps), scale = gamma * invstd, shift = beta - running_mean * scale).
+ *   desc_table: DEVICE array of `count` entries of 8 int64 {gamma, beta, running_mean, running_var (fp32 [C] each), out (the
+ *   flat fp32 output buffer), C | (bits of the float eps) << 32, offset (floats) of this layer's [2][C] table in `out`, number
+ *   of channels of the entries before this one}; total_channels = the sum of C over the table. */
+int peclr_bn2d_eval_tables(const void* desc_table, int count, int total_channels, peclr_stream_t stream);
 int peclr_bn2d_finalize_totals_f32(const double* totals, const float* shift, int C,
                                    float eps, float momentum, const float* gamma, const float* beta,
                                    float* running_mean, float* running_var,
@@ -666,6 +672,19 @@ int peclr_conv_h(int dtype, int NB, int H, int W, int Cin, int Cout, int taps, i
                  const peclr_bn_bwd_fuse* bn_bwd, peclr_stream_t stream);
 int peclr_conv3x3_s2_dgrad_h(int dtype, int NB, int Ho, int Wo, int Cout, int Cin, const void* dY, const void* Bp, void* dX,
                              int tile_rows, const void* zeros, const peclr_bn_bwd_fuse* bn_bwd, peclr_stream_t stream);
+/* Prediction (eval mode): the BatchNorm2d (+ residual add) (+ ReLU) behind a convolution, folded into that convolution's
+ * epilogue -- per output element, in fp32 on the accumulator,
+ *     v = fmaf(acc, scale[col], shift[col]);  if (addend) v += addend;  if (relu) v = max(v, 0);  out = round_to_16_bit(v)
+ * ONE rounding per layer (convolution -> peclr_bn2d_apply rounds the convolution's output and then the layer's), and no
+ * apply pass over the activation.  scale_shift: that layer's fp32 [2][N] table (scale row, then shift row), 16-byte aligned,
+ * as peclr_bn2d_eval_tables or an eval-mode peclr_bn2d_finalize_f32 writes it; NULL is PECLR_ERR_NULL.  The weights are NOT
+ * rescaled: the planes peclr_h_pack makes serve unchanged.  ReLU drops a NaN as peclr_bn2d_apply's does (fmaxf).  Shapes,
+ * alignment and tile_rows as peclr_gemm_h / peclr_conv_h (forward: no flip); the addend of peclr_gemm_h_bnact is dense
+ * ([M][ldd], nullable); no statistics, no backward reduction. */
+int peclr_gemm_h_bnact(int dtype, int M, int N, int K, const void* A, int lda, const void* Bp, void* C, int ldc, const void* addend,
+                       int ldd, const float* scale_shift, int relu, int tile_rows, peclr_stream_t stream);
+int peclr_conv_h_bnact(int dtype, int NB, int H, int W, int Cin, int Cout, int taps, int stride, const void* X, const void* Bp, void* Y,
+                       int tile_rows, const void* zeros, const float* scale_shift, int relu, peclr_stream_t stream);
 /* Weight gradient of a 16-bit 1x1 convolution (csrc/wgrad_h.hip): dW[Cout][Cin] (fp32) = dY^T X over the rows of two NHWC
  * activations -- A = dY [K][lda] (M = Cout), B = X [K][ldb] (N = Cin); stride = 2 (the 1x1 / stride-2 shortcut): A's K rows are
  * the Ho x Wo output pixels, B holds the 2 Ho x 2 Wo input pixels.  Both operands go global -> LDS by LDS-DMA as they lie in

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import struct
 from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_uint32, c_uint64, c_void_p
 from typing import Optional
 
@@ -107,6 +108,9 @@ SIGNATURES = {
     "peclr_conv_h_row_blocks": (c_int, [c_int] * 7),
     "peclr_gemm_h": (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, c_int, _P, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P]),
     "peclr_conv_h": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
+    "peclr_gemm_h_bnact": (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, c_int, _P, c_int, _P, c_int, c_int, _P]),
+    "peclr_conv_h_bnact": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, c_int, _P]),
+    "peclr_bn2d_eval_tables": (c_int, [_P, c_int, c_int, _P]),
     "peclr_conv3x3_s2_dgrad_h": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P]),
     "peclr_wgrad3_h_slabs": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "peclr_wgrad3_h": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P]),
@@ -857,6 +861,52 @@ def conv_h(x: torch.Tensor, planes: torch.Tensor, cout: int, taps: int = 9, stri
     return _with_partial(y, partial, ns)
 
 
+def _fold_table(scale_shift, n: int, device, who: str):
+    """The fp32 [2, n] scale / shift table of the BatchNorm2d folded into `who`'s epilogue (None -> the library's null code)."""
+    if scale_shift is None:
+        return None
+    if scale_shift.dtype != torch.float32 or scale_shift.numel() != 2 * n or not scale_shift.is_contiguous() or scale_shift.device != device:
+        raise PeclrHipError(f"{who}: scale_shift is the contiguous fp32 [2, {n}] table of the folded BatchNorm2d on {device}")
+    return scale_shift.data_ptr()
+
+
+def gemm_h_bnact(a: torch.Tensor, planes: torch.Tensor, n: int, scale_shift: Optional[torch.Tensor], relu: bool = True,
+                 addend: Optional[torch.Tensor] = None, tag: str = "conv1x1_bnact", tile_rows: int = 0) -> torch.Tensor:
+    """`gemm_h` with the eval-mode BatchNorm2d (+ dense addend) (+ ReLU) behind it in the epilogue (peclr_gemm_h_bnact):
+    C = round(relu(fmaf(A . B_t^T, scale, shift) + addend)), one rounding; scale_shift: that layer's fp32 [2, n] table."""
+    m, k = a.shape
+    io = _half_io(a, "gemm_h_bnact A")
+    _h_planes_ok(planes, n, k, "gemm_h_bnact")
+    if not a.is_contiguous() or (addend is not None and (tuple(addend.shape) != (m, n) or addend.dtype != a.dtype or not addend.is_contiguous())):
+        raise PeclrHipError(f"gemm_h_bnact: contiguous {a.dtype} A {tuple(a.shape)} / addend [{m}, {n}] expected")
+    out = torch.empty((m, n), device=a.device, dtype=a.dtype)
+    _launch(tag, "peclr_gemm_h_bnact", io, m, n, k, a.data_ptr(), k, _ptr(planes, torch.uint8), out.data_ptr(), n,
+            addend.data_ptr() if addend is not None else None, n, _fold_table(scale_shift, n, a.device, "gemm_h_bnact"), int(relu),
+            tile_rows, _stream(), nbytes=2 * (m * k + m * n + (m * n if addend is not None else 0) + k * n) + 8 * n,
+            flops=2 * m * n * k, kernel="conv_h_kernel")
+    return out
+
+
+def conv_h_bnact(x: torch.Tensor, planes: torch.Tensor, cout: int, scale_shift: Optional[torch.Tensor], relu: bool = True, taps: int = 9,
+                 stride: int = 1, tag: Optional[str] = None, tile_rows: int = 0) -> torch.Tensor:
+    """`conv_h` (forward) with the eval-mode BatchNorm2d (+ ReLU) behind it in the epilogue (peclr_conv_h_bnact)."""
+    nb, cin, h, w = x.shape
+    io = _half_io(x, "conv_h_bnact x")
+    xp = _nhwc_ptr(x, "conv_h_bnact x", x.dtype)
+    _h_planes_ok(planes, cout, taps * cin, "conv_h_bnact")
+    if h % stride or w % stride:
+        raise PeclrHipError(f"conv_h_bnact: {h} x {w} input with stride {stride}")
+    ho, wo = h // stride, w // stride
+    y = torch.empty((nb, cout, ho, wo), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
+    m = nb * ho * wo
+    _launch(tag or ("conv3x3_bnact" if stride == 1 else "conv_s2_bnact"), "peclr_conv_h_bnact", io, nb, h, w, cin, cout, taps, stride, xp,
+            _ptr(planes, torch.uint8), y.data_ptr(), tile_rows, _hzeros(x.device, x.dtype).data_ptr(),
+            _fold_table(scale_shift, cout, x.device, "conv_h_bnact"), int(relu), _stream(),
+            nbytes=2 * (nb * h * w * cin + m * cout + taps * cin * cout) + 8 * cout, flops=2 * m * taps * cin * cout,
+            kernel="conv_h_kernel (3x3)" if taps == 9 else "conv_h_kernel (stride 2)")
+    return y
+
+
 def wgrad_h_ok(gy: torch.Tensor, x: torch.Tensor, taps: int, stride: int) -> bool:
     """Does peclr_wgrad_h take this weight gradient?  (1x1 convolutions, stride 1 or 2, channel counts multiples of 32.)"""
     cout, cin = gy.shape[1], x.shape[1]
@@ -1058,6 +1108,58 @@ def _bn2d_scale_shift(x, gamma, beta, running_mean, running_var, nbt, training, 
                 _ptr(running_mean), _ptr(running_var), _ptr(nbt, torch.int64, "num_batches_tracked") if training else None,
                 save[0].data_ptr(), save[1].data_ptr(), ss.data_ptr(), _stream(), nbytes=8 * ns * c)
     return save, ss
+
+
+class BnEvalTables:
+    """The eval-mode scale / shift tables of a list of BatchNorm2d layers, written by ONE launch (peclr_bn2d_eval_tables) into
+    one flat fp32 buffer; `table(i)` is layer i's [2, C] view of it.  `layers`: (gamma, beta, running_mean, running_var, eps)
+    per layer, fp32 HIP tensors.  The descriptor table is built and uploaded here, once; `stale(layers)` says whether a tensor
+    has moved since (then build a new object -- not while a hipGraph is being captured: the upload is a host-to-device copy)."""
+
+    def __init__(self, layers):
+        if not layers:
+            raise PeclrHipError("BnEvalTables: no layers")
+        dev = layers[0][0].device
+        rows, self.offsets, chan = [], [], 0
+        for gamma, beta, rm, rv, eps in layers:
+            c = gamma.numel()
+            for t in (gamma, beta, rm, rv):
+                _ptr(t, what="BnEvalTables: BatchNorm2d parameter / running statistic")
+                if t.numel() != c or t.device != dev:
+                    raise PeclrHipError("BnEvalTables: gamma, beta, running_mean, running_var of one layer are [C] tensors on one device")
+            self.offsets.append((2 * chan, c))
+            rows.append([gamma.data_ptr(), beta.data_ptr(), rm.data_ptr(), rv.data_ptr(), 0,
+                         c | (int.from_bytes(struct.pack("<f", float(eps)), "little") << 32), 2 * chan, chan])
+            chan += c
+        self.flat = torch.empty(2 * chan, device=dev, dtype=torch.float32)
+        for r in rows:
+            r[4] = self.flat.data_ptr()
+        self.ptrs = self._ptrs(layers)
+        self._keep = [t for layer in layers for t in layer[:4]]
+        self.table_dev = torch.tensor(rows, dtype=torch.int64).to(dev)
+        self.count, self.channels = len(rows), chan
+        self.views = [self.flat[off:off + 2 * c].view(2, c) for off, c in self.offsets]
+
+    @staticmethod
+    def _ptrs(layers):
+        return [(g.data_ptr(), b.data_ptr(), rm.data_ptr(), rv.data_ptr(), float(eps)) for g, b, rm, rv, eps in layers]
+
+    def stale(self, layers) -> bool:
+        return self._ptrs(layers) != self.ptrs
+
+    def launch(self):
+        _launch("bn2d_eval_tables", "peclr_bn2d_eval_tables", self.table_dev.data_ptr(), self.count, self.channels, _stream(),
+                nbytes=24 * self.channels, kernel="bn2d_eval_tables_kernel")
+        return self
+
+    def table(self, i: int) -> torch.Tensor:
+        return self.views[i]
+
+
+def bn2d_eval_tables(layers) -> "BnEvalTables":
+    """One launch for the eval-mode tables of `layers` (see `BnEvalTables`); a caller that runs this every forward keeps the object
+    and calls its `launch()`."""
+    return BnEvalTables(layers).launch()
 
 
 _ABSMAX_SLABS: dict = {}

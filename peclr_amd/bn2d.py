@@ -150,6 +150,9 @@ class Routing:
     wgrad16: bool = dataclasses.field(default_factory=lambda: _env_flag("PECLR_WGRAD16"))              # ... and their weight gradients
     stem_wgrad: bool = dataclasses.field(default_factory=lambda: _env_flag("PECLR_STEM_WGRAD"))        # ... and its weight gradient
     stem: bool = dataclasses.field(default_factory=lambda: _env_flag("PECLR_STEM"))                    # the 7x7 / stride-2 stem forward in-tree (csrc/stem.hip)
+    # 16-bit prediction: the eval-mode BatchNorm layers of the bottleneck blocks folded into the 16-bit convolutions' epilogues
+    # (`fold_plan`, resnet.Bottleneck._run_folded).  Opt-in: FreiHANDPredictor(precision="bf16") turns it on for its own passes
+    fold_eval_bn: bool = dataclasses.field(default_factory=lambda: _env_flag("PECLR_FOLD_EVAL_BN", "0"))
     force: bool = dataclasses.field(default_factory=lambda: _env_flag("PECLR_ROUTE_FORCE", "0"))
 
     # ---- "does the in-tree kernel pay at this shape" (measured on ResNet-50's shapes; the kernels accept far more)
@@ -1551,12 +1554,110 @@ class FusedBatchNormAct2d(nn.BatchNorm2d):
         return F.max_pool2d(y, 3, stride=2, padding=1) if pool else y
 
 
+# ------------------------------------------------------------------ 16-bit prediction: eval-mode BatchNorm in the convolution epilogues
+def _fold_pair_ok(conv, bn, kernel, strides) -> bool:
+    """May `bn` (eval mode) be folded into `conv`'s 16-bit epilogue?  The layer must have its own scale, shift and running
+    statistics, the convolution must be one the pack groups take (`X6PackGroup.member`: channel counts conv_h accepts)."""
+    return (isinstance(bn, FusedBatchNormAct2d) and bool(bn.affine) and bool(bn.track_running_stats) and isinstance(conv, Conv2d)
+            and conv.kernel_size == kernel and conv.stride in strides and X6PackGroup.member(conv)
+            and conv.out_channels == bn.num_features)
+
+
+def fold_plan(backbone: nn.Module):
+    """[(convolution name, BatchNorm name)] under `backbone` whose eval-mode BatchNorm2d the 16-bit prediction path applies in the
+    convolution's epilogue (`ROUTING.fold_eval_bn`), in the order the blocks launch them.  Pure host logic.  Bottleneck blocks
+    only, and a block only as a whole (one layer that does not qualify keeps the whole block on the unfolded path).  Two layers
+    keep their pass because it does more than scale and shift: the stem's bn1 (its pass also max-pools; not in a block anyway)
+    and the last block's bn3 when `tail_avgpool` is set (its pass average-pools and never writes the activation)."""
+    from .resnet import Bottleneck
+
+    plan = []
+    for name, block in backbone.named_modules():
+        if not isinstance(block, Bottleneck):
+            continue
+        one, any_s = ((1, 1),), ((1, 1), (2, 2))
+        pairs = [("conv1", "bn1", block.conv1, block.bn1, (1, 1), one), ("conv2", "bn2", block.conv2, block.bn2, (3, 3), any_s)]
+        ds = block.downsample
+        if ds is not None:
+            if not (isinstance(ds, nn.Sequential) and len(ds) == 2):
+                continue
+            pairs.append(("downsample.0", "downsample.1", ds[0], ds[1], (1, 1), any_s))
+        pairs.append(("conv3", "bn3", block.conv3, block.bn3, (1, 1), one))
+        if not all(_fold_pair_ok(conv, bn, k, s) for _, _, conv, bn, k, s in pairs):
+            continue
+        if getattr(block.bn3, "tail_avgpool", False):
+            pairs.pop()
+        plan += [(f"{name}.{c}", f"{name}.{b}") for c, b, *_ in pairs]
+    return plan
+
+
+class _FoldState:
+    """What a backbone keeps between folded forwards: the plan (made once: `enable_hip_batchnorm` drops this object), its
+    BatchNorm modules, and the `_capi.BnEvalTables` whose ONE launch per forward writes every layer's table -- inside a
+    hipGraph capture too, so a replay sees the running statistics of its own moment.  The descriptor table is re-built only
+    when a parameter or buffer has moved (`data_ptr`)."""
+
+    MISSING = ("folded BatchNorm: the descriptor table of the scale / shift launch does not exist yet (or a parameter has moved) and "
+               "cannot be uploaded while a hipGraph is being captured -- run one eager forward pass first")
+
+    def __init__(self, backbone):
+        mods = dict(backbone.named_modules())
+        self.plan = fold_plan(backbone)
+        self.bns = [mods[b] for _, b in self.plan]
+        self.tables = None
+
+    def begin(self):
+        layers = [(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps) for bn in self.bns]
+        if self.tables is None or self.tables.stale(layers):
+            if _capi.capture_id() != 0:
+                raise _capi.PeclrHipError(self.MISSING)
+            self.tables = _capi.BnEvalTables(layers)
+        self.tables.launch()
+        for bn, ss in zip(self.bns, self.tables.views):
+            bn.__dict__["_fold_ss"] = ss
+
+    def end(self):
+        for bn in self.bns:
+            bn.__dict__.pop("_fold_ss", None)
+
+
+def fold_applies(backbone: nn.Module, x: Tensor) -> bool:
+    """Does a forward of `backbone` on `x` take the folded path?  The switch, eval mode, no autograd, HIP kernels on, a HIP input
+    under bf16 / fp16 autocast -- and a plan that folds anything."""
+    if not (ROUTING.fold_eval_bn and ROUTING.conv16 and not backbone.training and not torch.is_grad_enabled() and x.is_cuda
+            and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") in _HALF
+            and getattr(getattr(backbone, "bn1", None), "hip", False)):
+        return False
+    st = backbone.__dict__.get("_fold_state")
+    if st is None:
+        st = backbone.__dict__["_fold_state"] = _FoldState(backbone)
+    return bool(st.plan)
+
+
+@contextlib.contextmanager
+def folded_eval_bn(backbone: nn.Module):
+    """One forward with the planned BatchNorm layers folded (after `fold_applies`): launches the tables, hands every planned
+    layer its slice (`_fold_ss`) for the duration, and takes the slices back."""
+    st = backbone.__dict__["_fold_state"]
+    st.begin()
+    try:
+        yield st
+    finally:
+        st.end()
+
+
+def fold_table_of(bn):
+    """This forward's scale / shift table of `bn`, or None (not planned, or no folded forward is running)."""
+    return bn.__dict__.get("_fold_ss")
+
+
 def enable_hip_batchnorm(module: nn.Module, enabled: bool = True, sync_group=None) -> int:
     """Switch every FusedBatchNormAct2d under `module` to the HIP kernels (or back).  The caller is
     responsible for feeding fp32 channels_last HIP tensors; anything else raises.
     sync_group: process group whose ranks share their batch statistics (None = per-rank)."""
     n = 0
     for m in module.modules():
+        m.__dict__.pop("_fold_state", None)             # (the folded-prediction plan and tables: re-made by the next folded forward)
         if isinstance(m, FusedBatchNormAct2d):
             m.hip = enabled
             m.sync_group = sync_group if enabled else None

@@ -486,6 +486,39 @@ __global__ __launch_bounds__(T) void bn2d_eval_params_kernel(int C, float eps, c
     scale_shift[C + c] = beta[c] - rm[c] * sc;
 }
 
+// ... of every layer of a table in one launch (prediction with the BatchNorm layers folded into the convolution epilogues:
+// one launch per forward instead of one per layer).  Thread = one channel of one layer; the arithmetic is the kernel's above.
+struct EvalTableDesc {      // device table entry (8 x int64)
+    const float* gamma; const float* beta; const float* rm; const float* rv;
+    float* out;             // the flat output buffer
+    int C; float eps;
+    int64_t offset;         // floats: this layer's [2][C] table starts at out + offset
+    int64_t chan_begin;     // channels of the entries before this one
+};
+
+__global__ __launch_bounds__(T) void bn2d_eval_tables_kernel(const EvalTableDesc* __restrict__ descs, int count, int total) {
+    static_assert(sizeof(EvalTableDesc) == 64, "8 x int64 entries");
+    const int gc = blockIdx.x * T + threadIdx.x;
+    if (gc >= total) return;
+    int lo = 0, hi = count - 1;                            // the last entry that begins at or before channel gc
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (descs[mid].chan_begin <= gc) lo = mid; else hi = mid - 1;
+    }
+    const EvalTableDesc e = descs[lo];
+    const int c = gc - (int)e.chan_begin;
+    if (c >= e.C) return;
+    const int C = e.C;
+    const float eps = e.eps;
+    const float* __restrict__ gamma = e.gamma; const float* __restrict__ beta = e.beta;
+    const float* __restrict__ rm = e.rm; const float* __restrict__ rv = e.rv;
+    float* __restrict__ scale_shift = e.out + e.offset;
+    const float invstd = 1.0f / sqrtf(rv[c] + eps);
+    const float sc = gamma[c] * invstd;
+    scale_shift[c] = sc;
+    scale_shift[C + c] = beta[c] - rm[c] * sc;
+}
+
 // ------------------------------------------------------------------ forward: apply
 // ReLU bit mask, 1 bit per element, layout [R][C/32] uint32 (bit c%32 of word (r, c/32)): independent
 // of the launch geometry.  The 32/W lanes that own one word are adjacent lanes of one wave in the same
@@ -1327,6 +1360,14 @@ extern "C" int peclr_bn2d_finalize_f32(float* partial, int n_split, int R, int C
         hipLaunchKernelGGL(bn2d_eval_params_kernel, dim3((C + T - 1) / T), dim3(T), 0, s, C, eps, gamma, beta, running_mean,
                            running_var, save_mean, save_invstd, scale_shift);
     }
+    return launch_status();
+}
+
+extern "C" int peclr_bn2d_eval_tables(const void* desc_table, int count, int total_channels, peclr_stream_t stream) {
+    if (!desc_table) return PECLR_ERR_NULL;
+    if (count <= 0 || total_channels < count) return PECLR_ERR_SHAPE;
+    hipLaunchKernelGGL(bn2d_eval_tables_kernel, dim3((total_channels + T - 1) / T), dim3(T), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const EvalTableDesc*>(desc_table), count, total_channels);
     return launch_status();
 }
 

@@ -41,7 +41,12 @@ struct HArgs {
     int M, N, K, lda, ldo, ldd;
     int add_h, add_w;                    // > 0: the addend holds every second pixel of add_h x add_w images (compact stride-2 gradient)
     const unsigned* add_mask;            // optional 1-bit mask of the addend ([M][N / 32])
-    const float* stat_shift;             // optional BatchNorm statistics of the output (layout of peclr_bn2d_stats' partials)
+    // EP bit 2 (folded eval-mode BatchNorm2d: a launch that can have no statistics) keeps its table where the statistics' shift
+    // lies, and its flag in the struct's tail padding: the argument block of every other instantiation is what it was, byte for byte
+    union {
+        const float* stat_shift;         // optional BatchNorm statistics of the output (layout of peclr_bn2d_stats' partials)
+        const float* fold_ss;            // EP bit 2: fp32 [2][N], scale row then shift row (bn2d_eval_params_kernel's scale_shift)
+    };
     float* stat_partial;
     int H, W, flip;                      // TAPS = 9: rows are the pixels of H x W images; flip = the input gradient's filter
     int stride, Hin, Win;                // stride = 2 (forward): rows are OUTPUT pixels of an Hin x Win input
@@ -57,7 +62,9 @@ struct HArgs {
     int bb_relu;
     float* bb_partial;
     int stream_out;                      // the output (and its addend) is larger than the caches: non-temporal epilogue
+    int fold_relu;                       // EP bit 2: ReLU after scale, shift and addend
 };
+static_assert(sizeof(HArgs) == 192, "the folded BatchNorm's fields add nothing to the kernels' argument block");
 
 // (H below: mfma.hpp's BF16 / F16.  Both operands arrive through its lds_dma16 family: every wait on the vm counter is written
 // by hand)
@@ -70,7 +77,10 @@ struct HArgs {
 // WM: 32-row MFMA tiles per wave (2 -> 256-row workgroup tile, 1 -> 128); NTL: 32-column tiles per wave (4 -> 128 output
 // columns per workgroup, 2 -> 64); TAPS = 9: 3x3 / padding 1 as an implicit GEMM, K ordered (tap, channel)
 // EP: epilogue features compiled in (registers are allotted for the largest path of an instantiation, and these launches live
-// on workgroups per CU): bit 0 = an addend (dense / compact stride-2 / 1-bit-masked), bit 1 = the BatchNorm backward reduction
+// on workgroups per CU): bit 0 = an addend (dense / compact stride-2 / 1-bit-masked), bit 1 = the BatchNorm backward reduction,
+// bit 2 = the eval-mode BatchNorm2d (+ ReLU) that consumes the output, folded in: out = round(relu(fmaf(acc, scale, shift) + addend))
+// -- ONE rounding, of the fp32 value, where convolution -> peclr_bn2d_apply rounds twice; dense addends only, no statistics, no
+// backward reduction, forward geometry only (the entry points refuse the rest), and none of their code is compiled in
 #ifdef PECLR_CONV_H_TIMING                                 // experiment builds only (tools/exp/ab): shader clocks per kernel phase
 __device__ unsigned long long conv_h_timing[8];
 #define PECLR_PHASE(k) do { if (threadIdx.x == 0 && blockIdx.x == 8) { const unsigned long long now_ = __builtin_readcyclecounter(); atomicAdd(&conv_h_timing[k], now_ - tphase); tphase = now_; } } while (0)
@@ -90,7 +100,8 @@ template <typename H, int WM, int TAPS, int NTL, int EP, int RING = 0>
 __global__ __launch_bounds__(256, (WM == 1 && RING == 0) ? ((EP & 2) ? 3 : 4) : 2) void conv_h_kernel(HArgs g) {
     static_assert(RING == 0 || (TAPS == 9 && RING % 64 == 0 && (WM == 2 || (WM == 1 && RING == 384))),
                   "ring stages: 3x3 on 256-row tiles (W <= 62) or, for rows of 63 ... 126 pixels, on 128-row tiles");
-    constexpr bool ADD = (EP & 1) != 0, BBF = (EP & 2) != 0;
+    constexpr bool ADD = (EP & 1) != 0, BBF = (EP & 2) != 0, FOLD = (EP & 4) != 0;
+    static_assert(!(FOLD && BBF), "the folded BatchNorm is a forward epilogue");
     constexpr int RM = 32 * WM, TM = 4 * RM;
     constexpr int NA = RING ? RING / 64 : RM / 16;       // A DMA instructions per wave and k-step / ring stage (16 rows x 64 B each)
     constexpr int NBD = NTL == 4 ? 2 : 1;                // B DMA instructions per wave and k-step
@@ -266,12 +277,16 @@ __global__ __launch_bounds__(256, (WM == 1 && RING == 0) ? ((EP & 2) ? 3 : 4) : 
     // statistics' shift of this lane's columns; the BatchNorm backward's mean / invstd / scale / shift of column tid (to LDS
     // after the loop).  Always NE load instructions, whatever the launch asks for, so that the DMA waits below stay exact
     // (without statistics they read the first floats of the packed weights)
-    constexpr int NE = NTL + (BBF ? 4 : 0);
+    // (FOLD has no such constants: its scale / shift rows are read in the epilogue, 16 bytes per lane, after the last DMA wait)
+    constexpr int NE = FOLD ? 0 : NTL + (BBF ? 4 : 0);
     float kshift[NTL];
-    {
+    if constexpr (!FOLD) {
         const float* sp = g.stat_partial ? g.stat_shift + n0 : reinterpret_cast<const float*>(g.Bp);
 #pragma unroll
         for (int y = 0; y < NTL; ++y) kshift[y] = sp[y * 32 + i];
+    } else {
+#pragma unroll
+        for (int y = 0; y < NTL; ++y) kshift[y] = 0.f;
     }
     float bcst[4] = {0.f, 0.f, 0.f, 0.f};
     if constexpr (BBF) {
@@ -399,14 +414,16 @@ __global__ __launch_bounds__(256, (WM == 1 && RING == 0) ? ((EP & 2) ? 3 : 4) : 
         for (int y = 0; y < NTL; ++y)
 #pragma unroll
             for (int r = 0; r < 16; r += 2) {
-                if (!ADD || !g.addend) {                  // (with an addend the rounding happens after the addition, below)
+                // (with an addend the rounding happens after the addition, below; FOLD: the accumulators stay fp32 until scale,
+                // shift, addend and ReLU are in -- one rounding, at the store)
+                if (!FOLD && (!ADD || !g.addend)) {
                     const unsigned p = H::pack2(acc[a][y][r], acc[a][y][r + 1]);
                     acc[a][y][r] = H::up(p & 0xFFFFu);
                     acc[a][y][r + 1] = H::up(p >> 16);
                 }
             }
     float* sl = reinterpret_cast<float*>(lds + 4 * 32 * XE * 4);      // [wave][2][128] column sums
-    if (g.stat_partial) {
+    if (!FOLD && g.stat_partial) {
         const bool full = !RING && row_block * TM + TM <= g.M;     // (uniform: whole tile inside the matrix)
         unsigned long long ring_ok = 0;                   // RING: bit r = row r of this wave's 64 is a pixel (not padding)
         if constexpr (RING != 0) ring_ok = __ballot(ring_row(m0 + lane) >= 0);
@@ -473,6 +490,14 @@ __global__ __launch_bounds__(256, (WM == 1 && RING == 0) ? ((EP & 2) ? 3 : 4) : 
         float sb[8], sg[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q) sb[q] = sg[q] = 0.f;
+        float fsc[8], fsh[8];                             // FOLD: scale / shift of this lane's eight columns
+        if constexpr (FOLD) {
+#pragma unroll
+            for (int q = 0; q < 8; q += 4) {
+                *reinterpret_cast<f32x4*>(fsc + q) = *reinterpret_cast<const f32x4*>(g.fold_ss + nt + ec + q);
+                *reinterpret_cast<f32x4*>(fsh + q) = *reinterpret_cast<const f32x4*>(g.fold_ss + g.N + nt + ec + q);
+            }
+        }
         if (BBF && g.bb_partial) {
 #pragma unroll
             for (int q = 0; q < 8; q += 4) {
@@ -496,7 +521,7 @@ __global__ __launch_bounds__(256, (WM == 1 && RING == 0) ? ((EP & 2) ? 3 : 4) : 
                 if (ADD && g.addend && om[a][jj] >= 0) {
                     size_t arow = m;
                     bool has = true;
-                    if (g.add_h) {
+                    if (!FOLD && g.add_h) {
                         const int w = m % g.add_w, hq = m / g.add_w, h = hq % g.add_h, img = hq / g.add_h;
                         has = ((h | w) & 1) == 0;
                         arow = ((size_t)img * (g.add_h >> 1) + (h >> 1)) * (g.add_w >> 1) + (w >> 1);
@@ -505,7 +530,7 @@ __global__ __launch_bounds__(256, (WM == 1 && RING == 0) ? ((EP & 2) ? 3 : 4) : 
                         const u32x4* asrc4 = reinterpret_cast<const u32x4*>(g.addend + arow * g.ldd + nt + ec);
                         const u32x4 tv = g.stream_out ? __builtin_nontemporal_load(asrc4) : *asrc4;
                         dv[jj] = make_uint4(tv[0], tv[1], tv[2], tv[3]);
-                        ab[jj] = g.add_mask ? (g.add_mask[(size_t)m * (g.N >> 5) + ((nt + ec) >> 5)] >> (ec & 31)) & 0xFFu : 0xFFu;
+                        ab[jj] = !FOLD && g.add_mask ? (g.add_mask[(size_t)m * (g.N >> 5) + ((nt + ec) >> 5)] >> (ec & 31)) & 0xFFu : 0xFFu;
                     }
                 }
                 if (BBF && g.bb_partial && om[a][jj] >= 0) {
@@ -527,8 +552,12 @@ __global__ __launch_bounds__(256, (WM == 1 && RING == 0) ? ((EP & 2) ? 3 : 4) : 
                 // instruction per half, and the reduction's normalisation (x - mean) * invstd keeps its factor for the end.
                 const unsigned dw[4] = {dv[jj].x, dv[jj].y, dv[jj].z, dv[jj].w};
                 unsigned ow[4];
+                if constexpr (FOLD) {
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) c[q] = fmaf(c[q], fsc[q], fsh[q]);
+                }
                 if (ADD && g.addend) {
-                    if (g.add_mask) {                     // 1-bit mask of the addend (an identity shortcut's (dy, mask) hand-over)
+                    if (!FOLD && g.add_mask) {            // 1-bit mask of the addend (an identity shortcut's (dy, mask) hand-over)
                         const unsigned bits = ab[jj];
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
@@ -538,6 +567,12 @@ __global__ __launch_bounds__(256, (WM == 1 && RING == 0) ? ((EP & 2) ? 3 : 4) : 
                     } else {                              // dense, or compact with zeros where the row has no entry
 #pragma unroll
                         for (int q = 0; q < 4; ++q) { c[2 * q] += H::lo(dw[q]); c[2 * q + 1] += H::hi(dw[q]); }
+                    }
+                }
+                if constexpr (FOLD) {
+                    if (g.fold_relu) {                    // (fmaxf drops a NaN, as peclr_bn2d_apply's ReLU does)
+#pragma unroll
+                        for (int q = 0; q < 8; ++q) c[q] = fmaxf(c[q], 0.f);
                     }
                 }
 #pragma unroll
@@ -733,9 +768,12 @@ int launch_h(const HArgs& g, int tile_rows, int taps, hipStream_t stream) {
 }
 
 template <typename H>
-int launch_ep(const HArgs& g, int tile_rows, int taps, hipStream_t stream) {
-    const int ep = (g.addend ? 1 : 0) | (g.bb_partial ? 2 : 0);
+int launch_ep(const HArgs& g, int tile_rows, int taps, bool fold, hipStream_t stream) {
+    const int ep = (g.addend ? 1 : 0) | (g.bb_partial ? 2 : 0) | (fold ? 4 : 0);
     switch (ep) {
+        case 4: return launch_h<H, 4>(g, tile_rows, taps, stream);
+        case 5: return launch_h<H, 5>(g, tile_rows, taps, stream);
+        case 6: case 7: return PECLR_ERR_UNSUPPORTED;
         case 0: return launch_h<H, 0>(g, tile_rows, taps, stream);
         case 1: return launch_h<H, 1>(g, tile_rows, taps, stream);
         case 2: return launch_h<H, 2>(g, tile_rows, taps, stream);
@@ -743,9 +781,12 @@ int launch_ep(const HArgs& g, int tile_rows, int taps, hipStream_t stream) {
     }
 }
 
-int dispatch(int dtype, const HArgs& g, int tile_rows, int taps, hipStream_t stream) {
-    if (dtype == PECLR_DTYPE_BF16) return launch_ep<BF16>(g, tile_rows, taps, stream);
-    if (dtype == PECLR_DTYPE_F16) return launch_ep<F16>(g, tile_rows, taps, stream);
+// fold: EP bit 2, g.fold_ss / g.fold_relu describe the BatchNorm2d folded into the epilogue
+int dispatch(int dtype, const HArgs& g, int tile_rows, int taps, hipStream_t stream, bool fold = false) {
+    // the folded BatchNorm is a forward epilogue over a plain output: no statistics, no backward reduction, dense addends only
+    if (fold && (!g.fold_ss || g.stat_partial || g.bb_partial || g.add_h || g.add_mask || g.flip || g.s2d)) return PECLR_ERR_UNSUPPORTED;
+    if (dtype == PECLR_DTYPE_BF16) return launch_ep<BF16>(g, tile_rows, taps, fold, stream);
+    if (dtype == PECLR_DTYPE_F16) return launch_ep<F16>(g, tile_rows, taps, fold, stream);
     return PECLR_ERR_UNSUPPORTED;
 }
 
@@ -796,40 +837,63 @@ extern "C" int peclr_conv_h_row_blocks(int NB, int H, int W, int Cout, int taps,
 
 // 1x1 / stride-1 product with the optional epilogues: dense addend (add_h = 0), compact stride-2 addend (add_h, add_w > 0),
 // 1-bit mask on the dense addend, BatchNorm statistics of the output, BatchNorm backward reduction.
-extern "C" int peclr_gemm_h(int dtype, int M, int N, int K, const void* A, int lda, const void* Bp, void* C, int ldc,
-                            const void* addend, int ldd, int add_h, int add_w, const unsigned* addend_mask, int tile_rows,
-                            const float* stat_shift, float* stat_partial, const peclr_bn_bwd_fuse* bb, peclr_stream_t stream) {
+namespace {
+// (fold_ss / fold_relu: peclr_gemm_h_bnact's folded BatchNorm; null for peclr_gemm_h)
+int gemm_h_checked(int dtype, int M, int N, int K, const void* A, int lda, const void* Bp, void* C, int ldc,
+                   const void* addend, int ldd, int add_h, int add_w, const unsigned* addend_mask, int tile_rows,
+                   const float* stat_shift, float* stat_partial, const peclr_bn_bwd_fuse* bb, const float* fold_ss, int fold_relu,
+                   peclr_stream_t stream) {
     if (!A || !Bp || !C || (stat_partial && !stat_shift)) return PECLR_ERR_NULL;
     if (bb && (stat_partial || !bb->x || !bb->mean || !bb->invstd || !bb->scale_shift || !bb->partial || ldc != N)) return PECLR_ERR_NULL;
     if (M <= 0 || N <= 0 || K <= 0 || N % 64 || K % HK) return PECLR_ERR_SHAPE;
     if (add_h && (!addend || add_h < 2 || add_w < 2 || add_h % 2 || add_w % 2 || M % (add_h * add_w))) return PECLR_ERR_SHAPE;
     if (addend_mask && (!addend || add_h || N % 32)) return PECLR_ERR_SHAPE;
     if (lda % 8 || lda < K || ldc % 8 || ldc < N || (addend && (ldd % 8 || ldd < N))) return PECLR_ERR_SHAPE;
-    if (!aligned16(A) || !aligned16(Bp) || !aligned16(C) || (addend && !aligned16(addend))) return PECLR_ERR_ALIGN;
+    if (!aligned16(A) || !aligned16(Bp) || !aligned16(C) || (addend && !aligned16(addend)) || !aligned16(fold_ss)) return PECLR_ERR_ALIGN;
     if (tile_rows == 0) tile_rows = pick_rows(M, N);
     if (tile_rows != 128 && tile_rows != 256) return PECLR_ERR_UNSUPPORTED;
     HArgs g;
     g.A = static_cast<const h16_t*>(A); g.Bp = Bp; g.addend = static_cast<const h16_t*>(addend); g.out = static_cast<h16_t*>(C);
     g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldo = ldc; g.ldd = ldd; g.add_h = add_h; g.add_w = add_w; g.add_mask = addend_mask;
     g.stat_shift = stat_shift; g.stat_partial = stat_partial;
+    if (fold_ss) g.fold_ss = fold_ss;                     // (shares the statistics' slot: checked exclusive in dispatch)
     g.H = g.W = 1; g.flip = 0; g.zeros = nullptr; g.stride = 1; g.Hin = g.Win = 1; g.s2d = 0; g.Mp = 0;
     set_bb(g, bb);
+    g.fold_relu = fold_relu ? 1 : 0;
     g.stream_out = stream_past_caches_h((size_t)M * N * 2);
-    return dispatch(dtype, g, tile_rows, 1, static_cast<hipStream_t>(stream));
+    return dispatch(dtype, g, tile_rows, 1, static_cast<hipStream_t>(stream), fold_ss != nullptr);
+}
+}  // namespace
+
+extern "C" int peclr_gemm_h(int dtype, int M, int N, int K, const void* A, int lda, const void* Bp, void* C, int ldc,
+                            const void* addend, int ldd, int add_h, int add_w, const unsigned* addend_mask, int tile_rows,
+                            const float* stat_shift, float* stat_partial, const peclr_bn_bwd_fuse* bb, peclr_stream_t stream) {
+    return gemm_h_checked(dtype, M, N, K, A, lda, Bp, C, ldc, addend, ldd, add_h, add_w, addend_mask, tile_rows, stat_shift, stat_partial,
+                          bb, nullptr, 0, stream);
+}
+
+// ... with the eval-mode BatchNorm2d (+ ReLU) behind it folded into the epilogue: C = round(relu(fmaf(A . W^T, scale, shift) + addend)),
+// scale_shift = that layer's fp32 [2][N] table (peclr_bn2d_eval_tables / peclr_bn2d_finalize_f32 in eval mode); dense addend only.
+extern "C" int peclr_gemm_h_bnact(int dtype, int M, int N, int K, const void* A, int lda, const void* Bp, void* C, int ldc,
+                                  const void* addend, int ldd, const float* scale_shift, int relu, int tile_rows, peclr_stream_t stream) {
+    if (!scale_shift) return PECLR_ERR_NULL;
+    return gemm_h_checked(dtype, M, N, K, A, lda, Bp, C, ldc, addend, ldd, 0, 0, nullptr, tile_rows, nullptr, nullptr, nullptr,
+                          scale_shift, relu, stream);
 }
 
 // 3x3 / padding 1 (taps = 9) or 1x1 (taps = 1) convolution of an NHWC tensor, stride 1 or 2: forward (flip = 0) or, stride 1,
 // the input gradient (flip = 1, X = dY, planes packed with transposed = 9).
-extern "C" int peclr_conv_h(int dtype, int NB, int H, int W, int Cin, int Cout, int taps, int stride, const void* X, const void* Bp,
-                            void* Y, int flip, int tile_rows, const void* zeros, const float* stat_shift, float* stat_partial,
-                            const peclr_bn_bwd_fuse* bb, peclr_stream_t stream) {
+namespace {
+int conv_h_checked(int dtype, int NB, int H, int W, int Cin, int Cout, int taps, int stride, const void* X, const void* Bp,
+                   void* Y, int flip, int tile_rows, const void* zeros, const float* stat_shift, float* stat_partial,
+                   const peclr_bn_bwd_fuse* bb, const float* fold_ss, int fold_relu, peclr_stream_t stream) {
     if (!X || !Bp || !Y || !zeros || (stat_partial && !stat_shift)) return PECLR_ERR_NULL;
     if (bb && (stat_partial || !bb->x || !bb->mean || !bb->invstd || !bb->scale_shift || !bb->partial || Cout % 32)) return PECLR_ERR_NULL;
     if (NB <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cout % 64 || Cin % HK || (taps != 1 && taps != 9) ||
         (stride != 1 && stride != 2) || (stride == 2 && (H % 2 || W % 2 || flip || bb)) || (taps == 1 && stride == 1))
         return PECLR_ERR_SHAPE;
     if ((long)NB * H * W > 0x7FFFFFFFL / 2) return PECLR_ERR_SHAPE;
-    if (!aligned16(X) || !aligned16(Bp) || !aligned16(Y) || !aligned16(zeros)) return PECLR_ERR_ALIGN;
+    if (!aligned16(X) || !aligned16(Bp) || !aligned16(Y) || !aligned16(zeros) || !aligned16(fold_ss)) return PECLR_ERR_ALIGN;
     const int Ho = H / stride, Wo = W / stride, M = NB * Ho * Wo;
     if (tile_rows == 0) tile_rows = ring_default(taps, stride, 0, Wo) ? PECLR_CONV_H_RING : pick_rows(M, Cout);
     if (tile_rows != 128 && tile_rows != 256 && tile_rows != PECLR_CONV_H_RING) return PECLR_ERR_UNSUPPORTED;
@@ -840,10 +904,28 @@ extern "C" int peclr_conv_h(int dtype, int NB, int H, int W, int Cin, int Cout, 
     g.A = static_cast<const h16_t*>(X); g.Bp = Bp; g.addend = nullptr; g.out = static_cast<h16_t*>(Y);
     g.M = M; g.N = Cout; g.K = taps * Cin; g.lda = Cin; g.ldo = Cout; g.ldd = Cout; g.add_h = g.add_w = 0; g.add_mask = nullptr;
     g.stat_shift = stat_shift; g.stat_partial = stat_partial;
+    if (fold_ss) g.fold_ss = fold_ss;
     g.H = Ho; g.W = Wo; g.flip = flip ? 1 : 0; g.zeros = static_cast<const h16_t*>(zeros); g.stride = stride; g.Hin = H; g.Win = W; g.s2d = 0;
     set_bb(g, bb);
+    g.fold_relu = fold_relu ? 1 : 0;
     g.stream_out = stream_past_caches_h((size_t)M * Cout * 2);
-    return dispatch(dtype, g, tile_rows, taps, static_cast<hipStream_t>(stream));
+    return dispatch(dtype, g, tile_rows, taps, static_cast<hipStream_t>(stream), fold_ss != nullptr);
+}
+}  // namespace
+
+extern "C" int peclr_conv_h(int dtype, int NB, int H, int W, int Cin, int Cout, int taps, int stride, const void* X, const void* Bp,
+                            void* Y, int flip, int tile_rows, const void* zeros, const float* stat_shift, float* stat_partial,
+                            const peclr_bn_bwd_fuse* bb, peclr_stream_t stream) {
+    return conv_h_checked(dtype, NB, H, W, Cin, Cout, taps, stride, X, Bp, Y, flip, tile_rows, zeros, stat_shift, stat_partial, bb,
+                          nullptr, 0, stream);
+}
+
+// ... forward, with the eval-mode BatchNorm2d (+ ReLU) behind it folded into the epilogue (as peclr_gemm_h_bnact)
+extern "C" int peclr_conv_h_bnact(int dtype, int NB, int H, int W, int Cin, int Cout, int taps, int stride, const void* X, const void* Bp,
+                                  void* Y, int tile_rows, const void* zeros, const float* scale_shift, int relu, peclr_stream_t stream) {
+    if (!scale_shift) return PECLR_ERR_NULL;
+    return conv_h_checked(dtype, NB, H, W, Cin, Cout, taps, stride, X, Bp, Y, 0, tile_rows, zeros, nullptr, nullptr, nullptr,
+                          scale_shift, relu, stream);
 }
 
 // Input gradient of the 3x3 / padding-1 / stride-2 convolution: four dense implicit GEMMs, one per parity class of input pixels.
@@ -860,7 +942,7 @@ extern "C" int peclr_conv3x3_s2_dgrad_h(int dtype, int NB, int Ho, int Wo, int C
     HArgs g;
     g.A = static_cast<const h16_t*>(dY); g.Bp = Bp; g.addend = nullptr; g.out = static_cast<h16_t*>(dX);
     g.M = M; g.N = Cin; g.K = 9 * Cout; g.lda = Cout; g.ldo = Cin; g.ldd = Cin; g.add_h = g.add_w = 0; g.add_mask = nullptr;
-    g.stat_shift = nullptr; g.stat_partial = nullptr;
+    g.stat_shift = nullptr; g.stat_partial = nullptr; g.fold_relu = 0;
     g.H = Ho; g.W = Wo; g.flip = 1; g.zeros = static_cast<const h16_t*>(zeros); g.stride = 1; g.Hin = Ho; g.Win = Wo; g.s2d = 1; g.Mp = 0;
     set_bb(g, bb);
     g.stream_out = stream_past_caches_h((size_t)M * 4 * Cin * 2);

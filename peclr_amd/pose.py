@@ -28,7 +28,10 @@ import torch
 from torch import Tensor, nn
 from torch.autograd.function import once_differentiable
 
+import contextlib
+
 from . import _capi
+from . import bn2d as _bn2d
 from . import resnet as _resnet
 from .bn2d import FusedBatchNormAct2d, enable_hip_batchnorm
 from .encoder import TailAvgPool
@@ -162,10 +165,19 @@ class RN25DwMLPref(nn.Module):
                 and self.backend_model.fc.weight.is_cuda)
 
     def features(self, img: Tensor) -> Tensor:
-        """The backbone up to the pooled [B, 2048] features (everything but `fc`)."""
+        """The backbone up to the pooled [B, 2048] features (everything but `fc`).  Under bf16 / fp16 autocast, in eval mode and
+        with `bn2d.ROUTING.fold_eval_bn` on, the bottleneck blocks apply their BatchNorm layers in the convolution epilogues
+        (`bn2d.fold_plan`): one launch writes all their tables first, once per call."""
         bb = self.backend_model
         if bb.bn1.hip:
             img = img.contiguous(memory_format=torch.channels_last)
+        if _bn2d.fold_applies(bb, img):
+            with _bn2d.folded_eval_bn(bb):
+                return self._features(bb, img)
+        return self._features(bb, img)
+
+    @staticmethod
+    def _features(bb, img: Tensor) -> Tensor:
         x = _resnet._bn(bb.bn1, _resnet._conv(bb.conv1, img, bb.bn1), relu=True)
         x = bb.layer4(bb.layer3(bb.layer2(bb.layer1(bb.maxpool(x)))))
         return torch.flatten(bb.avgpool(x), 1)
@@ -306,9 +318,20 @@ class FreiHANDPredictor:
     """pred_fh.py's two-pass prediction for a whole batch on the device.
 
     predict(images_u8 [B,H,W,3], K [B,3,3], scale [B]) -> float64 [B,21,3] HIP tensor, FreiHAND joint order, metres.
-    `last` keeps the pass-1 / pass-2 output dicts and T1 / T2 of the latest call (tests)."""
+    `last` keeps the pass-1 / pass-2 output dicts and T1 / T2 of the latest call (tests).
+    precision: "fp32" / 32 (the reference's, the default), or "bf16" / "fp16" / 16 (= fp16): both passes run under
+    `torch.autocast("cuda", dtype)` -- the backbone on the 16-bit convolution kernels, crops, head and lifting in fp32 / fp64 as
+    before.  fold_bn (16-bit only): the eval-mode BatchNorm layers of the bottleneck blocks in the convolution epilogues
+    (`bn2d.fold_plan`); None = the default for the precision, `FOLD_BN_DEFAULT`."""
 
-    def __init__(self, model: RN25DwMLPref, crop_size: int = CROP_SIZE, bbox_scale: float = BBOX_SCALE):
+    PRECISIONS = {"fp32": None, 32: None, "bf16": torch.bfloat16, "fp16": torch.float16, 16: torch.float16}
+    FOLD_BN_DEFAULT = True        # what fold_bn=None means for a 16-bit precision
+
+    def __init__(self, model: RN25DwMLPref, crop_size: int = CROP_SIZE, bbox_scale: float = BBOX_SCALE, precision="fp32", fold_bn=None):
+        if isinstance(precision, bool) or not isinstance(precision, (str, int)) or precision not in self.PRECISIONS:
+            raise ValueError(f"FreiHANDPredictor: precision must be one of 'fp32', 32, 'bf16', 'fp16', 16 -- got {precision!r}")
+        self.autocast_dtype = self.PRECISIONS[precision]
+        self.fold_bn = self.autocast_dtype is not None and (self.FOLD_BN_DEFAULT if fold_bn is None else bool(fold_bn))
         self.model, self.size = model, crop_size
         self.T1 = initial_transform(crop_size, bbox_scale)
         self.device = model.backend_model.fc.weight.device
@@ -320,6 +343,12 @@ class FreiHANDPredictor:
         self._graph = None
 
     def _passes(self, images: Tensor, K: Tensor, scale: Tensor):
+        if self.autocast_dtype is None:                   # fp32: exactly the launches of before (whatever the switches say)
+            return self._two_passes(images, K, scale)
+        with torch.autocast("cuda", dtype=self.autocast_dtype), _bn2d.routing(fold_eval_bn=self.fold_bn):
+            return self._two_passes(images, K, scale)
+
+    def _two_passes(self, images: Tensor, K: Tensor, scale: Tensor):
         m = self.model
         if m.training or not m.backend_model.bn1.hip:
             raise _capi.PeclrHipError("FreiHANDPredictor: the model must be in eval mode with the HIP kernels on (enable_hip())")

@@ -18,7 +18,8 @@ from typing import List, Type, Union
 import torch
 from torch import Tensor, nn
 
-from .bn2d import Conv2d, FusedBatchNormAct2d, checkpoint_block, fork_conv1x1
+from . import _capi
+from .bn2d import ROUTING, Conv2d, FusedBatchNormAct2d, _h_ok, _nchw, _rows, checkpoint_block, fold_table_of, fork_conv1x1
 
 
 def conv3x3(cin, cout, stride=1):
@@ -99,7 +100,38 @@ class Bottleneck(nn.Module):
     def forward(self, x: Tensor) -> Tensor:
         return checkpoint_block(self._run, x) if self.checkpoint else self._run(x)
 
+    def _folds(self, x: Tensor) -> bool:
+        """16-bit prediction with the BatchNorm layers in the convolution epilogues: the switch, eval mode, no autograd, 16-bit
+        NHWC input under the matching autocast, and this forward's tables (only planned blocks get any: `bn2d.fold_plan`)."""
+        return (fold_table_of(self.bn1) is not None and not self.training and not torch.is_grad_enabled() and _h_ok(self.conv1, x)
+                and x.shape[2] % self.conv2.stride[0] == 0 and x.shape[3] % self.conv2.stride[1] == 0)
+
+    def _run_folded(self, x: Tensor) -> Tensor:
+        """conv1 + bn1 + ReLU -> conv2 + bn2 + ReLU -> (downsample conv + its bn) -> conv3 + bn3 + shortcut + ReLU: four launches,
+        one rounding each, no BatchNorm pass.  The weights are the planes the training path packs (nothing is rescaled).  The
+        last block of the encoder (`tail_avgpool`: no table for bn3) keeps conv3 unfused and hands its output to the tail pass."""
+        dt = x.dtype
+        n, _, h, w = x.shape
+        planes = lambda conv: conv.x6_group.planes(conv, dt)[0]
+        s = self.conv2.stride[0]
+        out = _nchw(_capi.gemm_h_bnact(_rows(x), planes(self.conv1), self.conv1.out_channels, fold_table_of(self.bn1), relu=True), n, h, w)
+        out = _capi.conv_h_bnact(out, planes(self.conv2), self.conv2.out_channels, fold_table_of(self.bn2), relu=True, taps=9, stride=s)
+        identity = x
+        if self.downsample is not None:
+            dconv, dbn = self.downsample[0], self.downsample[1]
+            if dconv.stride[0] == 1:
+                identity = _nchw(_capi.gemm_h_bnact(_rows(x), planes(dconv), dconv.out_channels, fold_table_of(dbn), relu=False), n, h, w)
+            else:
+                identity = _capi.conv_h_bnact(x, planes(dconv), dconv.out_channels, fold_table_of(dbn), relu=False, taps=1, stride=2)
+        ss3 = fold_table_of(self.bn3)
+        if ss3 is None:
+            return _bn(self.bn3, _conv(self.conv3, out, self.bn3, sole_consumer=True), identity, relu=True)
+        n, _, h, w = out.shape
+        return _nchw(_capi.gemm_h_bnact(_rows(out), planes(self.conv3), self.conv3.out_channels, ss3, relu=True, addend=_rows(identity)), n, h, w)
+
     def _run(self, x: Tensor) -> Tensor:
+        if ROUTING.fold_eval_bn and self._folds(x):
+            return self._run_folded(x)
         # x has two consumers; in backward "conv1's input gradient + the residual branch's gradient" is one GEMM
         # (the 1x1 convolutions that run as in-tree GEMMs sum the statistics of the BatchNorm behind them in their epilogue)
         out, identity = fork_conv1x1(self.conv1, x, stats_for=self.bn1)

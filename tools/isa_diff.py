@@ -7,7 +7,8 @@ For a source tree, every file of csrc/Makefile's SRCS is compiled with the Makef
 Functions are paired by DEMANGLED name with namespace qualifiers dropped (moving a tag type such as BF16 out of an anonymous
 namespace renames every kernel instantiated on it and changes nothing else); comments, the `__hip_cuid_<hash of the source>`
 lines and the function numbers inside local labels are dropped.  Per file: `identical`, or the first function that differs;
-then, per kernel, the resource numbers of the code-object metadata on both sides (`a|b`, marked where they differ).
+then, per kernel, the resource numbers of the code-object metadata on both sides (`a|b`, marked where they differ; `-`: the
+kernel exists on one side only -- the functions both sides have are compared all the same).
 Text and numbers only.  Exit status 1 if anything differs.
 """
 import argparse
@@ -81,16 +82,22 @@ def compare(a_text, b_text, demangle=cxxfilt):
     """-> (verdict line, table rows, same?)"""
     (fa, ra), (fb, rb) = parse(a_text, demangle), parse(b_text, demangle)
     verdict = "identical (%d functions, %d kernels)" % (len(fa), len(ra))
+    common = [name for name in fa if name in fb]
+    changed = None
+    for name in common:
+        if fa[name] != fb[name]:
+            la, lb = fa[name].splitlines(), fb[name].splitlines()
+            at = next((i for i, (x, y) in enumerate(zip(la, lb)) if x != y), min(len(la), len(lb)))
+            changed = "DIFFERENT: %s, line %d of %d|%d:\n    a: %s\n    b: %s" % (
+                name, at, len(la), len(lb), la[at].strip() if at < len(la) else "<end>", lb[at].strip() if at < len(lb) else "<end>")
+            break
     if sorted(fa) != sorted(fb) or sorted(ra) != sorted(rb):
-        verdict = "DIFFERENT function lists: only in a %s, only in b %s" % (sorted(set(fa) - set(fb)), sorted(set(fb) - set(fa)))
-    else:
-        for name in fa:
-            if fa[name] != fb[name]:
-                la, lb = fa[name].splitlines(), fb[name].splitlines()
-                at = next((i for i, (x, y) in enumerate(zip(la, lb)) if x != y), min(len(la), len(lb)))
-                verdict = "DIFFERENT: %s, line %d of %d|%d:\n    a: %s\n    b: %s" % (
-                    name, at, len(la), len(lb), la[at].strip() if at < len(la) else "<end>", lb[at].strip() if at < len(lb) else "<end>")
-                break
+        # (a side that adds or drops functions: the ones both sides have are still compared, so that "N new kernels, every old
+        # one untouched" can be read off the report)
+        verdict = "DIFFERENT function lists: only in a %s, only in b %s\n  the %d functions both sides have: %s" % (
+            sorted(set(fa) - set(fb)), sorted(set(fb) - set(fa)), len(common), changed or "identical")
+    elif changed:
+        verdict = changed
     rows, same = [], verdict.startswith("identical")
     for name in sorted(set(ra) | set(rb)):
         x, y = ra.get(name), rb.get(name)

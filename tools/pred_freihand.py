@@ -31,6 +31,11 @@ def parse_args(argv=None):
     ap.add_argument("--data", required=True, help="FreiHAND root (evaluation_K.json, evaluation_scale.json, evaluation/rgb/)")
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--split", choices=("evaluation", "training"), default="evaluation")
+    # (optional extras stay out of the namespace unless given: `vars(args)` of a plain call is what it always was)
+    ap.add_argument("--precision", choices=("fp32", "bf16", "fp16"), default=argparse.SUPPRESS,
+                    help="default fp32; bf16 / fp16: the backbone under autocast on the 16-bit kernels (crops, head and lifting stay fp32 / fp64)")
+    ap.add_argument("--no-fold-bn", action="store_true", default=argparse.SUPPRESS,
+                    help="16-bit: keep the BatchNorm passes (default: folded into the convolution epilogues)")
     ap.add_argument("--eval", action="store_true", help="score against DIR/<split>_xyz.json instead of writing a submission")
     return ap.parse_args(argv)
 
@@ -70,7 +75,7 @@ def main(argv=None):
     model = RN25DwMLPref(model_type)
     model.load_state_dict(torch.load(args.model_path, map_location="cpu")["state_dict"])
     model = model.eval().to("cuda").enable_hip()
-    pred = FreiHANDPredictor(model)
+    pred = FreiHANDPredictor(model, precision=getattr(args, "precision", "fp32"), fold_bn=False if getattr(args, "no_fold_bn", False) else None)
     if args.eval:
         from peclr_amd.pose_eval import PoseEvaluator
 
