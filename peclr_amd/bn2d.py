@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import contextlib
 import dataclasses
+import functools
 import os
 
 from typing import Optional
@@ -356,6 +357,22 @@ def _new_absmax(x: Tensor):
     return _capi.absmax_slot(x.device) if (ROUTING.x6_pair and ROUTING.gemm_x6p and x.is_cuda and x.dtype == torch.float32) else None
 
 
+def _publish_absmax(x: Tensor, amax):
+    """The slot a forward pass over `x` writes its output's maximum to, published to the caller's list `amax` (None: the caller
+    wants no maximum); None when there is none."""
+    slot = _new_absmax(x) if amax is not None else None
+    if slot is not None:
+        amax[:] = [slot]
+    return slot
+
+
+def _tagged(t: Tensor, slot) -> Tensor:
+    """`t`, carrying the maximum `slot` its pass wrote (None: the pass wrote none)."""
+    if slot is not None:
+        _tag_absmax(t, slot)
+    return t
+
+
 def _pair_planes(conv, amax, which: int, planes):
     """What a packed-weight GEMM of `conv` runs on: (planes, {"pair": (amax, w_scale)}) -- the fp16-pair planes of matrix `which`
     (0 forward, 1 input gradient) when the activation operand's maximum `amax` is known -- else (planes[which], {}): the
@@ -365,6 +382,17 @@ def _pair_planes(conv, amax, which: int, planes):
         return planes[which], {}
     pp = group.planes(conv, "pair")
     return pp[which], {"pair": (amax, group.pair_scales(conv)[which])}
+
+
+def _launch_packed(kernel, a: Tensor, conv, amax, which: int, planes, *rest, rows_six_pair=None, **kw):
+    """ONE launch of a packed-weight kernel of `conv`: `kernel(a, planes of matrix which, *rest, **kw)` on what `_pair_planes`
+    picks -- the fp16-pair planes (and `pair=`) where the maximum `amax` of the activation operand `a` is known, else the
+    six-product planes.  rows_six_pair: None, or the kernel's `tile_rows` as (in the six-product form, in pair arithmetic) -- the
+    3x3 kernels' tile height depends on which arithmetic was taken."""
+    pl, pkw = _pair_planes(conv, amax, which, planes)
+    if rows_six_pair is not None:
+        kw["tile_rows"] = rows_six_pair[bool(pkw)]
+    return kernel(a, pl, *rest, **pkw, **kw)
 
 
 _HALF = (torch.bfloat16, torch.float16)
@@ -394,12 +422,10 @@ class _BN2dAct(torch.autograd.Function):
         # the ReLU mask can be recomputed from x unless a residual was added before it; then the
         # forward writes a 1-bit mask (or, for C % 32 != 0, the backward re-reads y)
         need_mask = relu and residual is not None
-        slot = _new_absmax(x) if (amax is not None and defer is None) else None
+        slot = _publish_absmax(x, amax if defer is None else None)
         y, save, ss, mask = _capi.bn2d_fwd(x, None if res_deferred is not None else residual, weight, bias, *stat_args, relu,
                                            want_mask=need_mask, apply=defer is None,
                                            residual_bn=res_deferred[:2] if res_deferred is not None else None, absmax=slot, **stat_kw)
-        if slot is not None:
-            amax[:] = [slot]
         ctx.handover = None
         if defer is not None:
             # (the fourth entry: what the consumer's backward needs to perform this layer's backward too -- `_dual_backward_ok`)
@@ -440,9 +466,7 @@ class _BN2dAct(torch.autograd.Function):
             _, dx, dgamma, dbeta, slot, owner = handed
             if owner is not ctx.handover:
                 raise _capi.PeclrHipError("fused BatchNorm2d: a shortcut layer's gradients arrived at another layer")
-            if slot is not None:
-                _tag_absmax(dx, slot)
-            return dx, dgamma, dbeta, None, None, None, None, None, None, None, None, None
+            return _tagged(dx, slot), dgamma, dbeta, None, None, None, None, None, None, None, None, None
         if handed is not None:
             dy = _dense_of(handed, dy.shape)
         dy = dy.to(x.dtype).contiguous(memory_format=torch.channels_last)
@@ -462,15 +486,12 @@ class _BN2dAct(torch.autograd.Function):
             slot_s = _new_absmax(xs)
             dx, dgamma, dbeta, dxs, dgamma_s, dbeta_s = _capi.bn2d_bwd_res_bn(dy, x, mask, save, ss, training, xs, save_s, ss_s,
                                                                               ctx.dual["training"], pre=pre, absmax=slot, absmax_s=slot_s)
-            if slot is not None:
-                _tag_absmax(dx, slot)
             dres = _lazy_grad(("bn", dxs, dgamma_s, dbeta_s, slot_s, ctx.dual), xs.shape, xs.device, xs.dtype)
-            return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None, None
+            return _tagged(dx, slot), dgamma, dbeta, dres, None, None, None, None, None, None, None, None
         dx, dgamma, dbeta, dres = _capi.bn2d_bwd(dy, x, y, mask, save, ss, training, relu,
                                                  has_res and ctx.needs_input_grad[3] and not lazy, sync_group=ctx.sync_group, pre=pre,
                                                  absmax=slot)
-        if slot is not None:
-            _tag_absmax(dx, slot)               # (the convolution whose output x is reads it off its `gy`: same tensor object)
+        _tagged(dx, slot)                       # (the convolution whose output x is reads it off its `gy`: same tensor object)
         if lazy:
             dres = _lazy_grad(("mask", dy, mask), x.shape, x.device, x.dtype)
         elif has_res and dres is None and ctx.needs_input_grad[3]:
@@ -507,10 +528,7 @@ class _Materialize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, placeholder, deferred, amax=None):
         x, ss, relu = deferred[:3]
-        slot = _new_absmax(x) if amax is not None else None
-        if slot is not None:
-            amax[:] = [slot]
-        return _capi.bn2d_apply(x, ss, relu=relu, absmax=slot)
+        return _capi.bn2d_apply(x, ss, relu=relu, absmax=_publish_absmax(x, amax))
 
     @staticmethod
     def backward(ctx, gy):
@@ -521,9 +539,7 @@ def _materialized(x: Tensor, deferred) -> Tensor:
     if len(deferred) > 3:
         deferred[3]["materialized"] = True      # (this reader's gradient comes back dense: `_dual_backward_ok`)
     amax = []
-    y = _Materialize.apply(x, deferred, amax)
-    if amax:
-        _tag_absmax(y, amax[0])
+    y = _tagged(_Materialize.apply(x, deferred, amax), amax[0] if amax else None)
     link = getattr(x, "_peclr_bn_link", None)
     if link:
         y._peclr_bn_link = link
@@ -536,10 +552,7 @@ class _BN2dReluPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, bn: "FusedBatchNormAct2d", pre=None, amax=None):
         training, sync, stat_args, stat_kw = bn._fwd_args(pre)
-        slot = _new_absmax(x) if amax is not None else None
-        if slot is not None:
-            amax[:] = [slot]
-        y, x_at_max, code, save, ss = _capi.bn2d_pool_fwd(x, weight, bias, *stat_args, absmax=slot, **stat_kw)
+        y, x_at_max, code, save, ss = _capi.bn2d_pool_fwd(x, weight, bias, *stat_args, absmax=_publish_absmax(x, amax), **stat_kw)
         ctx.save_for_backward(x, x_at_max, code, save, ss)
         ctx.cfg = (training, sync)
         return y
@@ -573,9 +586,7 @@ class _BN2dAddReluAvgPool(torch.autograd.Function):
         slot = _new_absmax(x)
         dx, dgamma, dbeta, dres = _capi.bn2d_avgpool_bwd(d_pooled.float().contiguous(), x, mask, save, ss, training,
                                                          sync_group=sync, absmax=slot)
-        if slot is not None:
-            _tag_absmax(dx, slot)
-        return dx, dgamma, dbeta, dres, None, None
+        return _tagged(dx, slot), dgamma, dbeta, dres, None, None
 
 
 # ---- weight gradients on a side stream.  In the backward pass a convolution's weight gradient (MFMA-bound) is
@@ -711,6 +722,15 @@ def _x6_wgrad_pays(rows: int, cout: int, cin: int) -> bool:
     return ROUTING.gemm_x6 and cout >= wide and cin >= wide and cout % 4 == 0 and cin % 4 == 0 and (rows >= 8192 or ROUTING.force)
 
 
+def _like_param(dw: Tensor, ref: Tensor, taps: int) -> Tensor:
+    """The slab sum `dw` [Cout, taps * Cin] of a weight-gradient kernel as a tensor shaped and strided like the parameter `ref`
+    (same memory): nine taps lie in the channels_last storage order [Cout][3][3][Cin]; one tap is [Cout][Cin] in memory under
+    either of the parameter's layouts."""
+    if taps == 9:
+        return dw.view(ref.shape[0], 3, 3, ref.shape[1]).permute(0, 3, 1, 2)      # = a channels_last [Cout, Cin, 3, 3] tensor
+    return dw.as_strided(ref.shape, ref.stride())
+
+
 def _wgrad_1x1_x6(gy: Tensor, x: Tensor, weight: Tensor, param=None):
     """d(weight) of a 1x1 / stride-1 convolution as dY^T X on the bf16 matrix cores (fp32 accuracy, deterministic
     split-K), shaped and strided like the weight; parked for `param` on the side stream when that mode is on."""
@@ -718,8 +738,7 @@ def _wgrad_1x1_x6(gy: Tensor, x: Tensor, weight: Tensor, param=None):
         gy2, x2 = _rows(gy), _rows(x)
         dw = (_capi.gemm_x6t(gy2, x2, tag="conv1x1_wgrad") if ROUTING.gemm_x6t
               else _capi.gemm_x6_tn(gy2, x2, tag="conv1x1_wgrad"))
-        ref = param if param is not None else weight
-        return dw.as_strided(ref.shape, ref.stride())       # same memory, the parameter's (channels_last) strides
+        return _like_param(dw, param if param is not None else weight, 1)
 
     return _on_side_stream(param, (gy, x), run)
 
@@ -772,15 +791,11 @@ def _wgrad_3x3_x6(gy: Tensor, x: Tensor, weight: Tensor, param=None, stride: int
     points at, all in one launch that splits dY once for the nine taps (peclr_gemm_x6t_f32, taps = 9; fp32 accuracy,
     fixed-order split-K: deterministic), written in the weight's own channels_last storage order [Cout][3][3][Cin].
     taps = 1 with stride 2: the 1x1 / stride-2 shortcut convolution (X read at every second pixel)."""
-    cin = x.shape[1]
-    cout, ho, wo = gy.shape[1:]
+    ho, wo = gy.shape[2:]
 
     def run():
         dw = _capi.gemm_x6t(_rows(gy), _rows(x), taps=taps, hw=(ho, wo), stride=stride, tag="conv3x3_wgrad" if taps == 9 else "conv1x1_wgrad")
-        if taps == 9:
-            return dw.view(cout, 3, 3, cin).permute(0, 3, 1, 2)      # = a channels_last [Cout, Cin, 3, 3] tensor
-        ref = param if param is not None else weight
-        return dw.as_strided(ref.shape, ref.stride())               # [Cout][Cin] in memory either way
+        return _like_param(dw, param if param is not None else weight, taps)
 
     return _on_side_stream(param, (gy, x), run)
 
@@ -794,10 +809,7 @@ def _conv1x1_fwd(x: Tensor, weight: Tensor, conv, planes, stats, amax) -> Tensor
     x2 = _rows(x)
     if planes is None:
         return _nchw(_capi.gemm_x6(x2, weight.detach().reshape(cout, cin), tag="conv1x1_fwd"), n, h, w)
-
-    def launch(**kw):
-        pl, pkw = _pair_planes(conv, amax, 0, planes)
-        return _capi.gemm_x6p(x2, pl, cout, tag="conv1x1_fwd", **pkw, **kw)
+    launch = functools.partial(_launch_packed, _capi.gemm_x6p, x2, conv, amax, 0, planes, cout, tag="conv1x1_fwd")
     return _nchw(_with_stats(stats, cout, launch), n, h, w)          # channels_last NCHW view of the NHWC result
 
 
@@ -807,8 +819,8 @@ def _wgrad_narrow_x6(gy: Tensor, x: Tensor, weight: Tensor, param=None, stride: 
     plain copies -- and dY^T X runs as ONE taps = 1 product on peclr_gemm_x6t_f32, so the result is fixed-order and
     bit-identical run to run like the wide route's.  The gather costs taps x the input, which is why this is the route of
     `routing(force=True)` only: at these sizes MIOpen's kernels are faster, but do not give the same bits on every run."""
-    n, cin, h, w = x.shape
-    cout, ho, wo = gy.shape[1:]
+    n, cin = x.shape[:2]
+    ho, wo = gy.shape[2:]
 
     def run():
         xn = x.permute(0, 2, 3, 1)                                      # the NHWC storage as it lies
@@ -819,19 +831,43 @@ def _wgrad_narrow_x6(gy: Tensor, x: Tensor, weight: Tensor, param=None, stride: 
             cols = xn[:, ::stride, ::stride]
         # (.contiguous(): a no-op except where a one-pixel-wide slice kept the input's row stride)
         dw = _capi.gemm_x6t(_rows(gy).contiguous(), cols.reshape(n * ho * wo, taps * cin).contiguous(), tag="conv3x3_wgrad" if taps == 9 else "conv1x1_wgrad")
-        if taps == 9:
-            return dw.view(cout, 3, 3, cin).permute(0, 3, 1, 2)      # = a channels_last [Cout, Cin, 3, 3] tensor
-        ref = param if param is not None else weight
-        return dw.as_strided(ref.shape, ref.stride())
+        return _like_param(dw, param if param is not None else weight, taps)
 
     return _on_side_stream(param, (gy, x), run)
+
+
+def _wgrad(gy: Tensor, x: Tensor, weight: Tensor, param, *, taps: int, stride: int, padding):
+    """d(weight) of an fp32 convolution of the fused backbone -- 1x1 / stride 1 (the bottleneck entry included), 3x3 / stride 1,
+    3x3 and 1x1 / stride 2 -- from the kernel that pays for its shape: THE place that decides it.  Returns dW shaped and strided
+    like the parameter, or None when the gradient was parked for `param` on the side stream.
+    1x1 / stride 1: dY^T X on the matrix cores where `_x6_wgrad_pays`.  The others: peclr_gemm_x6t_f32 with taps / stride
+    (`_wgrad_3x3_x6`) for channels_last weights of at least 64 channels (3x3 / stride 1: 64 output channels with
+    `ROUTING.x6_layer1_wgrad` -- the 64 x 64 block with two tap halves -- else 128; stride 2: both sides, and an input exactly twice
+    the output) whose output is at least 6 columns wide; narrower ones take the gathered, still fixed-order form
+    (`_wgrad_narrow_x6`) under `ROUTING.force` only.  Everything else: MIOpen (`_conv_wgrad`)."""
+    cin, cout = x.shape[1], gy.shape[1]
+    if taps == 1 and stride == 1:
+        if x.dtype == torch.float32 and _x6_wgrad_pays(x.shape[0] * x.shape[2] * x.shape[3], cout, cin):
+            return _wgrad_1x1_x6(gy, x, weight, param)
+        return _conv_wgrad(gy, x, weight, (1, 1), padding, param)
+    in_tree = ROUTING.gemm_x6t and weight.is_contiguous(memory_format=torch.channels_last) and cin % 4 == 0 and cout % 4 == 0
+    if stride == 1:
+        in_tree = in_tree and ROUTING.conv3x3_wgrad_x6 and cout >= (64 if ROUTING.x6_layer1_wgrad else 128)
+    else:
+        in_tree = (in_tree and ROUTING.conv_s2_wgrad_x6 and x.shape[2] == 2 * gy.shape[2] and x.shape[3] == 2 * gy.shape[3]
+                   and cout >= 64 and cin >= 64)
+    if in_tree and (x if stride == 1 else gy).shape[3] >= 6:
+        return _wgrad_3x3_x6(gy, x, weight, param, stride=stride, taps=taps)
+    if in_tree and ROUTING.force:             # fewer than 6 columns: the gathered, still fixed-order form
+        return _wgrad_narrow_x6(gy, x, weight, param, stride=stride, taps=taps)
+    return _conv_wgrad(gy, x, weight, (stride, stride), padding, param)
 
 
 class _Conv1x1Gemm(torch.autograd.Function):
     """1x1 / stride-1 convolution of an NHWC fp32 tensor as the GEMM it is, on the bf16 matrix cores at fp32 accuracy:
     forward y[R, Cout] = x[R, Cin] . W^T and / or the input gradient dx[R, Cin] = dy[R, Cout] . W, each where `_x6_pays`
     (weight planes packed once per step when the convolution belongs to an X6PackGroup: peclr_gemm_x6p_f32; otherwise
-    both operands split per workgroup: peclr_gemm_x6_f32); the other direction and small weight gradients stay on MIOpen."""
+    both operands split per workgroup: peclr_gemm_x6_f32); the other direction stays on MIOpen.  Weight gradient: `_wgrad`."""
 
     @staticmethod
     def forward(ctx, x, weight, conv, use_fwd: bool, use_bwd: bool, stats=None, link=None, amax=None):
@@ -852,16 +888,11 @@ class _Conv1x1Gemm(torch.autograd.Function):
         n, cin, h, w = x.shape
         cout = weight.shape[0]
         gy = gy.contiguous(memory_format=torch.channels_last)
-        dw = None
-        if ctx.needs_input_grad[1]:
-            dw = (_wgrad_1x1_x6(gy, x, weight, param) if _x6_wgrad_pays(n * h * w, cout, cin)
-                  else _conv_wgrad(gy, x, weight, (1, 1), (0, 0), param))
+        dw = _wgrad(gy, x, weight, param, taps=1, stride=1, padding=(0, 0)) if ctx.needs_input_grad[1] else None
         dx = None
         if ctx.needs_input_grad[0]:
             if use_bwd and planes is not None:
-                def launch(**kw):
-                    pl, pkw = _pair_planes(conv, _absmax_of(gy), 1, planes)
-                    return _capi.gemm_x6p(_rows(gy), pl, cin, tag="conv1x1_dgrad", **pkw, **kw)
+                launch = functools.partial(_launch_packed, _capi.gemm_x6p, _rows(gy), conv, _absmax_of(gy), 1, planes, cin, tag="conv1x1_dgrad")
                 dx = _nchw(_with_bn_bwd(ctx.link, x, launch), n, h, w)
             elif use_bwd:
                 wt = weight.detach().reshape(cout, cin).t().contiguous()          # [Cin][Cout]: K-contiguous B operand
@@ -876,8 +907,8 @@ class _Conv3x3Gemm(torch.autograd.Function):
     """3x3 / stride-1 / padding-1 convolution of an NHWC fp32 tensor as an implicit GEMM on the bf16 matrix cores at
     fp32 accuracy (peclr_conv3x3_x6p_f32: rows = output pixels, K = 9 Cin in (tap, channel) order, the activation rows
     of a k-step read from the pixel its tap points at, the filter from planes packed once per step): forward and input
-    gradient (the same kernel on the flipped filter); the weight gradient as nine dY^T X products in one launch
-    (`_wgrad_3x3_x6`)."""
+    gradient (the same kernel on the flipped filter); the weight gradient where `_wgrad` routes it (nine dY^T X products in one
+    launch: `_wgrad_3x3_x6`)."""
 
     @staticmethod
     def forward(ctx, x, weight, conv, stats=None, link=None, amax=None):
@@ -886,45 +917,30 @@ class _Conv3x3Gemm(torch.autograd.Function):
         ctx.cfg = (conv, planes)
         ctx.link = link
         cout = weight.shape[0]
-
-        def launch(**kw):
-            pl, pkw = _pair_planes(conv, amax, 0, planes)
-            tile_rows = ROUTING.conv3x3_pair_tile_rows if pkw else ROUTING.conv3x3_tile_rows
-            return _capi.conv3x3_x6p(x, pl, cout, tag="conv3x3_fwd", tile_rows=tile_rows, **pkw, **kw)
-        return _with_stats(stats, cout, launch)
+        return _with_stats(stats, cout, functools.partial(_launch_packed, _capi.conv3x3_x6p, x, conv, amax, 0, planes, cout, tag="conv3x3_fwd",
+                                                          rows_six_pair=(ROUTING.conv3x3_tile_rows, ROUTING.conv3x3_pair_tile_rows)))
 
     @staticmethod
     def backward(ctx, gy):
         x, weight = ctx.saved_tensors
         conv, planes = ctx.cfg
         gy = gy.contiguous(memory_format=torch.channels_last)
-        dw = None
-        if ctx.needs_input_grad[1]:
-            in_tree = (ROUTING.gemm_x6t and ROUTING.conv3x3_wgrad_x6 and weight.is_contiguous(memory_format=torch.channels_last)
-                       and x.shape[1] % 4 == 0 and gy.shape[1] % 4 == 0
-                       and gy.shape[1] >= (64 if ROUTING.x6_layer1_wgrad else 128))   # (64 output channels: the 64 x 64 block with two tap halves)
-            if in_tree and x.shape[3] >= 6:
-                dw = _wgrad_3x3_x6(gy, x, weight, conv.weight)
-            elif in_tree and ROUTING.force:          # fewer than 6 columns: the gathered, still fixed-order form
-                dw = _wgrad_narrow_x6(gy, x, weight, conv.weight)
-            else:
-                dw = _conv_wgrad(gy, x, weight, (1, 1), (1, 1), conv.weight)
+        dw = _wgrad(gy, x, weight, conv.weight, taps=9, stride=1, padding=(1, 1)) if ctx.needs_input_grad[1] else None
         dx = None
         if ctx.needs_input_grad[0]:
-            def launch(**kw):
-                pl, pkw = _pair_planes(conv, _absmax_of(gy), 1, planes)
-                tile_rows = ROUTING.conv3x3_pair_tile_rows if pkw else ROUTING.conv3x3_tile_rows
-                return _capi.conv3x3_x6p(gy, pl, x.shape[1], flip=True, tag="conv3x3_dgrad", tile_rows=tile_rows, **pkw, **kw)
-            dx = _with_bn_bwd(ctx.link, x, launch)
+            dx = _with_bn_bwd(ctx.link, x, functools.partial(
+                _launch_packed, _capi.conv3x3_x6p, gy, conv, _absmax_of(gy), 1, planes, x.shape[1], flip=True, tag="conv3x3_dgrad",
+                rows_six_pair=(ROUTING.conv3x3_tile_rows, ROUTING.conv3x3_pair_tile_rows)))
         return dx, dw, None, None, None, None
 
 
 class _ConvS2Gemm(torch.autograd.Function):
     """Stride-2 3x3 (padding 1) / 1x1 convolution of an NHWC fp32 tensor: forward on the six-product kernel
     (peclr_conv_s2_x6p_f32: the k-step's tap and the stride select the source pixel; BatchNorm statistics of the output
-    in the epilogue), weight gradient on peclr_gemm_x6t_f32 with stride 2.  Input gradient: 3x3 -- one dense implicit GEMM
-    per parity class of input pixels (peclr_conv3x3_s2_dgrad_x6p_f32); 1x1 shortcut -- kept compact for the block's
-    entry-gradient GEMM (`_compact_grad`) where that is its consumer, else MIOpen."""
+    in the epilogue), weight gradient where `_wgrad` routes it (peclr_gemm_x6t_f32 with stride 2).  Input gradient: 3x3 -- one
+    dense implicit GEMM per parity class of input pixels (peclr_conv3x3_s2_dgrad_x6p_f32); 1x1 shortcut -- kept compact for the
+    block's entry-gradient GEMM where that is its consumer, else scattered into zeros (`_shortcut_grad`); MIOpen where the input
+    is not exactly twice the output."""
 
     @staticmethod
     def forward(ctx, x, weight, conv, stats=None, compact=False, link=None, amax=None):
@@ -934,11 +950,8 @@ class _ConvS2Gemm(torch.autograd.Function):
         ctx.link = link
         planes = _x6_planes(conv)
         cout, taps = weight.shape[0], weight.shape[2] * weight.shape[3]
-
-        def launch(**kw):
-            pl, pkw = _pair_planes(conv, amax, 0, planes)
-            return _capi.conv_s2_x6p(x, pl, cout, taps, tag="conv_s2_fwd", tile_rows=ROUTING.s2_tile_rows if taps == 9 else 0, **pkw, **kw)
-        return _with_stats(stats, cout, launch)
+        return _with_stats(stats, cout, functools.partial(_launch_packed, _capi.conv_s2_x6p, x, conv, amax, 0, planes, cout, taps,
+                                                          tag="conv_s2_fwd", tile_rows=ROUTING.s2_tile_rows if taps == 9 else 0))
 
     @staticmethod
     def backward(ctx, gy):
@@ -946,37 +959,24 @@ class _ConvS2Gemm(torch.autograd.Function):
         conv = ctx.conv
         gy = gy.contiguous(memory_format=torch.channels_last)
         pad = list(conv.padding)
-        dw = None
-        if ctx.needs_input_grad[1]:
-            taps = weight.shape[2] * weight.shape[3]
-            in_tree = (ROUTING.gemm_x6t and ROUTING.conv_s2_wgrad_x6 and weight.is_contiguous(memory_format=torch.channels_last)
-                       and x.shape[2] == 2 * gy.shape[2] and x.shape[3] == 2 * gy.shape[3]
-                       and x.shape[1] % 4 == 0 and gy.shape[1] % 4 == 0 and gy.shape[1] >= 64 and x.shape[1] >= 64)
-            if in_tree and gy.shape[3] >= 6:
-                dw = _wgrad_3x3_x6(gy, x, weight, conv.weight, stride=2, taps=taps)
-            elif in_tree and ROUTING.force:          # fewer than 6 output columns: the gathered, still fixed-order form
-                dw = _wgrad_narrow_x6(gy, x, weight, conv.weight, stride=2, taps=taps)
-            else:
-                dw = _conv_wgrad(gy, x, weight, (2, 2), pad, conv.weight)
+        taps = weight.shape[2] * weight.shape[3]
+        dw = _wgrad(gy, x, weight, conv.weight, taps=taps, stride=2, padding=pad) if ctx.needs_input_grad[1] else None
         dx = None
         if ctx.needs_input_grad[0]:
-            if weight.shape[2] == 1 and x.shape[2] == 2 * gy.shape[2] and x.shape[3] == 2 * gy.shape[3]:
+            halved = x.shape[2] == 2 * gy.shape[2] and x.shape[3] == 2 * gy.shape[3]       # the input is exactly twice the output
+            if weight.shape[2] == 1 and halved:
                 # 1x1 shortcut: dY . W over the OUTPUT pixels only (three quarters of the input gradient are zeros).  Where it
                 # goes straight into the block's fused entry gradient it stays compact (the consumer adds it at the even
                 # pixels: no 4x larger tensor); elsewhere (BasicBlock networks: the block input is a plain tensor) it is
                 # scattered into zeros here -- never MIOpen's input gradient, whose fp32 1x1 / stride-2 solver adds with float
                 # atomics (a different last bit every run: tools/exp/two_outcome.py)
-                pl, kw = _pair_planes(conv, _absmax_of(gy), 1, _x6_planes(conv))
-                dc = _capi.gemm_x6p(_rows(gy), pl, x.shape[1], tag="conv_s2_dgrad", **kw)
-                dx = _compact_grad(dc, x.shape) if (ctx.compact and not torch.is_anomaly_enabled()) else _expand_compact(dc, x.shape)
-            elif (ROUTING.conv_s2_dgrad_x6 and weight.shape[2] == 3 and x.shape[2] == 2 * gy.shape[2] and x.shape[3] == 2 * gy.shape[3]
-                  and x.shape[1] % 64 == 0 and gy.shape[1] % 16 == 0):
+                dc = _launch_packed(_capi.gemm_x6p, _rows(gy), conv, _absmax_of(gy), 1, _x6_planes(conv), x.shape[1], tag="conv_s2_dgrad")
+                dx = _shortcut_grad(dc, x.shape, ctx.compact)
+            elif ROUTING.conv_s2_dgrad_x6 and weight.shape[2] == 3 and halved and x.shape[1] % 64 == 0 and gy.shape[1] % 16 == 0:
                 # 3x3: one dense implicit GEMM per parity class of input pixels (1, 2, 2, 4 taps); dx is the gradient arriving
                 # at the BatchNorm layer whose output x is: reduced in the epilogue
-                def launch(**kw):
-                    pl, pkw = _pair_planes(conv, _absmax_of(gy), 1, _x6_planes(conv))
-                    return _capi.conv3x3_s2_dgrad_x6p(gy, pl, x.shape[1], tile_rows=ROUTING.s2_tile_rows, **pkw, **kw)
-                dx = _with_bn_bwd(ctx.link, x, launch)
+                dx = _with_bn_bwd(ctx.link, x, functools.partial(_launch_packed, _capi.conv3x3_s2_dgrad_x6p, gy, conv, _absmax_of(gy), 1,
+                                                                 _x6_planes(conv), x.shape[1], tile_rows=ROUTING.s2_tile_rows))
             else:
                 dx = torch.ops.aten.convolution_backward(gy, x, weight, None, [2, 2], pad, [1, 1], False, [0, 0], 1, [True, False, False])[0]
         return dx, dw, None, None, None, None, None
@@ -1008,6 +1008,13 @@ def _lazy_grad(payload, shape, device, dtype=torch.float32) -> Tensor:
 
 def _compact_grad(dc: Tensor, shape) -> Tensor:
     return _lazy_grad(("s2", dc), shape, dc.device, dc.dtype)
+
+
+def _shortcut_grad(dc: Tensor, shape, compact: bool) -> Tensor:
+    """The input gradient (of `shape`) of a 1x1 / stride-2 shortcut convolution from its compact product `dc`: handed over compact
+    where the consumer takes that form (`compact`: the block's entry-gradient GEMM) -- not under anomaly mode, whose checks would
+    meet the NaN view -- else scattered into zeros."""
+    return _compact_grad(dc, shape) if (compact and not torch.is_anomaly_enabled()) else _expand_compact(dc, shape)
 
 
 def _take_lazy(g: Tensor):
@@ -1119,12 +1126,7 @@ def _wgrad_h(gy: Tensor, x: Tensor, conv, stride: int):
     w = conv.weight
     taps = w.shape[2] * w.shape[3]
     if ROUTING.wgrad16 and w.is_contiguous(memory_format=torch.channels_last) and _capi.wgrad_h_ok(gy, x, taps, stride):
-        def run():
-            dw = _capi.wgrad_h(gy, x, taps, stride)       # [Cout, taps * Cin] fp32
-            if taps == 9:
-                return dw.view(w.shape[0], 3, 3, w.shape[1]).permute(0, 3, 1, 2)    # = a channels_last [Cout, Cin, 3, 3] tensor
-            return dw.as_strided(w.shape, w.stride())
-        return _on_side_stream(w, (gy, x), run)
+        return _on_side_stream(w, (gy, x), lambda: _like_param(_capi.wgrad_h(gy, x, taps, stride), w, taps))     # [Cout, taps * Cin] fp32
     return _conv_wgrad(gy, x, w, conv.stride, conv.padding, w)
 
 
@@ -1132,7 +1134,7 @@ class _ConvH(torch.autograd.Function):
     """A residual block's convolution on 16-bit (bf16 / fp16 autocast) NHWC activations, in-tree (csrc/conv_h.hip): 1x1 or
     3x3 / padding 1, stride 1 or 2 -- forward with the consuming BatchNorm's statistics in the epilogue, input gradient with
     the producing BatchNorm's backward reduction in the epilogue, both from weight planes packed once per step out of the
-    fp32 master weights.  Same hand-over protocols as the fp32 classes above (`stats`, `link`, compact shortcut gradient)."""
+    fp32 master weights.  Same hand-over protocols as the fp32 classes above (`stats`, `link`, `_shortcut_grad`)."""
 
     @staticmethod
     def forward(ctx, x, weight, conv, stats=None, link=None, compact=False):
@@ -1169,7 +1171,7 @@ class _ConvH(torch.autograd.Function):
                 # 1x1 / stride-2 shortcut: dY . W over the OUTPUT pixels only; the block's entry-gradient GEMM adds it at the even
                 # pixels, any other consumer gets it scattered into zeros (deterministic, unlike MIOpen's atomics)
                 dc = _capi.gemm_h(_rows(gy), planes[1], cin, tag="conv_s2_dgrad")
-                dx = _compact_grad(dc, x.shape) if (ctx.compact and not torch.is_anomaly_enabled()) else _expand_compact(dc, x.shape)
+                dx = _shortcut_grad(dc, x.shape, ctx.compact)
             else:
                 dx = torch.ops.aten.convolution_backward(gy, x, conv.weight.detach().to(x.dtype), None, [2, 2], [0, 0], [1, 1], False,
                                                          [0, 0], 1, [True, False, False])[0]
@@ -1239,28 +1241,20 @@ class Conv2d(nn.Conv2d):
         w = self.weight
         return st.fresh(w, 0, lambda: st.pack([w], lambda: _capi.StemPlanes(w.detach(), dtype), self.STEM_MISSING))
 
-    def forward(self, x: Tensor, stats_for=None, sole_consumer: bool = False) -> Tensor:
-        """stats_for: the BatchNorm2d that consumes the output -- when this convolution runs as an in-tree GEMM its
-        epilogue sums that layer's training statistics (one pass over the activation less).
-        sole_consumer: the caller guarantees that NOTHING else reads `x` (bn -> conv inside a residual block): only then
-        is this convolution's input gradient THE gradient arriving at the BatchNorm layer that produced x, and only then
-        may the input-gradient GEMM perform that layer's backward reduction in its epilogue.  A block input (x also feeds
-        the shortcut) is not: BasicBlock.conv1 passes False."""
-        bn_link = _bn_link_of if sole_consumer else (lambda t: None)
-        deferred = getattr(x, "_peclr_deferred", None)
-        if deferred is not None:
-            x = _materialized(x, tuple(deferred))       # a BatchNorm layer's placeholder (its apply pass was left to another reader): written after all
+    def _in_tree(self, x: Tensor, stats, bn_link):
+        """conv(x) on the in-tree arm that takes it -- the stem, the 16-bit kernels, fp32 1x1 / stride 1, stride 2, 3x3 / stride 1, in
+        that order; each arm has its own eligibility test and its own rule for the BatchNorm hand-over `link` -- or None: no arm does.
+        stats: None or [bn], for the arm's epilogue (`_with_stats`); bn_link: `_bn_link_of`, or a function returning None."""
         if (self.hip_stem and ROUTING.stem and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3
                 and x.shape[2] >= 8 and x.shape[3] >= 8 and x.is_contiguous(memory_format=torch.channels_last)
                 and self.weight.is_cuda and self.weight.dtype == torch.float32):
-            stats = [stats_for] if stats_for is not None else None
-            return _attach_stats(_StemConv.apply(x, self.weight, self, stats), stats)
+            return _StemConv.apply(x, self.weight, self, stats)
+        grad = torch.is_grad_enabled() and x.requires_grad
+        # a 1x1 / stride-2 shortcut whose input gradient goes straight into the block's entry-gradient GEMM hands it over compact
+        compact = (ROUTING.s2_dgrad_compact and self.kernel_size == (1, 1) and self.stride == (2, 2)
+                   and getattr(x, "_peclr_compact_ok", False) and grad)
         if self.hip_gemm and _h_ok(self, x) and (x.shape[2] % self.stride[0] == 0 and x.shape[3] % self.stride[1] == 0):
-            stats = [stats_for] if stats_for is not None else None
-            grad = torch.is_grad_enabled() and x.requires_grad
-            compact = (ROUTING.s2_dgrad_compact and self.kernel_size == (1, 1) and self.stride == (2, 2)
-                       and getattr(x, "_peclr_compact_ok", False) and grad)
-            return _attach_stats(_ConvH.apply(x, self.weight, self, stats, bn_link(x) if grad else None, compact), stats)
+            return _ConvH.apply(x, self.weight, self, stats, bn_link(x) if grad else None, compact)
         # what every fp32 in-tree arm below needs of its input: an NHWC fp32 device tensor outside autocast
         fp32 = (self.hip_gemm and x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled("cuda") and x.dim() == 4
                 and x.is_contiguous(memory_format=torch.channels_last))
@@ -1268,25 +1262,37 @@ class Conv2d(nn.Conv2d):
                 and self.bias is None):
             rows = x.shape[0] * x.shape[2] * x.shape[3]
             use_fwd = _x6_pays(rows, self.out_channels, self.in_channels)
-            use_bwd = _x6_pays(rows, self.in_channels, self.out_channels) and torch.is_grad_enabled() and x.requires_grad
+            use_bwd = _x6_pays(rows, self.in_channels, self.out_channels) and grad
             use_wgrad = (_x6_wgrad_pays(rows, self.out_channels, self.in_channels) and torch.is_grad_enabled()
                          and self.weight.requires_grad)
             if use_fwd or use_bwd or use_wgrad:
-                stats = [stats_for] if (stats_for is not None and use_fwd) else None
-                return _attach_stats(_Conv1x1Gemm.apply(x, self.weight, self, use_fwd, use_bwd, stats, bn_link(x) if use_bwd else None, _absmax_of(x)), stats)
+                return _Conv1x1Gemm.apply(x, self.weight, self, use_fwd, use_bwd, stats if use_fwd else None,
+                                          bn_link(x) if use_bwd else None, _absmax_of(x))
         if (fp32 and ROUTING.conv_s2_x6 and ROUTING.gemm_x6p and getattr(self, "x6_group", None) is not None and self.stride == (2, 2)
                 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
                 and (x.shape[0] * x.shape[2] * x.shape[3] >= 32768 or ROUTING.force)):
-            stats = [stats_for] if stats_for is not None else None
-            compact = (ROUTING.s2_dgrad_compact and self.kernel_size == (1, 1) and getattr(x, "_peclr_compact_ok", False)
-                       and torch.is_grad_enabled() and x.requires_grad)
-            link = bn_link(x) if (torch.is_grad_enabled() and x.requires_grad and self.kernel_size == (3, 3)) else None
-            return _attach_stats(_ConvS2Gemm.apply(x, self.weight, self, stats, compact, link, _absmax_of(x)), stats)
+            link = bn_link(x) if (grad and self.kernel_size == (3, 3)) else None
+            return _ConvS2Gemm.apply(x, self.weight, self, stats, compact, link, _absmax_of(x))
         if (fp32 and ROUTING.conv3x3_x6 and ROUTING.gemm_x6p and getattr(self, "x6_group", None) is not None and self.kernel_size == (3, 3)
                 and self.stride == (1, 1)
                 and (x.shape[0] * x.shape[2] * x.shape[3] >= 8192 or ROUTING.force)):
-            stats = [stats_for] if stats_for is not None else None
-            return _attach_stats(_Conv3x3Gemm.apply(x, self.weight, self, stats, bn_link(x), _absmax_of(x)), stats)
+            return _Conv3x3Gemm.apply(x, self.weight, self, stats, bn_link(x), _absmax_of(x))
+        return None
+
+    def forward(self, x: Tensor, stats_for=None, sole_consumer: bool = False) -> Tensor:
+        """stats_for: the BatchNorm2d that consumes the output -- when this convolution runs as an in-tree GEMM its
+        epilogue sums that layer's training statistics (one pass over the activation less).
+        sole_consumer: the caller guarantees that NOTHING else reads `x` (bn -> conv inside a residual block): only then
+        is this convolution's input gradient THE gradient arriving at the BatchNorm layer that produced x, and only then
+        may the input-gradient GEMM perform that layer's backward reduction in its epilogue.  A block input (x also feeds
+        the shortcut) is not: BasicBlock.conv1 passes False."""
+        deferred = getattr(x, "_peclr_deferred", None)
+        if deferred is not None:
+            x = _materialized(x, tuple(deferred))       # a BatchNorm layer's placeholder (its apply pass was left to another reader): written after all
+        stats = [stats_for] if stats_for is not None else None
+        y = self._in_tree(x, stats, _bn_link_of if sole_consumer else (lambda t: None))
+        if y is not None:
+            return _attach_stats(y, stats)              # (the ONE place the epilogue's statistics are handed on)
         if (_overlap_stream() is not None and x.is_cuda and torch.is_grad_enabled() and self.bias is None
                 and self.groups == 1 and self.dilation == (1, 1) and isinstance(self.padding, tuple)
                 and x.is_contiguous(memory_format=torch.channels_last) and self.weight.requires_grad):
@@ -1320,7 +1326,8 @@ class _ForkConv1x1(torch.autograd.Function):
     """Bottleneck entry: (x, W) -> (conv1x1(x, W), x).  The block input feeds both the first convolution and
     the identity branch, so its gradient is dY W + d_identity: autograd runs MIOpen's dgrad and then an
     elementwise add over the block input (3.6 % of the fp32 step); here both are ONE fp32 GEMM with the
-    identity gradient added in the epilogue.  Small shapes' forward and weight gradient stay on MIOpen."""
+    identity gradient added in the epilogue.  Small shapes' forward stays on MIOpen; the weight gradient goes where `_wgrad`
+    routes it."""
 
     @staticmethod
     def forward(ctx, x, weight, conv, stats=None, link=None, flags=None, amax=None):
@@ -1350,9 +1357,7 @@ class _ForkConv1x1(torch.autograd.Function):
         dw = None
         gy = gy.to(x.dtype)
         if ctx.needs_input_grad[1]:
-            gyc = gy.contiguous(memory_format=torch.channels_last)
-            dw = (_wgrad_1x1_x6(gyc, x, weight, ctx.param) if (x.dtype == torch.float32 and _x6_wgrad_pays(n * h * w, cmid, cin))
-                  else _conv_wgrad(gyc, x, weight, (1, 1), (0, 0), ctx.param))
+            dw = _wgrad(gy.contiguous(memory_format=torch.channels_last), x, weight, ctx.param, taps=1, stride=1, padding=(0, 0))
         dx = None
         if ctx.needs_input_grad[0]:
             gy = gy.contiguous(memory_format=torch.channels_last)
@@ -1361,12 +1366,8 @@ class _ForkConv1x1(torch.autograd.Function):
             if ctx.use_bwd and ctx.planes is not None:
                 # fp32 on the bf16 matrix cores (exact 3-way split, six products; `use_bwd`: fp32 only), weight planes packed once
                 # per step; the result is the gradient arriving at the previous block's last BatchNorm: reduced in the epilogue
-                addend = _entry_addend(gid, lazy, x)
-
-                def launch(**kw):
-                    pl, pkw = _pair_planes(ctx.conv, _absmax_of(gy), 1, ctx.planes)
-                    return _entry_gemm(a, pl, cin, **addend, **pkw, **kw)
-                out = _with_bn_bwd(ctx.link, x, launch)
+                out = _with_bn_bwd(ctx.link, x, functools.partial(_launch_packed, _entry_gemm, a, ctx.conv, _absmax_of(gy), 1, ctx.planes, cin,
+                                                                  **_entry_addend(gid, lazy, x)))
             else:
                 dense = gid if lazy is None else _dense_of(lazy, x.shape)        # (these kernels add a dense tensor only)
                 d = _rows(dense.to(x.dtype).contiguous(memory_format=torch.channels_last))
@@ -1425,19 +1426,17 @@ def fork_conv1x1(conv: nn.Conv2d, x: Tensor, stats_for=None):
           and conv.padding == (0, 0) and conv.groups == 1 and conv.bias is None and x.requires_grad
           and x.is_contiguous(memory_format=torch.channels_last)
           and conv.weight.shape[0] % 8 == 0 and conv.weight.shape[1] % 8 == 0)
-    if ok and _h_ok(conv, x):
-        stats = [stats_for] if stats_for is not None else None
-        out, identity = _ForkConvH.apply(x, conv.weight, conv, stats, _bn_link_of(x))
-        identity._peclr_compact_ok = True         # its backward takes the shortcut's gradient compact / as (dy, mask)
-        return _attach_stats(out, stats), identity
     if ok:
         stats = [stats_for] if stats_for is not None else None
-        flags = []
-        out, identity = _ForkConv1x1.apply(x, conv.weight, conv, stats, _bn_link_of(x), flags, _absmax_of(x))
-        if _absmax_of(x) is not None:
-            _tag_absmax(identity, _absmax_of(x))            # (the same values: the downsample convolution reads them too)
-        if flags and flags[0]:
-            identity._peclr_compact_ok = True     # a 1x1 / stride-2 shortcut may hand its input gradient over compact
+        if _h_ok(conv, x):
+            out, identity = _ForkConvH.apply(x, conv.weight, conv, stats, _bn_link_of(x))
+            identity._peclr_compact_ok = True         # its backward takes the shortcut's gradient compact / as (dy, mask)
+        else:
+            flags, amax = [], _absmax_of(x)
+            out, identity = _ForkConv1x1.apply(x, conv.weight, conv, stats, _bn_link_of(x), flags, amax)
+            _tagged(identity, amax)                   # (the same values: the downsample convolution reads them too)
+            if flags and flags[0]:
+                identity._peclr_compact_ok = True     # a 1x1 / stride-2 shortcut may hand its input gradient over compact
         return _attach_stats(out, stats), identity
     return (conv(x, stats_for=stats_for) if isinstance(conv, Conv2d) else conv(x)), x     # (x has two consumers: no link)
 
@@ -1521,10 +1520,7 @@ class FusedBatchNormAct2d(nn.BatchNorm2d):
                     residual, res_deferred = _materialized(residual, res_deferred), None
             amax = [] if (ROUTING.x6_pair and x.dtype == torch.float32) else None
             if pool:
-                y = _BN2dReluPool.apply(x, self.weight, self.bias, self, pre, amax)
-                if amax:
-                    _tag_absmax(y, amax[0])
-                return y
+                return _tagged(_BN2dReluPool.apply(x, self.weight, self.bias, self, pre, amax), amax[0] if amax else None)
             if self.tail_avgpool and relu and residual is not None and self.num_features % 32 == 0:
                 return _BN2dAddReluAvgPool.apply(x, self.weight, self.bias, residual, self, pre)
             link = [] if (ROUTING.bn_bwd_in_gemm and torch.is_grad_enabled() and x.requires_grad) else None
@@ -1535,8 +1531,7 @@ class FusedBatchNormAct2d(nn.BatchNorm2d):
                 if not relu and isinstance(consumer, FusedBatchNormAct2d) and consumer._takes_deferred_residual(x):
                     defer = []
             y = _BN2dAct.apply(x, self.weight, self.bias, residual, self, relu, pre, link, lazy_res, defer, res_deferred, amax)
-            if amax:
-                _tag_absmax(y, amax[0])         # max |y|, on the device: the "pair" GEMMs that read y derive its power of two from it
+            _tagged(y, amax[0] if amax else None)   # max |y|, on the device: the "pair" GEMMs that read y derive its power of two from it
             if link:
                 y._peclr_bn_link = link
             if defer:

@@ -720,6 +720,32 @@ def test_compact_shortcut_gradient_protocol():
     assert torch.equal(dense, dy * bits.view(2, 3, 3, 64).permute(0, 3, 1, 2)) and not B._COMPACT
 
 
+def test_shortcut_gradient_is_compact_only_for_a_consumer_that_takes_it_and_never_under_anomaly_mode():
+    """bn2d._shortcut_grad, the hand-over of a 1x1 / stride-2 shortcut's input gradient (fp32 and 16-bit classes alike): the NaN
+    view carrying the compact product when the consumer takes that form, the product scattered into zeros otherwise -- and under
+    anomaly mode, whose NaN checks would trip over the view."""
+    from peclr_amd import bn2d as B
+
+    dc = torch.arange(2 * 2 * 3 * 5, dtype=torch.float32).view(2 * 2 * 3, 5) + 1.0
+    shape = (2, 5, 4, 6)
+    dense = torch.zeros(shape)
+    dense[:, :, ::2, ::2] = dc.view(2, 2, 3, 5).permute(0, 3, 1, 2)
+    B.end_backward()
+    try:
+        lazy = B._shortcut_grad(dc, shape, True)
+        assert tuple(lazy.shape) == shape and not any(lazy.stride()) and torch.isnan(lazy).all() and len(B._COMPACT) == 1
+        assert B._take_compact(lazy) is dc and not B._COMPACT
+        for compact in (False, 0, None):
+            full = B._shortcut_grad(dc, shape, compact)
+            assert torch.equal(full, dense) and full.is_contiguous(memory_format=torch.channels_last) and not B._COMPACT
+        with torch.autograd.detect_anomaly(check_nan=False):
+            full = B._shortcut_grad(dc, shape, True)
+        assert torch.equal(full, dense) and not B._COMPACT
+        assert not torch.is_anomaly_enabled() and torch.isnan(B._shortcut_grad(dc, shape, True)).all()
+    finally:
+        B.end_backward()
+
+
 def test_capture_guard_holds_the_collector_and_restores_it(monkeypatch):
     """Trainer._capturing (hipGraph lifetime): garbage is collected before the capture starts, the
     cyclic collector is off while it records (also when the recorded code raises) and back afterwards; the graph object is
@@ -864,6 +890,32 @@ def test_absmax_tag_is_dropped_when_the_tensor_is_written_after_the_pass_that_me
         assert bn2d._absmax_of(t) is slot
     with bn2d.routing(x6_pair=False):
         assert bn2d._absmax_of(t) is None
+
+
+def test_absmax_slot_is_published_where_one_is_wanted_and_tagged_where_one_was_written(monkeypatch):
+    """bn2d._publish_absmax / _tagged, the two halves of the slot protocol of the BatchNorm passes: a pass whose caller passed a
+    list makes a slot (where `_new_absmax` gives one: fp32 device tensors with pair arithmetic on) and the list comes back as
+    [slot]; no list, or no slot -> None and the list untouched.  The result of the pass is tagged with the slot it wrote, and left
+    alone when there was none."""
+    from peclr_amd import bn2d
+
+    x = torch.ones(2, 3)
+    amax = []
+    assert bn2d._new_absmax(x) is None                                     # a CPU tensor: no pass leaves a maximum
+    assert bn2d._publish_absmax(x, amax) is None and amax == [] and bn2d._publish_absmax(x, None) is None
+    slots = []
+    monkeypatch.setattr(bn2d, "_new_absmax", lambda t: slots.append(torch.zeros(1)) or slots[-1])
+    assert bn2d._publish_absmax(x, None) is None and not slots             # nobody wants one: none is made
+    slot = bn2d._publish_absmax(x, amax)
+    assert slot is slots[0] and len(slots) == 1 and len(amax) == 1 and amax[0] is slot
+    again = bn2d._publish_absmax(x, amax)
+    assert again is slots[1] and len(amax) == 1 and amax[0] is again       # the list is replaced, not extended
+    with bn2d.routing(x6_pair=True):
+        y = torch.ones(4)
+        assert bn2d._tagged(y, None) is y and bn2d._absmax_of(y) is None
+        assert bn2d._tagged(y, slot) is y and bn2d._absmax_of(y) is slot
+        y.add_(1.0)
+        assert bn2d._absmax_of(y) is None                                  # (the tag carries the version it was written at)
 
 
 def test_stats_hand_over_fills_the_list_only_when_the_batchnorm_takes_statistics(monkeypatch):
@@ -1024,3 +1076,123 @@ def test_nhwc_row_views_and_entry_addend_keywords():
     mask = torch.zeros(30, 1, dtype=torch.int32)
     kw = B._entry_addend(gid, ("mask", x, mask), x)
     assert kw["addend"].data_ptr() == x.data_ptr() and tuple(kw["addend"].shape) == (30, 8) and kw["addend_mask"] is mask
+
+
+# ---- which kernel computes an fp32 convolution's weight gradient.  Rows: (geometry, Cin, Cout, input H = W, weight layout, routing
+# overrides, expected route).  Geometries: "1x1" (_Conv1x1Gemm), "entry" (_ForkConv1x1), "3x3" (_Conv3x3Gemm), "3x3s2" / "1x1s2"
+# (_ConvS2Gemm); batch 2, so 64 x 64 pixels are 8 192 rows and 8 x 8 are 128.  Routes: "x6t" (peclr_gemm_x6t_f32 with the
+# geometry's taps / stride), "tn" (peclr_gemm_x6_tn_f32), "narrow" (the gathered one-tap product on peclr_gemm_x6t_f32), "miopen".
+_CL, _NCHW = "channels_last", "contiguous"
+_WGRAD_ROUTES = [
+    # 1x1 / stride 1: `_x6_wgrad_pays` -- both widths >= 64 (128 without the layer1 kernels), 8 192 rows unless forced
+    ("1x1", 64, 256, 64, _CL, {}, "x6t"), ("1x1", 256, 64, 64, _NCHW, {}, "x6t"), ("1x1", 64, 256, 8, _CL, {}, "miopen"),
+    ("1x1", 64, 256, 8, _CL, {"force": True}, "x6t"), ("1x1", 32, 64, 64, _CL, {}, "miopen"), ("1x1", 64, 32, 64, _CL, {"force": True}, "miopen"),
+    ("1x1", 64, 256, 64, _CL, {"gemm_x6": False}, "miopen"), ("1x1", 64, 256, 64, _CL, {"gemm_x6t": False}, "miopen"),
+    ("1x1", 128, 256, 64, _CL, {"gemm_x6t": False}, "tn"), ("1x1", 128, 128, 64, _NCHW, {"gemm_x6t": False}, "tn"),
+    ("1x1", 64, 256, 64, _CL, {"x6_layer1_wgrad": False}, "miopen"), ("1x1", 128, 128, 64, _CL, {"x6_layer1_wgrad": False}, "x6t"),
+    ("1x1", 64, 64, 64, _CL, {"conv3x3_wgrad_x6": False}, "x6t"), ("1x1", 64, 64, 64, _CL, {"conv_s2_wgrad_x6": False}, "x6t"),
+    # the bottleneck entry: the same rule, fp32 activations only
+    ("entry", 256, 64, 64, _CL, {}, "x6t"), ("entry", 64, 64, 64, _NCHW, {}, "x6t"), ("entry", 256, 64, 8, _CL, {}, "miopen"),
+    ("entry", 256, 64, 8, _CL, {"force": True}, "x6t"), ("entry", 256, 32, 64, _CL, {}, "miopen"), ("entry", 256, 128, 64, _CL, {"gemm_x6t": False}, "tn"),
+    ("entry", 256, 64, 64, _CL, {"gemm_x6": False}, "miopen"), ("entry", 256, 64, 64, _CL, {"x6_layer1_wgrad": False}, "miopen"),
+    ("entry-bf16", 256, 64, 64, _CL, {}, "miopen"), ("entry-bf16", 256, 64, 8, _CL, {"force": True}, "miopen"),
+    # 3x3 / stride 1: channels_last weights, 64 output channels (128 without the layer1 kernels), 6 columns (else gathered, forced only)
+    ("3x3", 128, 128, 8, _CL, {}, "x6t"), ("3x3", 64, 64, 64, _CL, {}, "x6t"), ("3x3", 32, 64, 8, _CL, {}, "x6t"), ("3x3", 64, 32, 8, _CL, {}, "miopen"),
+    ("3x3", 256, 256, 8, _CL, {}, "x6t"), ("3x3", 256, 256, 4, _CL, {}, "miopen"), ("3x3", 256, 256, 4, _CL, {"force": True}, "narrow"),
+    ("3x3", 128, 128, 8, _NCHW, {}, "miopen"), ("3x3", 128, 128, 4, _NCHW, {"force": True}, "miopen"),
+    ("3x3", 64, 64, 8, _CL, {"x6_layer1_wgrad": False}, "miopen"), ("3x3", 64, 128, 8, _CL, {"x6_layer1_wgrad": False}, "x6t"),
+    ("3x3", 128, 128, 8, _CL, {"gemm_x6t": False}, "miopen"), ("3x3", 128, 128, 8, _CL, {"conv3x3_wgrad_x6": False}, "miopen"),
+    ("3x3", 128, 128, 8, _CL, {"conv_s2_wgrad_x6": False}, "x6t"), ("3x3", 128, 128, 8, _CL, {"gemm_x6": False}, "x6t"),
+    # 3x3 / stride 2: both widths >= 64, the input exactly twice the output, 6 OUTPUT columns
+    ("3x3s2", 128, 128, 16, _CL, {}, "x6t"), ("3x3s2", 64, 64, 16, _CL, {"x6_layer1_wgrad": False}, "x6t"), ("3x3s2", 256, 256, 8, _CL, {}, "miopen"),
+    ("3x3s2", 256, 256, 8, _CL, {"force": True}, "narrow"), ("3x3s2", 32, 64, 16, _CL, {}, "miopen"), ("3x3s2", 64, 32, 16, _CL, {"force": True}, "miopen"),
+    ("3x3s2", 128, 128, 15, _CL, {}, "miopen"), ("3x3s2", 128, 128, 15, _CL, {"force": True}, "miopen"), ("3x3s2", 128, 128, 16, _NCHW, {}, "miopen"),
+    ("3x3s2", 128, 128, 16, _CL, {"gemm_x6t": False}, "miopen"), ("3x3s2", 128, 128, 16, _CL, {"conv_s2_wgrad_x6": False}, "miopen"),
+    ("3x3s2", 128, 128, 16, _CL, {"conv3x3_wgrad_x6": False}, "x6t"), ("3x3s2", 128, 128, 16, _CL, {"gemm_x6": False}, "x6t"),
+    # 1x1 / stride 2 (the shortcut): the same rule, one tap; either spelling of a [Cout, Cin, 1, 1] weight's strides is channels_last
+    ("1x1s2", 256, 512, 16, _CL, {}, "x6t"), ("1x1s2", 64, 128, 16, _NCHW, {}, "x6t"), ("1x1s2", 256, 512, 8, _CL, {}, "miopen"),
+    ("1x1s2", 256, 512, 8, _NCHW, {"force": True}, "narrow"), ("1x1s2", 32, 64, 16, _CL, {}, "miopen"), ("1x1s2", 256, 512, 15, _CL, {"force": True}, "miopen"),
+    ("1x1s2", 256, 512, 16, _CL, {"conv_s2_wgrad_x6": False}, "miopen"), ("1x1s2", 256, 512, 16, _CL, {"gemm_x6t": False}, "miopen"),
+]
+
+
+@pytest.mark.parametrize("geometry,cin,cout,hw,layout,overrides,route", _WGRAD_ROUTES,
+                         ids=[f"{r[0]}-{r[1]}to{r[2]}-{r[3]}px-{r[4]}-{','.join(f'{k}={v}' for k, v in r[5].items()) or 'default'}" for r in _WGRAD_ROUTES])
+def test_which_kernel_computes_an_fp32_weight_gradient(monkeypatch, geometry, cin, cout, hw, layout, overrides, route):
+    """The backward of each fp32 convolution class, driven by hand on CPU tensors with the kernels replaced by recorders: which
+    one is called, with which taps / hw / stride / tag and operand shapes, and -- the recorders return counting tensors -- that
+    the gradient that comes back is the kernel's [Cout, taps * Cin] result seen in the parameter's shape and strides, in place."""
+    import types
+
+    from peclr_amd import _capi
+    from peclr_amd import bn2d as B
+
+    calls = []
+
+    def counting(kind, m, k, **what):
+        out = torch.arange(m * k, dtype=torch.float32).view(m, k)
+        calls.append(dict(what, kind=kind, out=out))
+        return out
+
+    monkeypatch.setattr(_capi, "gemm_x6t", lambda a, b, taps=1, hw=None, stride=1, tag="gemm_x6t": counting(
+        "x6t", a.shape[1], taps * b.shape[1], a=tuple(a.shape), b=tuple(b.shape), taps=taps, hw=hw, stride=stride, tag=tag))
+    monkeypatch.setattr(_capi, "gemm_x6_tn", lambda a, b, tag="gemm_x6_tn": counting(
+        "tn", a.shape[1], b.shape[1], a=tuple(a.shape), b=tuple(b.shape), taps=1, hw=None, stride=1, tag=tag))
+    monkeypatch.setattr(_capi, "wgrad_h", lambda *a, **k: calls.append(dict(kind="wgrad_h")))
+    monkeypatch.setattr(_capi, "wgrad_h_ok", lambda *a, **k: calls.append(dict(kind="wgrad_h_ok")) or True)
+    monkeypatch.setattr(B, "_conv_wgrad", lambda gy, x, weight, stride, padding, param=None: counting(
+        "miopen", weight.shape[0], weight[0].numel(), a=tuple(gy.shape), b=tuple(x.shape), stride=tuple(stride), padding=tuple(padding),
+        weight=weight, param=param).view(weight.shape))
+
+    ksize, stride = (3 if geometry.startswith("3x3") else 1), (2 if geometry.endswith("s2") else 1)
+    taps, pad = ksize * ksize, ksize // 2
+    ho = (hw + 2 * pad - ksize) // stride + 1
+    dtype = torch.bfloat16 if geometry.endswith("bf16") else torch.float32
+    x = torch.zeros(2, cin, hw, hw, dtype=dtype).contiguous(memory_format=torch.channels_last)
+    gy = torch.zeros(2, cout, ho, ho, dtype=dtype).contiguous(memory_format=torch.channels_last)
+    conv = torch.nn.Conv2d(cin, cout, ksize, stride=stride, padding=pad, bias=False)
+    if layout == _CL:
+        conv = conv.to(memory_format=torch.channels_last)
+    weight = conv.weight
+    ctx = types.SimpleNamespace(saved_tensors=(x, weight), needs_input_grad=(False, True) + (None,) * 6, conv=conv, link=None, compact=False,
+                                param=weight, planes=None, use_bwd=False)
+    base = dict(force=False, gemm_x6=True, gemm_x6t=True, x6_layer1_wgrad=True, conv3x3_wgrad_x6=True, conv_s2_wgrad_x6=True)
+    assert B._overlap_stream() is None                                      # (`_on_side_stream` runs inline)
+    with B.routing(**{**base, **overrides}):
+        if geometry == "1x1":
+            ctx.cfg = (conv, False, None)
+            dw = B._Conv1x1Gemm.backward(ctx, gy)[1]
+        elif geometry.startswith("entry"):
+            dw = B._ForkConv1x1.backward(ctx, gy, torch.zeros_like(x))[1]
+        elif geometry == "3x3":
+            ctx.cfg = (conv, None)
+            dw = B._Conv3x3Gemm.backward(ctx, gy)[1]
+        else:
+            dw = B._ConvS2Gemm.backward(ctx, gy)[1]
+    assert len(calls) == 1, [c["kind"] for c in calls]
+    call = calls[0]
+    rows = 2 * ho * ho
+    assert call["kind"] == {"narrow": "x6t"}.get(route, route)
+    assert call["a"] == ((rows, cout) if route != "miopen" else tuple(gy.shape))
+    if route == "miopen":
+        assert call["b"] == tuple(x.shape) and call["stride"] == (stride, stride) and call["padding"] == (pad, pad)
+        assert call["weight"] is weight and call["param"] is weight
+        assert dw.data_ptr() == call["out"].data_ptr() and tuple(dw.shape) == tuple(weight.shape) and dw.is_contiguous()
+        return
+    tag = "conv3x3_wgrad" if taps == 9 else "conv1x1_wgrad"
+    if route == "narrow":                       # the taps' pixels gathered: ONE one-tap product over [rows, taps * Cin]
+        assert (call["b"], call["taps"], call["hw"], call["stride"], call["tag"]) == ((rows, taps * cin), 1, None, 1, tag)
+    elif geometry in ("1x1", "entry"):
+        assert (call["b"], call["taps"], call["hw"], call["stride"], call["tag"]) == ((2 * hw * hw, cin), 1, None, 1, tag)
+    else:
+        assert (call["b"], call["taps"], call["hw"], call["stride"], call["tag"]) == ((2 * hw * hw, cin), taps, (ho, ho), stride, tag)
+    # the layout: the kernel's [Cout][tap][Cin] rows, in place, under the parameter's shape (and, for one tap, strides)
+    out = call["out"]
+    assert dw.data_ptr() == out.data_ptr() and tuple(dw.shape) == tuple(weight.shape)
+    if taps == 9:
+        assert dw.stride() == (9 * cin, 1, 3 * cin, cin) and dw.is_contiguous(memory_format=torch.channels_last)
+        assert torch.equal(dw, out.view(cout, 3, 3, cin).permute(0, 3, 1, 2))
+        assert float(dw[1, 2, 1, 0]) == 1 * 9 * cin + (1 * 3 + 0) * cin + 2
+    else:
+        assert dw.stride() == weight.stride() and torch.equal(dw.reshape(cout, cin), out)
+        assert float(dw[1, 2, 0, 0]) == cin + 2
