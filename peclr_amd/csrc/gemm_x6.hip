@@ -121,13 +121,13 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void gemm_x6_nt128_kernel(X6A
                     b[y][p] = *reinterpret_cast<const uint4*>(lb + p * PLANE_B + (wn * 32 * NB + 32 * y + i) * XLD + ko);
             }
             // smallest products first; the accumulators are independent chains
-#define PECLR_X6(P, Q)                                                        \
-    _Pragma("unroll") for (int y = 0; y < NB; ++y) {                          \
-        acc[0][y] = mma_bf16(a[0][P], b[y][Q], acc[0][y]);                         \
-        acc[1][y] = mma_bf16(a[1][P], b[y][Q], acc[1][y]);                         \
-    }
-            PECLR_X6(2, 0) PECLR_X6(0, 2) PECLR_X6(1, 1) PECLR_X6(1, 0) PECLR_X6(0, 1) PECLR_X6(0, 0)
-#undef PECLR_X6
+#pragma unroll
+            for (int pr = 0; pr < 6; ++pr)
+#pragma unroll
+                for (int y = 0; y < NB; ++y) {
+                    acc[0][y] = mma_bf16(a[0][X6_PA[pr]], b[y][X6_QB[pr]], acc[0][y]);
+                    acc[1][y] = mma_bf16(a[1][X6_PA[pr]], b[y][X6_QB[pr]], acc[1][y]);
+                }
         }
     };
     gload(0);
@@ -278,13 +278,13 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void gemm_x6_tn128_kernel(X6A
                 for (int y = 0; y < NB; ++y)
                     b[y][p] = *reinterpret_cast<const uint4*>(lb + p * PLANE_B + (wn * 32 * NB + 32 * y + i) * XLD + ko);
             }
-#define PECLR_X6(P, Q)                                                        \
-    _Pragma("unroll") for (int y = 0; y < NB; ++y) {                          \
-        acc[0][y] = mma_bf16(a[0][P], b[y][Q], acc[0][y]);                         \
-        acc[1][y] = mma_bf16(a[1][P], b[y][Q], acc[1][y]);                         \
-    }
-            PECLR_X6(2, 0) PECLR_X6(0, 2) PECLR_X6(1, 1) PECLR_X6(1, 0) PECLR_X6(0, 1) PECLR_X6(0, 0)
-#undef PECLR_X6
+#pragma unroll
+            for (int pr = 0; pr < 6; ++pr)
+#pragma unroll
+                for (int y = 0; y < NB; ++y) {
+                    acc[0][y] = mma_bf16(a[0][X6_PA[pr]], b[y][X6_QB[pr]], acc[0][y]);
+                    acc[1][y] = mma_bf16(a[1][X6_PA[pr]], b[y][X6_QB[pr]], acc[1][y]);
+                }
         }
     };
     gload(kbeg);

@@ -354,8 +354,9 @@ __global__ __launch_bounds__(256, 2) void gemm_x6p_kernel(X6PArgs g) {
     _Pragma("unroll") for (int y = 0; y < 2; ++y) _Pragma("unroll") for (int a = 0; a < WM; ++a) \
         if constexpr (ABL & 8) { asm volatile("" :: "v"(af[a][P].x), "v"(af[a][P].w), "v"(bf[y][Q].x), "v"(bf[y][Q].w)); } \
         else acc[a][2 * half + y] = mman<NP>(af[a][P], bf[y][Q], acc[a][2 * half + y]);
-            if constexpr (NP == 3 && !(ABL & 64)) { PECLR_X6(NP - 1, 0) PECLR_X6(0, NP - 1) PECLR_X6(1, 1) }       // (ABL 64: three products only -- timing probe)
-            PECLR_X6(1, 0) PECLR_X6(0, 1) PECLR_X6(0, 0)                  // (NP = 2: lo.hi, hi.lo, hi.hi -- smallest first)
+            // the order of mfma.hpp; its last three alone for NP = 2 (lo.hi, hi.lo, hi.hi -- smallest first) and for ABL 64 (timing probe)
+#pragma unroll
+            for (int pr = (NP == 3 && !(ABL & 64)) ? 0 : 3; pr < 6; ++pr) PECLR_X6(X6_PA[pr], X6_QB[pr])
 #undef PECLR_X6
             if (half == 0 && SPLIT) {
                 if constexpr (!AREG) wait_vmcnt<0>();
@@ -494,8 +495,9 @@ __global__ __launch_bounds__(256, 2) void gemm_x6p_kernel(X6PArgs g) {
 #define PECLR_X6(P, Q)                                                                        \
     _Pragma("unroll") for (int y = 0; y < 2; ++y) _Pragma("unroll") for (int a = 0; a < WM; ++a) \
         acc[a][2 * half + y] = mman<NP>(af[a][P], bf[y][Q], acc[a][2 * half + y]);
-                    if constexpr (NP == 3 && !(ABL & 64)) { PECLR_X6(NP - 1, 0) PECLR_X6(0, NP - 1) PECLR_X6(1, 1) }
-                    PECLR_X6(1, 0) PECLR_X6(0, 1) PECLR_X6(0, 0)
+                    // (written out, not the main loop's loop over pr: that changes one instantiation's code)
+                    if constexpr (NP == 3 && !(ABL & 64)) { PECLR_X6(X6_PA[0], X6_QB[0]) PECLR_X6(X6_PA[1], X6_QB[1]) PECLR_X6(X6_PA[2], X6_QB[2]) }
+                    PECLR_X6(X6_PA[3], X6_QB[3]) PECLR_X6(X6_PA[4], X6_QB[4]) PECLR_X6(X6_PA[5], X6_QB[5])
 #undef PECLR_X6
                     if (half == 0) {
                         if (j == 0 && kc + 1 < nkc && !(ABL & 2)) { load_patch(kc + 1); asm volatile("" ::: "memory"); }

@@ -40,53 +40,161 @@ struct X6TArgs {
 
 __device__ __forceinline__ int slot_of(int i) { return (i & 3) * 8 + ((i >> 2) ^ (((i >> 1) & 1) << 2)); }
 
-// MT x NT: 32 x 32 MFMA tiles per wave; waves WGM (M) x 8 / WGM (N): workgroup tile 32 WGM MT x 256 / WGM NT (4 x 2 waves:
-// 128 MT x 64 NT; 2 x 4 waves for the 64-row gradients of layer1: 64 MT x 128 NT).  GEO: B's rows are the pixels of the
-// stride-2 convolution's input (a 1x1 / stride-2 shortcut), found from the output pixel each row of A is.
+// ---- what the kernels below share.  Constants, the Quarter split (which stood in lambdas) and zero() are structs and
+// __forceinline__ helpers; what stands in the kernels' BODIES -- slab store, thread roles, descriptor, whole-quad split -- is shared
+// as macros further down, because as functions those pieces change the device code (docs/history.md, section H: do not retry
+// those forms).  Either way the kernels compile to the instructions they had with the code written out
+// (profiles/isa_identity_wgrad_x6t.txt, tools/isa_diff.py).
+constexpr int XEPL = 36;                                      // floats per row of a wave's 32 x 32 epilogue transpose
+
+__device__ __forceinline__ void zero(f32x16& acc) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+}
+
+// The second forms' split: two of the lane's four rows (2 qp, 2 qp + 1), one of its four channels -> 4 bytes in each plane: a
+// quarter-unit, cut into three pieces of ~5 vector instructions (split3_pk of common.hpp, step by step) so that each fits under ONE
+// MFMA of the loop.  q_store: the planes lie plane_stride bytes apart.
+struct Quarter { unsigned h, m; float r0, r1; };
+__device__ __forceinline__ void q_first(Quarter& s, int qp, int j, const f32x4 (&r)[4]) {
+    const float x0 = r[2 * qp][j], x1 = r[2 * qp + 1][j];
+    s.h = pk_bf16(x0, x1);
+    s.r0 = sub_f32(x0, __uint_as_float(s.h << 16));
+    s.r1 = sub_f32(x1, __uint_as_float(s.h & 0xFFFF0000u));
+}
+__device__ __forceinline__ void q_second(Quarter& s) {
+    s.m = pk_bf16(s.r0, s.r1);
+    s.r0 = sub_f32(s.r0, __uint_as_float(s.m << 16));
+    s.r1 = sub_f32(s.r1, __uint_as_float(s.m & 0xFFFF0000u));
+}
+__device__ __forceinline__ void q_store(const Quarter& s, unsigned char* d, int plane_stride) {
+    *reinterpret_cast<unsigned*>(d) = s.h;
+    *reinterpret_cast<unsigned*>(d + plane_stride) = s.m;
+    *reinterpret_cast<unsigned*>(d + 2 * plane_stride) = pk_bf16(s.r0, s.r1);
+}
+
+// Tiles of the 1x1 kernels.  MT x NT: 32 x 32 MFMA tiles per wave; waves WGM (M) x 8 / WGM (N): workgroup tile 32 WGM MT x 256 / WGM NT
+// (4 x 2 waves: 128 MT x 64 NT; 2 x 4 waves for the 64-row gradients of layer1: 64 MT x 128 NT).
+template <int MT, int NT, int WGM>
+struct X6TTile {
+    static constexpr int WGN = 8 / WGM;
+    static constexpr int TM = 32 * WGM * MT, TN = 32 * WGN * NT;
+    static_assert((TM + TN) / 64 <= 8 && TM % 64 == 0 && TN % 64 == 0, "one 64-column group of the split per wave");
+    static constexpr int HALF_A = TM * 16, HALF_B = TN * 16;  // bytes of one k-half of a plane
+    static constexpr int PL_A = 2 * HALF_A, PL_B = 2 * HALF_B;
+    static constexpr int BUF = 3 * (PL_A + PL_B);             // one k-step of both operands
+    static_assert(2 * BUF >= 8 * 32 * XEPL * 4, "epilogue transposes live in the plane buffers");
+};
+// Tiles of the 3x3 kernels: a workgroup owns 32 WGM (Cout) x 64 (Cin) of all nine taps
+template <int WGM>
+struct X6WTile {
+    static constexpr int GRP = 3 * 2 * 64 * 16;               // bytes of one 64-column group: [plane][k-half][tile][slot][16]
+    static constexpr int NGA = WGM / 2, NG = NGA + 9, BUF = NG * GRP;    // groups: NGA of dY, then one of X per tap
+    static constexpr int NACC = WGM == 4 ? 9 : 5;             // accumulators (taps) per wave
+};
+
+// ---- What stands in the kernels' BODIES and is shared, as macros: the same text in every kernel is the only form that keeps
+// their device code identical (as functions these pieces compile differently, and the order of statements matters:
+// docs/history.md, section H).  Each macro is the one copy to edit; the ROLES / FRAGS macros declare the locals they name.
+
+// Epilogue, one 32 x 32 accumulator -> rows MT_ .., columns COL0 + NT_ .. of this split's slab OUT (leading dimension LDC) through
+// the wave-private transpose WLDS (32 rows of XEPL floats; same wave wrote and reads: LDS operations of one wave complete in
+// order), 16-byte stores.  I = lane & 31, KH = lane >> 5, ER = lane >> 3, EC = 4 (lane & 7); rows >= M_ and columns NT_ + .. >= N_
+// are not stored.  COL0: the 3x3 kernels' tap * N.
+#define PECLR_STORE_SLAB_TILE(WLDS, I, KH, ER, EC, ACC, OUT, LDC, MT_, NT_, COL0, M_, N_)                                  \
+    do {                                                                                                                   \
+        _Pragma("unroll") for (int r = 0; r < 16; ++r) WLDS[mfma32_row(r, KH) * XEPL + I] = ACC[r];                        \
+        _Pragma("unroll") for (int jj = 0; jj < 4; ++jj) {                                                                 \
+            const int m = MT_ + ER + 8 * jj, n = NT_ + EC;                                                                 \
+            const float4 c = *reinterpret_cast<const float4*>(WLDS + (ER + 8 * jj) * XEPL + EC);                           \
+            if (m < M_ && n < N_) *reinterpret_cast<float4*>(OUT + (size_t)m * LDC + COL0 + n) = c;                        \
+        }                                                                                                                  \
+    } while (0)
+
+// Buffer descriptor of BYTES bytes at BASE.  Every word through readfirstlane: the descriptor must sit in scalar registers, or each
+// load becomes a waterfall loop.
+#define PECLR_WAVE_UNIFORM_RSRC(BASE, BYTES)                                                                                \
+    ({                                                                                                                     \
+        const unsigned long long bp = reinterpret_cast<unsigned long long>(BASE);                                          \
+        const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)bp), bhi = __builtin_amdgcn_readfirstlane((unsigned)(bp >> 32)); \
+        __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>((unsigned long long)bhi << 32 | blo), (short)0,          \
+                                          __builtin_amdgcn_readfirstlane(BYTES), 0x00020000);                              \
+    })
+
+// The first forms' split: a thread's 4 (k) values V0 .. V3 of column CIN + J -> two packed k-pairs in each of the three planes
+// (STRIDE bytes apart), 8-byte stores.
+#define PECLR_SPLIT_STORE_QUAD(BASE, CIN, J, STRIDE, V0, V1, V2, V3)                                                        \
+    do {                                                                                                                   \
+        unsigned h[2], m[2], l[2];                                                                                         \
+        split3_pk(V0, V1, h[0], m[0], l[0]);                                                                               \
+        split3_pk(V2, V3, h[1], m[1], l[1]);                                                                               \
+        unsigned char* d = BASE + slot_of(CIN + J) * 16;                                                                   \
+        *reinterpret_cast<uint2*>(d) = make_uint2(h[0], h[1]);                                                             \
+        *reinterpret_cast<uint2*>(d + STRIDE) = make_uint2(m[0], m[1]);                                                    \
+        *reinterpret_cast<uint2*>(d + 2 * STRIDE) = make_uint2(l[0], l[1]);                                                \
+    } while (0)
+
+// Roles of a thread of the 1x1 kernels in the split: operand (A for the first TM threads' worth of blocks, then B), column chunk
+// (4 columns), k-quad (4 rows).  Lane bits: [2:0] chunk within a 32-column tile, [3] k-quad & 1, [4] k-half, [5] tile parity; a wave
+// covers 64 columns: wave w the 64-column group w over A's then B's columns.  chunk: 0..15 within the group; col: first of the
+// thread's 4 columns inside the tile; plane store address of column col + j: tile (col >> 5), slot of ((col & 31) + j), k-quad half;
+// once: rows exactly one workgroup of a split reads (non-temporal loads, see gemm_x6t_kernel).
+#define PECLR_X6T_ROLES(WAVE)                                                                                               \
+    const bool is_a = WAVE < T::TM / 64;                                                                                   \
+    const bool active = WAVE < (T::TM + T::TN) / 64;                                                                       \
+    const int cgrp = is_a ? WAVE : WAVE - T::TM / 64;                                                                      \
+    const int chunk = (lane & 7) + 8 * (lane >> 5);                                                                        \
+    const int kq = (lane >> 3) & 3;                                                                                        \
+    const int col = cgrp * 64 + 4 * chunk;                                                                                 \
+    [[maybe_unused]] const float* src = is_a ? g.A + m0 + col : g.B + n0 + col;                                            \
+    const int ld = is_a ? g.lda : g.ldb;                                                                                   \
+    const bool col_ok = active && (is_a ? m0 + col < g.M : n0 + col < g.N);                                                \
+    const int tile = col >> 5, cin = col & 31;                                                                             \
+    const int st_base = (kq >> 1) * (is_a ? T::HALF_A : T::HALF_B) + tile * 512 + (kq & 1) * 8 + (is_a ? 0 : 3 * T::PL_A); \
+    const int st_plane = is_a ? T::PL_A : T::PL_B;                                                                         \
+    const bool once = is_a ? nct == 1 : (int)gridDim.x == nct
+// ... and where it reads its fragments: fa + a * 512 + plane * PL_A, fb + y * 512 + plane * PL_B
+#define PECLR_X6T_FRAGS                                                                                                     \
+    const int fa = kh * T::HALF_A + (wm * MT) * 512 + slot_of(i) * 16;                                                     \
+    const int fb = 3 * T::PL_A + kh * T::HALF_B + (wn * NT) * 512 + slot_of(i) * 16
+
+// Roles of the 3x3 kernels: of a wave (WGM = 4: waves 4 x 2, all nine taps; WGM = 2: 2 x 2 x two tap halves -- tap0: first tap
+// of this wave) ...
+#define PECLR_X6W_WAVE_ROLES(WAVE)                                                                                          \
+    const int wm = WGM == 4 ? WAVE >> 1 : (WAVE >> 1) & 1, wn = WAVE & 1;                                                  \
+    const int tap0 = WGM == 4 ? 0 : (WAVE >> 2) * 5;                                                                       \
+    const int ntap = WGM == 4 ? 9 : (WAVE >> 2 ? 4 : 5)
+// ... of a lane in the split (st_off: inside a group's plane) ...
+#define PECLR_X6W_LANE_ROLES                                                                                                \
+    const int chunk = (lane & 7) + 8 * (lane >> 5), kq = (lane >> 3) & 3;                                                  \
+    const int cin = 4 * (chunk & 7), tile = chunk >> 3;                                                                    \
+    const int st_off = (kq >> 1) * 1024 + tile * 512 + (kq & 1) * 8
+// ... and the fragment reads: fa + plane * 2048, fb + tap * GRP + plane * 2048
+#define PECLR_X6W_FRAGS                                                                                                     \
+    const int fa = (wm >> 1) * T::GRP + kh * 1024 + (wm & 1) * 512 + slot_of(i) * 16;                                      \
+    const int fb = (T::NGA + tap0) * T::GRP + kh * 1024 + wn * 512 + slot_of(i) * 16
+
+// GEO: B's rows are the pixels of the stride-2 convolution's input (a 1x1 / stride-2 shortcut), found from the output pixel each
+// row of A is.
 // PF: k-steps of global loads in flight per thread (register stages).  (Measured on the 64-wide gradients, whose k-steps
 // are short: PF = 2 changes nothing -- hipcc's wait-count pass still drains every load before the split -- and PF = 4
 // costs the second workgroup per CU its registers, 262 -> 298 us.  PF = 1 everywhere.)
 template <int MT, int NT, int WGM, bool GEO, int PF>
 __global__ __launch_bounds__(512, 2) void gemm_x6t_kernel(X6TArgs g) {
-    constexpr int WGN = 8 / WGM;
-    constexpr int TM = 32 * WGM * MT, TN = 32 * WGN * NT;
-    static_assert((TM + TN) / 64 <= 8 && TM % 64 == 0 && TN % 64 == 0, "one 64-column group of the split per wave");
-    constexpr int HALF_A = TM * 16, HALF_B = TN * 16;         // bytes of one k-half of a plane
-    constexpr int PL_A = 2 * HALF_A, PL_B = 2 * HALF_B;
-    constexpr int BUF = 3 * (PL_A + PL_B);                    // one k-step of both operands
-    constexpr int XEPL = 36;
-    static_assert(2 * BUF >= 8 * 32 * XEPL * 4, "epilogue transposes live in the plane buffers");
-    __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * BUF];
+    using T = X6TTile<MT, NT, WGM>;
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * T::BUF];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WGN, wn = wave % WGN;
+    const int wm = wave / T::WGN, wn = wave % T::WGN;
     const int i = lane & 31, kh = lane >> 5;
-    const int nct = (g.N + TN - 1) / TN;
-    const int m0 = (int)(blockIdx.x / nct) * TM, n0 = (int)(blockIdx.x % nct) * TN;
+    const int nct = (g.N + T::TN - 1) / T::TN;
+    const int m0 = (int)(blockIdx.x / nct) * T::TM, n0 = (int)(blockIdx.x % nct) * T::TN;
     const int kbeg = blockIdx.y * g.kchunk, kend = min(g.K, kbeg + g.kchunk);
     const int nk = (kend - kbeg + TK - 1) / TK;
 
-    // ---- this thread's block of the split: operand (A for the first TM threads' worth of blocks, then B), column chunk
-    // (4 columns), k-quad (4 rows).  Lane bits: [2:0] chunk within a 32-column tile, [3] k-quad & 1, [4] k-half, [5] tile
-    // parity; a wave covers 64 columns.
-    const int blk_col64 = wave;                               // 64-column group index over A's then B's columns
-    const bool is_a = blk_col64 < TM / 64;
-    const bool active = blk_col64 < (TM + TN) / 64;
-    const int cgrp = is_a ? blk_col64 : blk_col64 - TM / 64;
-    const int chunk = (lane & 7) + 8 * (lane >> 5);           // 0..15 within the 64-column group
-    const int kq = (lane >> 3) & 3;
-    const int col = cgrp * 64 + 4 * chunk;                    // first of this thread's 4 columns inside the tile
-    const float* src = is_a ? g.A + m0 + col : g.B + n0 + col;
-    const int ld = is_a ? g.lda : g.ldb;
-    const bool col_ok = active && (is_a ? m0 + col < g.M : n0 + col < g.N);
-    // plane store address of column col + j: tile (col >> 5), slot of ((col & 31) + j), k-quad half
-    const int tile = col >> 5, cin = col & 31;
-    const int st_base = (kq >> 1) * (is_a ? HALF_A : HALF_B) + tile * 512 + (kq & 1) * 8 + (is_a ? 0 : 3 * PL_A);
-    const int st_plane = is_a ? PL_A : PL_B;
-
+    PECLR_X6T_ROLES(wave);
     // rows that exactly ONE workgroup of a split reads (the operand whose other side fits one tile: both operands of layer1's
     // 256 x 64 / 64 x 256 gradients) are loaded with the non-temporal hint: a linear read runs at 6.8 TB/s with it, 4.3 without
     // (tools/exp/rw_mix.hip); `conv1x1_wgrad~hbm` 192 -> 180 us.  Rows several workgroups share keep the plain load (L2 reuse).
-    const bool once = is_a ? nct == 1 : (int)gridDim.x == nct;
     f32x4 ld4[PF][4];
     // GEO: pixel (oh, ow) of the first row of this thread's next block, advanced by 16 rows per k-step (no divisions in
     // the loop); gload() is called with t = 0, 1, 2, ... in order
@@ -121,30 +229,18 @@ __global__ __launch_bounds__(512, 2) void gemm_x6t_kernel(X6TArgs g) {
     };
     auto split_store = [&](int buf, const f32x4 (&ld4)[4]) {
         if (!active) return;
-        unsigned char* base = lds + buf * BUF + st_base;
+        unsigned char* base = lds + buf * T::BUF + st_base;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            unsigned h[2], m[2], l[2];
-            float v[4] = {ld4[0][j], ld4[1][j], ld4[2][j], ld4[3][j]};
-            split3_pk(v[0], v[1], h[0], m[0], l[0]);
-            split3_pk(v[2], v[3], h[1], m[1], l[1]);
-            unsigned char* d = base + slot_of(cin + j) * 16;
-            *reinterpret_cast<uint2*>(d) = make_uint2(h[0], h[1]);
-            *reinterpret_cast<uint2*>(d + st_plane) = make_uint2(m[0], m[1]);
-            *reinterpret_cast<uint2*>(d + 2 * st_plane) = make_uint2(l[0], l[1]);
-        }
+        for (int j = 0; j < 4; ++j) PECLR_SPLIT_STORE_QUAD(base, cin, j, st_plane, ld4[0][j], ld4[1][j], ld4[2][j], ld4[3][j]);
     };
 
     f32x16 acc[MT][NT];
 #pragma unroll
     for (int a = 0; a < MT; ++a)
 #pragma unroll
-        for (int y = 0; y < NT; ++y)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][y][r] = 0.f;
+        for (int y = 0; y < NT; ++y) zero(acc[a][y]);
 
-    const int fa = kh * HALF_A + (wm * MT) * 512 + slot_of(i) * 16;                  // + a * 512 + plane * PL_A
-    const int fb = 3 * PL_A + kh * HALF_B + (wn * NT) * 512 + slot_of(i) * 16;       // + y * 512 + plane * PL_B
+    PECLR_X6T_FRAGS;
 
     // step u lives in register stage u % PF: loaded PF steps ahead, split into the planes one step ahead
     if (nk > 0) {
@@ -160,12 +256,12 @@ __global__ __launch_bounds__(512, 2) void gemm_x6t_kernel(X6TArgs g) {
     for (int st = 0; st < PF; ++st) {
         const int t = t0 + st;
         if (t >= nk) break;                                   // (uniform)
-        const unsigned char* bufp = lds + (t & 1) * BUF;
+        const unsigned char* bufp = lds + (t & 1) * T::BUF;
         uint4 af[MT][3];
 #pragma unroll
         for (int a = 0; a < MT; ++a)
 #pragma unroll
-            for (int p = 0; p < 3; ++p) af[a][p] = *reinterpret_cast<const uint4*>(bufp + fa + a * 512 + p * PL_A);
+            for (int p = 0; p < 3; ++p) af[a][p] = *reinterpret_cast<const uint4*>(bufp + fa + a * 512 + p * T::PL_A);
         constexpr int NH = NT > 2 ? 2 : 1, YH = NT / NH;          // B fragments in two halves (registers)
 #pragma unroll
         for (int half = 0; half < NH; ++half) {
@@ -173,11 +269,13 @@ __global__ __launch_bounds__(512, 2) void gemm_x6t_kernel(X6TArgs g) {
 #pragma unroll
             for (int y = 0; y < YH; ++y)
 #pragma unroll
-                for (int p = 0; p < 3; ++p) bf[y][p] = *reinterpret_cast<const uint4*>(bufp + fb + (half * YH + y) * 512 + p * PL_B);
+                for (int p = 0; p < 3; ++p) bf[y][p] = *reinterpret_cast<const uint4*>(bufp + fb + (half * YH + y) * 512 + p * T::PL_B);
 #define PECLR_X6(P, Q)                                                                        \
     _Pragma("unroll") for (int y = 0; y < YH; ++y) _Pragma("unroll") for (int a = 0; a < MT; ++a) \
         acc[a][half * YH + y] = mma_bf16(af[a][P], bf[y][Q], acc[a][half * YH + y]);
-            PECLR_X6(2, 0) PECLR_X6(0, 2) PECLR_X6(1, 1) PECLR_X6(1, 0) PECLR_X6(0, 1) PECLR_X6(0, 0)
+            // (written out, not a loop over pr: a loop changes the code of the 256 x 256 tile)
+            PECLR_X6(X6_PA[0], X6_QB[0]) PECLR_X6(X6_PA[1], X6_QB[1]) PECLR_X6(X6_PA[2], X6_QB[2])
+            PECLR_X6(X6_PA[3], X6_QB[3]) PECLR_X6(X6_PA[4], X6_QB[4]) PECLR_X6(X6_PA[5], X6_QB[5])
 #undef PECLR_X6
             if (half == 0 && t + 1 < nk) {
                 split_store((t + 1) & 1, ld4[(st + 1) % PF]);       // rows of step t + 1 -> the other buffer
@@ -196,14 +294,7 @@ __global__ __launch_bounds__(512, 2) void gemm_x6t_kernel(X6TArgs g) {
 #pragma unroll
         for (int y = 0; y < NT; ++y) {
             const int mt = m0 + (wm * MT + a) * 32, nt = n0 + (wn * NT + y) * 32;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) wlds[mfma32_row(r, kh) * XEPL + i] = acc[a][y][r];
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-                const int m = mt + er + 8 * jj, n = nt + ec;
-                const float4 c = *reinterpret_cast<const float4*>(wlds + (er + 8 * jj) * XEPL + ec);
-                if (m < g.M && n < g.N) *reinterpret_cast<float4*>(out + (size_t)m * g.ldc + n) = c;
-            }
+            PECLR_STORE_SLAB_TILE(wlds, i, kh, er, ec, acc[a][y], out, g.ldc, mt, nt, 0, g.M, g.N);
         }
 }
 
@@ -220,15 +311,10 @@ __global__ __launch_bounds__(512, 2) void gemm_x6t_kernel(X6TArgs g) {
 // "planes"), 2 = dY groups likewise, 4 = no plane stores after the first k-step, 8 = no global loads after the prologue
 template <int WGM, int ABL = 0>
 __global__ __launch_bounds__(512, 2) void gemm_x6w_kernel(X6TArgs g) {
-    constexpr int GRP = 3 * 2 * 64 * 16;                      // bytes of one 64-column group: [plane][k-half][tile][slot][16]
-    constexpr int NGA = WGM / 2, NG = NGA + 9, BUF = NG * GRP;
-    constexpr int NACC = WGM == 4 ? 9 : 5;
-    constexpr int XEPL = 36;
-    __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * BUF];
+    using T = X6WTile<WGM>;
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * T::BUF];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = WGM == 4 ? wave >> 1 : (wave >> 1) & 1, wn = wave & 1;
-    const int tap0 = WGM == 4 ? 0 : (wave >> 2) * 5;          // first tap of this wave
-    const int ntap = WGM == 4 ? 9 : (wave >> 2 ? 4 : 5);
+    PECLR_X6W_WAVE_ROLES(wave);
     const int i = lane & 31, kh = lane >> 5;
     const int nct = (g.N + 63) / 64;
     const int m0 = (int)(blockIdx.x / nct) * (32 * WGM), n0 = (int)(blockIdx.x % nct) * 64;
@@ -236,17 +322,15 @@ __global__ __launch_bounds__(512, 2) void gemm_x6w_kernel(X6TArgs g) {
     const int kbeg = blockIdx.y * g.kchunk, kend = min(g.K, kbeg + g.kchunk);
     const int nk = (kend - kbeg + TK - 1) / TK;
 
-    const int chunk = (lane & 7) + 8 * (lane >> 5), kq = (lane >> 3) & 3;
-    const int cin = 4 * (chunk & 7), tile = chunk >> 3;
-    const int st_off = (kq >> 1) * 1024 + tile * 512 + (kq & 1) * 8;     // inside a group's plane
+    PECLR_X6W_LANE_ROLES;
     // group gi: 0 .. NGA - 1 = dY columns m0 + 64 gi ...; NGA + tap = X columns n0 ..., rows shifted by the tap
     const int g1 = wave, g2 = wave + 8;                        // this wave's groups (g2 only for the first NG - 8 waves)
-    const bool two = g2 < NG;
+    const bool two = g2 < T::NG;
     struct Src { const float* p; int ld, dh, dw; bool ok, is_a; };
     auto src_of = [&](int gi) {
         Src s;
-        s.is_a = gi < NGA;
-        const int tap = gi - NGA;
+        s.is_a = gi < T::NGA;
+        const int tap = gi - T::NGA;
         s.dh = s.is_a ? 0 : tap / 3 - 1;
         s.dw = s.is_a ? 0 : tap % 3 - 1;
         const int c = 4 * chunk + (s.is_a ? 64 * gi : 0);
@@ -287,21 +371,16 @@ __global__ __launch_bounds__(512, 2) void gemm_x6w_kernel(X6TArgs g) {
             if (ow_t >= g.W) { ow_t -= g.W; oh_t = oh_t + 1 == g.H ? 0 : oh_t + 1; }
     };
     auto store1 = [&](int buf, int gi, const f32x4 (&r)[4]) {
-        unsigned char* base = lds + buf * BUF + gi * GRP + st_off;
+        unsigned char* base = lds + buf * T::BUF + gi * T::GRP + st_off;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            unsigned h[2], m[2], l[2];
-            if ((ABL & 1) && gi >= NGA || (ABL & 2) && gi < NGA) {
-                h[0] = __float_as_uint(r[0][j]); m[0] = __float_as_uint(r[1][j]); l[0] = h[0] ^ m[0];
-                h[1] = __float_as_uint(r[2][j]); m[1] = __float_as_uint(r[3][j]); l[1] = h[1] ^ m[1];
-            } else {
-                split3_pk(r[0][j], r[1][j], h[0], m[0], l[0]);
-                split3_pk(r[2][j], r[3][j], h[1], m[1], l[1]);
-            }
-            unsigned char* d = base + slot_of(cin + j) * 16;
-            *reinterpret_cast<uint2*>(d) = make_uint2(h[0], h[1]);
-            *reinterpret_cast<uint2*>(d + 2048) = make_uint2(m[0], m[1]);
-            *reinterpret_cast<uint2*>(d + 4096) = make_uint2(l[0], l[1]);
+            if (((ABL & 1) && gi >= T::NGA) || ((ABL & 2) && gi < T::NGA)) {      // (ablation: raw halves as "planes", no split)
+                const unsigned h0 = __float_as_uint(r[0][j]), m0 = __float_as_uint(r[1][j]), h1 = __float_as_uint(r[2][j]), m1 = __float_as_uint(r[3][j]);
+                unsigned char* d = base + slot_of(cin + j) * 16;
+                *reinterpret_cast<uint2*>(d) = make_uint2(h0, h1);
+                *reinterpret_cast<uint2*>(d + 2048) = make_uint2(m0, m1);
+                *reinterpret_cast<uint2*>(d + 4096) = make_uint2(h0 ^ m0, h1 ^ m1);
+            } else PECLR_SPLIT_STORE_QUAD(base, cin, j, 2048, r[0][j], r[1][j], r[2][j], r[3][j]);
         }
     };
     auto split_store = [&](int buf) {
@@ -309,13 +388,10 @@ __global__ __launch_bounds__(512, 2) void gemm_x6w_kernel(X6TArgs g) {
         if (two) store1(buf, g2, lb);
     };
 
-    f32x16 acc[NACC];
+    f32x16 acc[T::NACC];
 #pragma unroll
-    for (int tp = 0; tp < NACC; ++tp)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[tp][r] = 0.f;
-    const int fa = (wm >> 1) * GRP + kh * 1024 + (wm & 1) * 512 + slot_of(i) * 16;       // + plane * 2048
-    const int fb = (NGA + tap0) * GRP + kh * 1024 + wn * 512 + slot_of(i) * 16;           // + tap * GRP + plane * 2048
+    for (int tp = 0; tp < T::NACC; ++tp) zero(acc[tp]);
+    PECLR_X6W_FRAGS;
 
     if (nk > 0) {
         gload(0);
@@ -324,22 +400,18 @@ __global__ __launch_bounds__(512, 2) void gemm_x6w_kernel(X6TArgs g) {
     }
     __syncthreads();
     for (int t = 0; t < nk; ++t) {
-        const unsigned char* bufp = lds + (t & 1) * BUF;
+        const unsigned char* bufp = lds + (t & 1) * T::BUF;
         uint4 af[3];
 #pragma unroll
         for (int p = 0; p < 3; ++p) af[p] = *reinterpret_cast<const uint4*>(bufp + fa + p * 2048);
 #pragma unroll
-        for (int tp = 0; tp < NACC; ++tp) {
+        for (int tp = 0; tp < T::NACC; ++tp) {
             if (WGM == 4 || tp < ntap) {                      // (wave-uniform: the second tap half has four taps)
                 uint4 bf[3];
 #pragma unroll
-                for (int p = 0; p < 3; ++p) bf[p] = *reinterpret_cast<const uint4*>(bufp + fb + tp * GRP + p * 2048);
-                acc[tp] = mma_bf16(af[2], bf[0], acc[tp]);
-                acc[tp] = mma_bf16(af[0], bf[2], acc[tp]);
-                acc[tp] = mma_bf16(af[1], bf[1], acc[tp]);
-                acc[tp] = mma_bf16(af[1], bf[0], acc[tp]);
-                acc[tp] = mma_bf16(af[0], bf[1], acc[tp]);
-                acc[tp] = mma_bf16(af[0], bf[0], acc[tp]);
+                for (int p = 0; p < 3; ++p) bf[p] = *reinterpret_cast<const uint4*>(bufp + fb + tp * T::GRP + p * 2048);
+#pragma unroll
+                for (int pr = 0; pr < 6; ++pr) acc[tp] = mma_bf16(af[X6_PA[pr]], bf[X6_QB[pr]], acc[tp]);
             }
             if (tp == (WGM == 4 ? 2 : 1) && t + 1 < nk) {
                 if constexpr (!(ABL & 4)) split_store((t + 1) & 1);
@@ -354,16 +426,9 @@ __global__ __launch_bounds__(512, 2) void gemm_x6w_kernel(X6TArgs g) {
     const int er = lane >> 3, ec = (lane & 7) * 4;
     const int mt = m0 + wm * 32, nt = n0 + wn * 32;
 #pragma unroll
-    for (int tp = 0; tp < NACC; ++tp) {
+    for (int tp = 0; tp < T::NACC; ++tp) {
         if (WGM != 4 && tp >= ntap) break;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) wlds[mfma32_row(r, kh) * XEPL + i] = acc[tp][r];
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const int m = mt + er + 8 * jj, n = nt + ec;
-            const float4 c = *reinterpret_cast<const float4*>(wlds + (er + 8 * jj) * XEPL + ec);
-            if (m < g.M && n < g.N) *reinterpret_cast<float4*>(out + (size_t)m * g.ldc + (tap0 + tp) * g.N + n) = c;
-        }
+        PECLR_STORE_SLAB_TILE(wlds, i, kh, er, ec, acc[tp], out, g.ldc, mt, nt, (tap0 + tp) * g.N, g.M, g.N);
     }
 }
 
@@ -392,17 +457,12 @@ constexpr int X6W2_S2_MAX_HW = X6W2_TAB / 36 - 3;             // stride 2: four 
 
 template <int WGM, bool S2 = false>
 __global__ __launch_bounds__(512, 2) void gemm_x6w2_kernel(X6TArgs g) {
-    constexpr int GRP = 3 * 2 * 64 * 16;                      // bytes of one 64-column group: [plane][k-half][tile][slot][16]
-    constexpr int NGA = WGM / 2, NG = NGA + 9, BUF = NG * GRP;
-    constexpr int NACC = WGM == 4 ? 9 : 5;
-    constexpr int XEPL = 36;
-    __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * BUF + X6W2_TAB];
-    unsigned char* const tab = lds + 2 * BUF;
+    using T = X6WTile<WGM>;
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * T::BUF + X6W2_TAB];
+    unsigned char* const tab = lds + 2 * T::BUF;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = WGM == 4 ? wave >> 1 : (wave >> 1) & 1, wn = wave & 1;
-    const int tap0 = WGM == 4 ? 0 : (wave >> 2) * 5;          // first tap of this wave
-    const int ntap = WGM == 4 ? 9 : (wave >> 2 ? 4 : 5);
+    PECLR_X6W_WAVE_ROLES(wave);
     const int i = lane & 31, kh = lane >> 5;
     const int nct = (g.N + 63) / 64;
     const int m0 = (int)(blockIdx.x / nct) * (32 * WGM), n0 = (int)(blockIdx.x % nct) * 64;
@@ -451,9 +511,7 @@ __global__ __launch_bounds__(512, 2) void gemm_x6w2_kernel(X6TArgs g) {
         __syncthreads();
     }
 
-    const int chunk = (lane & 7) + 8 * (lane >> 5), kq = (lane >> 3) & 3;
-    const int cin = 4 * (chunk & 7), tile = chunk >> 3;
-    const int st_off = (kq >> 1) * 1024 + tile * 512 + (kq & 1) * 8;     // inside a group's plane
+    PECLR_X6W_LANE_ROLES;
     // group gi: 0 .. NGA - 1 = dY columns m0 + 64 gi ...; NGA + tap = X columns n0 ..., rows shifted by the tap
     struct Grp {
         __amdgpu_buffer_rsrc_t rs;       // (wave-uniform) the operand, cut off after the last row this group may read
@@ -466,32 +524,28 @@ __global__ __launch_bounds__(512, 2) void gemm_x6w2_kernel(X6TArgs g) {
     };
     auto grp_of = [&](int gi) {
         Grp s;
-        const bool is_a = gi < NGA;
-        const int tap = is_a ? 4 : gi - NGA;
+        const bool is_a = gi < T::NGA;
+        const int tap = is_a ? 4 : gi - T::NGA;
         const int shift = (tap / 3 - 1) * g.W + (tap % 3 - 1);
         const int ld = is_a ? g.lda : g.ldb;
         const int c = 4 * chunk + (is_a ? 64 * gi : 0);
         const bool ok = is_a ? m0 + c < g.M : n0 + c < g.N;
         const long rows = S2 ? (is_a ? (long)g.K : 4L * g.K) : (long)g.K + (shift < 0 ? shift : 0);
-        // (every word through readfirstlane: the descriptor must sit in scalar registers, or each load becomes a waterfall loop)
-        const unsigned long long bp = reinterpret_cast<unsigned long long>(is_a ? g.A : g.B);
-        const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)bp), bhi = __builtin_amdgcn_readfirstlane((unsigned)(bp >> 32));
-        s.rs = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>((unsigned long long)bhi << 32 | blo), (short)0,
-                                                 __builtin_amdgcn_readfirstlane((int)(rows * ld * 4)), 0x00020000);
+        s.rs = PECLR_WAVE_UNIFORM_RSRC(is_a ? g.A : g.B, (int)(rows * ld * 4));
         s.ld4 = __builtin_amdgcn_readfirstlane((unsigned)ld * 4u);
         s.step = TK * s.ld4;
         s.off = ok ? (unsigned)(((kbeg + 4 * kq + shift) * ld + (is_a ? m0 : n0) + c) * 4) : 0x80000000u;
-        s.tb = __builtin_amdgcn_readfirstlane(2 * BUF + tap * X6W2_MAX_HW);
+        s.tb = __builtin_amdgcn_readfirstlane(2 * T::BUF + tap * X6W2_MAX_HW);
         s.isx = !is_a;
         if constexpr (S2) {
             if (!is_a) s.off = ok ? (unsigned)((kbeg + 4 * kq) / HW) * s2_img + (unsigned)(n0 + c) * 4u : 0x80000000u;
-            s.tb = __builtin_amdgcn_readfirstlane(2 * BUF + tap * s2_row);
+            s.tb = __builtin_amdgcn_readfirstlane(2 * T::BUF + tap * s2_row);
         }
-        s.st = gi * GRP + st_off;
+        s.st = gi * T::GRP + st_off;
         return s;
     };
-    Grp G1 = grp_of(wave), G2 = grp_of(wave + 8 < NG ? wave + 8 : wave);
-    const bool two = wave + 8 < NG;
+    Grp G1 = grp_of(wave), G2 = grp_of(wave + 8 < T::NG ? wave + 8 : wave);
+    const bool two = wave + 8 < T::NG;
     int pk = (kbeg + 4 * kq) % HW;                            // pixel (inside its image) of this lane's first row of the step being loaded
 
     f32x4 la[4], lb[4];
@@ -524,25 +578,8 @@ __global__ __launch_bounds__(512, 2) void gemm_x6w2_kernel(X6TArgs g) {
         if constexpr (S2) G.off += G.isx ? winc : G.step;
         else G.off += G.step;
     };
-    // two of the lane's four rows (2 qp, 2 qp + 1), one of its four channels -> 4 bytes in each plane: a quarter-unit, cut into three
-    // pieces of ~5 vector instructions (split3_pk of common.hpp, step by step) so that each fits under ONE MFMA of the loop
-    struct Quarter { unsigned h, m; float r0, r1; };
-    auto q_first = [&](Quarter& s, int qp, int j, const f32x4 (&r)[4]) {
-        const float x0 = r[2 * qp][j], x1 = r[2 * qp + 1][j];
-        s.h = pk_bf16(x0, x1);
-        s.r0 = sub_f32(x0, __uint_as_float(s.h << 16));
-        s.r1 = sub_f32(x1, __uint_as_float(s.h & 0xFFFF0000u));
-    };
-    auto q_second = [&](Quarter& s) {
-        s.m = pk_bf16(s.r0, s.r1);
-        s.r0 = sub_f32(s.r0, __uint_as_float(s.m << 16));
-        s.r1 = sub_f32(s.r1, __uint_as_float(s.m & 0xFFFF0000u));
-    };
     auto q_third = [&](const Quarter& s, const Grp& G, int buf, int qp, int j) {
-        unsigned char* d = lds + G.st + buf * BUF + 4 * qp + slot_of(cin + j) * 16;
-        *reinterpret_cast<unsigned*>(d) = s.h;
-        *reinterpret_cast<unsigned*>(d + 2048) = s.m;
-        *reinterpret_cast<unsigned*>(d + 4096) = pk_bf16(s.r0, s.r1);
+        q_store(s, lds + G.st + buf * T::BUF + 4 * qp + slot_of(cin + j) * 16, 2048);
     };
     auto quarter = [&](const Grp& G, int buf, int qp, int j, const f32x4 (&r)[4]) {
         Quarter s;
@@ -551,13 +588,10 @@ __global__ __launch_bounds__(512, 2) void gemm_x6w2_kernel(X6TArgs g) {
         q_third(s, G, buf, qp, j);
     };
 
-    f32x16 acc[NACC];
+    f32x16 acc[T::NACC];
 #pragma unroll
-    for (int tp = 0; tp < NACC; ++tp)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[tp][r] = 0.f;
-    const int fa = (wm >> 1) * GRP + kh * 1024 + (wm & 1) * 512 + slot_of(i) * 16;       // + plane * 2048
-    const int fb = (NGA + tap0) * GRP + kh * 1024 + wn * 512 + slot_of(i) * 16;           // + tap * GRP + plane * 2048
+    for (int tp = 0; tp < T::NACC; ++tp) zero(acc[tp]);
+    PECLR_X6W_FRAGS;
 
     __syncthreads();                                          // the table
     // prologue: step 0 -> buffer 0; step 1 in flight
@@ -584,7 +618,7 @@ __global__ __launch_bounds__(512, 2) void gemm_x6w2_kernel(X6TArgs g) {
     auto run = [&](auto two_c) {
         constexpr bool TWO = decltype(two_c)::value;
         for (int t = 0; t < nk; ++t) {
-            const unsigned char* bufp = lds + (t & 1) * BUF;
+            const unsigned char* bufp = lds + (t & 1) * T::BUF;
             const int nb = (t + 1) & 1;
             // fragments: dY's three planes once per step; X's per tap -- plane 0 (first and last product of a tap) double-buffered,
             // planes 2 and 1 re-read into the same registers as soon as their last product of the tap has issued
@@ -597,11 +631,11 @@ __global__ __launch_bounds__(512, 2) void gemm_x6w2_kernel(X6TArgs g) {
             const unsigned n1 = S2 ? 0u : lds[G1.tb + pk], n2 = (!S2 && TWO) ? lds[G2.tb + pk] : 0u;          // masks of step t + 2
             unsigned tq[2] = {0u, 0u};                        // S2: the table entries of the row pair about to be re-loaded
 #pragma unroll
-            for (int tp = 0; tp < NACC; ++tp) {
+            for (int tp = 0; tp < T::NACC; ++tp) {
                 if (WGM != 4 && tp >= ntap) break;            // (wave-uniform; WGM = 4: never)
                 const int cb = tp & 1;
-                const bool more = tp + 1 < NACC;
-                const unsigned char* nx = bufp + fb + (tp + 1) * GRP;
+                const bool more = tp + 1 < T::NACC;
+                const unsigned char* nx = bufp + fb + (tp + 1) * T::GRP;
                 // Work between this tap's MFMAs.  Quarter-unit u = 0 .. 15: group u >> 3, rows qp = (u >> 2) & 1, channel j = u & 3, in three
                 // pieces; the fourth quarter of a row pair re-issues that pair's loads (for step t + 2) with its second and third piece,
                 // when the rows' registers are free.  WGM = 4 (nine taps): two quarters per tap, one piece per MFMA; WGM = 2 (five or
@@ -628,21 +662,23 @@ __global__ __launch_bounds__(512, 2) void gemm_x6w2_kernel(X6TArgs g) {
                     else { piece(2 * si); piece(2 * si + 1); }
                 };
 #define PECLR_FENCE __builtin_amdgcn_sched_barrier(0)
-                acc[tp] = mma_bf16(af[2], b0[cb], acc[tp]);       PECLR_FENCE;
+#define PECLR_MMA(PR) acc[tp] = mma_bf16(af[X6_PA[PR]], X6_QB[PR] == 0 ? b0[cb] : (X6_QB[PR] == 1 ? b1 : b2), acc[tp])
+                PECLR_MMA(0);                                 PECLR_FENCE;
                 if (more) b0[cb ^ 1] = *reinterpret_cast<const uint4*>(nx);
                 slot(0);                                      PECLR_FENCE;
-                acc[tp] = mma_bf16(af[0], b2, acc[tp]);           PECLR_FENCE;
+                PECLR_MMA(1);                                 PECLR_FENCE;
                 if (more) b2 = *reinterpret_cast<const uint4*>(nx + 4096);
                 slot(1);                                      PECLR_FENCE;
-                acc[tp] = mma_bf16(af[1], b1, acc[tp]);           PECLR_FENCE;
+                PECLR_MMA(2);                                 PECLR_FENCE;
                 slot(2);                                      PECLR_FENCE;
-                acc[tp] = mma_bf16(af[1], b0[cb], acc[tp]);       PECLR_FENCE;
+                PECLR_MMA(3);                                 PECLR_FENCE;
                 slot(3);                                      PECLR_FENCE;
-                acc[tp] = mma_bf16(af[0], b1, acc[tp]);           PECLR_FENCE;
+                PECLR_MMA(4);                                 PECLR_FENCE;
                 if (more) b1 = *reinterpret_cast<const uint4*>(nx + 2048);
                 slot(4);                                      PECLR_FENCE;
-                acc[tp] = mma_bf16(af[0], b0[cb], acc[tp]);       PECLR_FENCE;
+                PECLR_MMA(5);                                 PECLR_FENCE;
                 slot(5);                                      PECLR_FENCE;
+#undef PECLR_MMA
 #undef PECLR_FENCE
             }
             next_pixel();
@@ -659,16 +695,9 @@ __global__ __launch_bounds__(512, 2) void gemm_x6w2_kernel(X6TArgs g) {
     const int er = lane >> 3, ec = (lane & 7) * 4;
     const int mt = m0 + wm * 32, nt = n0 + wn * 32;
 #pragma unroll
-    for (int tp = 0; tp < NACC; ++tp) {
+    for (int tp = 0; tp < T::NACC; ++tp) {
         if (WGM != 4 && tp >= ntap) break;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) wlds[mfma32_row(r, kh) * XEPL + i] = acc[tp][r];
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const int m = mt + er + 8 * jj, n = nt + ec;
-            const float4 c = *reinterpret_cast<const float4*>(wlds + (er + 8 * jj) * XEPL + ec);
-            if (m < g.M && n < g.N) *reinterpret_cast<float4*>(out + (size_t)m * g.ldc + (tap0 + tp) * g.N + n) = c;
-        }
+        PECLR_STORE_SLAB_TILE(wlds, i, kh, er, ec, acc[tp], out, g.ldc, mt, nt, (tap0 + tp) * g.N, g.M, g.N);
     }
 }
 
@@ -687,42 +716,20 @@ __global__ __launch_bounds__(512, 2) void gemm_x6w2_kernel(X6TArgs g) {
 // (profiles/r06_x6t_ablate_pf2.txt); no gain, or a loss, on the wider tiles, which keep one set.
 template <int MT, int NT, int WGM, bool PF2 = false>
 __global__ __launch_bounds__(512, 2) void gemm_x6t2_kernel(X6TArgs g) {
-    constexpr int WGN = 8 / WGM;
-    constexpr int TM = 32 * WGM * MT, TN = 32 * WGN * NT;
-    static_assert((TM + TN) / 64 <= 8 && TM % 64 == 0 && TN % 64 == 0, "one 64-column group of the split per wave");
-    constexpr int HALF_A = TM * 16, HALF_B = TN * 16;         // bytes of one k-half of a plane
-    constexpr int PL_A = 2 * HALF_A, PL_B = 2 * HALF_B;
-    constexpr int BUF = 3 * (PL_A + PL_B);                    // one k-step of both operands
-    constexpr int XEPL = 36;
-    static_assert(2 * BUF >= 8 * 32 * XEPL * 4, "epilogue transposes live in the plane buffers");
-    __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * BUF];
+    using T = X6TTile<MT, NT, WGM>;
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * T::BUF];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WGN, wn = wave % WGN;
+    const int wm = wave / T::WGN, wn = wave % T::WGN;
     const int i = lane & 31, kh = lane >> 5;
-    const int nct = (g.N + TN - 1) / TN;
-    const int m0 = (int)(blockIdx.x / nct) * TM, n0 = (int)(blockIdx.x % nct) * TN;
+    const int nct = (g.N + T::TN - 1) / T::TN;
+    const int m0 = (int)(blockIdx.x / nct) * T::TM, n0 = (int)(blockIdx.x % nct) * T::TN;
     const int kbeg = blockIdx.y * g.kchunk, kend = min(g.K, kbeg + g.kchunk);
     const int nk = (kend - kbeg + TK - 1) / TK;
 
-    // this wave's group of the split (gemm_x6t_kernel's roles)
-    const bool is_a = wave < TM / 64;
-    const bool active = wave < (TM + TN) / 64;
-    const int cgrp = is_a ? wave : wave - TM / 64;
-    const int chunk = (lane & 7) + 8 * (lane >> 5);           // 0..15 within the 64-column group
-    const int kq = (lane >> 3) & 3;
-    const int col = cgrp * 64 + 4 * chunk;                    // first of this thread's 4 columns inside the tile
-    const int ld = is_a ? g.lda : g.ldb;
-    const bool col_ok = active && (is_a ? m0 + col < g.M : n0 + col < g.N);
-    const int tile = col >> 5, cin = col & 31;
-    const int st_base = (kq >> 1) * (is_a ? HALF_A : HALF_B) + tile * 512 + (kq & 1) * 8 + (is_a ? 0 : 3 * PL_A);
-    const int st_plane = is_a ? PL_A : PL_B;
-    const bool once = is_a ? nct == 1 : (int)gridDim.x == nct;     // rows exactly one workgroup of a split reads: non-temporal
+    PECLR_X6T_ROLES(wave);                                    // this wave's group of the split
 
-    const unsigned long long bp = reinterpret_cast<unsigned long long>(is_a ? g.A : g.B);
-    const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)bp), bhi = __builtin_amdgcn_readfirstlane((unsigned)(bp >> 32));
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>((unsigned long long)bhi << 32 | blo), (short)0,
-                                                                        __builtin_amdgcn_readfirstlane(g.K * ld * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = PECLR_WAVE_UNIFORM_RSRC(is_a ? g.A : g.B, g.K * ld * 4);
     const unsigned ld4b = __builtin_amdgcn_readfirstlane((unsigned)ld * 4u), stepb = TK * ld4b;
     unsigned off = col_ok ? (unsigned)(((kbeg + 4 * kq) * ld + (is_a ? m0 : n0) + col) * 4) : 0x80000000u;
 
@@ -731,35 +738,17 @@ __global__ __launch_bounds__(512, 2) void gemm_x6t2_kernel(X6TArgs g) {
         if (once) r4s[set][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(off + q * ld4b), 0, 2));
         else r4s[set][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(off + q * ld4b), 0, 0));
     };
-    struct Quarter { unsigned h, m; float r0, r1; };
-    auto q_first = [&](Quarter& s, int qp, int j, int set = 0) {
-        const float x0 = r4s[set][2 * qp][j], x1 = r4s[set][2 * qp + 1][j];
-        s.h = pk_bf16(x0, x1);
-        s.r0 = sub_f32(x0, __uint_as_float(s.h << 16));
-        s.r1 = sub_f32(x1, __uint_as_float(s.h & 0xFFFF0000u));
-    };
-    auto q_second = [&](Quarter& s) {
-        s.m = pk_bf16(s.r0, s.r1);
-        s.r0 = sub_f32(s.r0, __uint_as_float(s.m << 16));
-        s.r1 = sub_f32(s.r1, __uint_as_float(s.m & 0xFFFF0000u));
-    };
     auto q_third = [&](const Quarter& s, int buf, int qp, int j) {
-        unsigned char* d = lds + buf * BUF + st_base + 4 * qp + slot_of(cin + j) * 16;
-        *reinterpret_cast<unsigned*>(d) = s.h;
-        *reinterpret_cast<unsigned*>(d + st_plane) = s.m;
-        *reinterpret_cast<unsigned*>(d + 2 * st_plane) = pk_bf16(s.r0, s.r1);
+        q_store(s, lds + buf * T::BUF + st_base + 4 * qp + slot_of(cin + j) * 16, st_plane);
     };
 
     f32x16 acc[MT][NT];
 #pragma unroll
     for (int a = 0; a < MT; ++a)
 #pragma unroll
-        for (int y = 0; y < NT; ++y)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][y][r] = 0.f;
+        for (int y = 0; y < NT; ++y) zero(acc[a][y]);
 
-    const int fa = kh * HALF_A + (wm * MT) * 512 + slot_of(i) * 16;                  // + a * 512 + plane * PL_A
-    const int fb = 3 * PL_A + kh * HALF_B + (wn * NT) * 512 + slot_of(i) * 16;       // + y * 512 + plane * PL_B
+    PECLR_X6T_FRAGS;
 
     // prologue: step 0 -> buffer 0; step 1 in flight.  (Rows past the tensor read as zeros, rows past this slab are never multiplied.)
     if (active) {
@@ -769,7 +758,7 @@ __global__ __launch_bounds__(512, 2) void gemm_x6t2_kernel(X6TArgs g) {
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             Quarter s;
-            q_first(s, u >> 2, u & 3);
+            q_first(s, u >> 2, u & 3, r4s[0]);
             q_second(s);
             q_third(s, 0, u >> 2, u & 3);
         }
@@ -794,18 +783,18 @@ __global__ __launch_bounds__(512, 2) void gemm_x6t2_kernel(X6TArgs g) {
             const int t = t0 + par;
             if (PF2 && t >= nk) break;                        // (uniform)
             const int set = PF2 ? (par ^ 1) : 0;              // the set that holds step t + 1
-            const unsigned char* bufp = lds + (t & 1) * BUF;
+            const unsigned char* bufp = lds + (t & 1) * T::BUF;
             const int nb = (t + 1) & 1;
             uint4 af[MT][3], b0[2][YH], b1[YH], b2[YH];
 #pragma unroll
             for (int a = 0; a < MT; ++a)
 #pragma unroll
-                for (int p = 0; p < 3; ++p) af[a][p] = *reinterpret_cast<const uint4*>(bufp + fa + a * 512 + p * PL_A);
+                for (int p = 0; p < 3; ++p) af[a][p] = *reinterpret_cast<const uint4*>(bufp + fa + a * 512 + p * T::PL_A);
 #pragma unroll
             for (int y = 0; y < YH; ++y) {
                 b0[0][y] = *reinterpret_cast<const uint4*>(bufp + fb + y * 512);
-                b1[y] = *reinterpret_cast<const uint4*>(bufp + fb + y * 512 + PL_B);
-                b2[y] = *reinterpret_cast<const uint4*>(bufp + fb + y * 512 + 2 * PL_B);
+                b1[y] = *reinterpret_cast<const uint4*>(bufp + fb + y * 512 + T::PL_B);
+                b2[y] = *reinterpret_cast<const uint4*>(bufp + fb + y * 512 + 2 * T::PL_B);
             }
             Quarter qs;
             auto work_after = [&](int n) {                    // the pieces that follow MFMA n of the step
@@ -814,7 +803,7 @@ __global__ __launch_bounds__(512, 2) void gemm_x6t2_kernel(X6TArgs g) {
                 for (int e = 0; e < 24; ++e) {
                     if (e * NM / 24 != n) continue;
                     const int u = e / 3, k = e % 3, qp = u >> 2, j = u & 3;
-                    if (k == 0) q_first(qs, qp, j, set);
+                    if (k == 0) q_first(qs, qp, j, r4s[set]);
                     else if (k == 1) { q_second(qs); if (j == 3) issue_row(2 * qp, set); }
                     else { q_third(qs, nb, qp, j); if (j == 3) issue_row(2 * qp + 1, set); }
                 }
@@ -826,13 +815,12 @@ __global__ __launch_bounds__(512, 2) void gemm_x6t2_kernel(X6TArgs g) {
                 const unsigned char* nx = bufp + fb + (half + 1) * YH * 512;
 #pragma unroll
                 for (int pr = 0; pr < 6; ++pr) {
-                    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, QB[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
                     for (int y = 0; y < YH; ++y)
 #pragma unroll
                         for (int a = 0; a < MT; ++a) {
-                            const uint4& bb = QB[pr] == 0 ? b0[half & 1][y] : (QB[pr] == 1 ? b1[y] : b2[y]);
-                            acc[a][half * YH + y] = mma_bf16(af[a][PA[pr]], bb, acc[a][half * YH + y]);
+                            const uint4& bb = X6_QB[pr] == 0 ? b0[half & 1][y] : (X6_QB[pr] == 1 ? b1[y] : b2[y]);
+                            acc[a][half * YH + y] = mma_bf16(af[a][X6_PA[pr]], bb, acc[a][half * YH + y]);
                             PECLR_FENCE;
                             const int n = (half * 6 + pr) * YH * MT + y * MT + a;
                             // fragments of the second half: plane 0 into its second register set at once, planes 2 / 1 into the
@@ -840,11 +828,11 @@ __global__ __launch_bounds__(512, 2) void gemm_x6t2_kernel(X6TArgs g) {
                             if (more && pr == 0 && a == MT - 1) b0[(half + 1) & 1][y] = *reinterpret_cast<const uint4*>(nx + y * 512);
                             if (more && pr == 1 && a == MT - 1 && y == YH - 1) {
 #pragma unroll
-                                for (int yy = 0; yy < YH; ++yy) b2[yy] = *reinterpret_cast<const uint4*>(nx + yy * 512 + 2 * PL_B);
+                                for (int yy = 0; yy < YH; ++yy) b2[yy] = *reinterpret_cast<const uint4*>(nx + yy * 512 + 2 * T::PL_B);
                             }
                             if (more && pr == 4 && a == MT - 1 && y == YH - 1) {
 #pragma unroll
-                                for (int yy = 0; yy < YH; ++yy) b1[yy] = *reinterpret_cast<const uint4*>(nx + yy * 512 + PL_B);
+                                for (int yy = 0; yy < YH; ++yy) b1[yy] = *reinterpret_cast<const uint4*>(nx + yy * 512 + T::PL_B);
                             }
                             work_after(n);
                             PECLR_FENCE;
@@ -868,18 +856,19 @@ __global__ __launch_bounds__(512, 2) void gemm_x6t2_kernel(X6TArgs g) {
 #pragma unroll
         for (int y = 0; y < NT; ++y) {
             const int mt = m0 + (wm * MT + a) * 32, nt = n0 + (wn * NT + y) * 32;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) wlds[mfma32_row(r, kh) * XEPL + i] = acc[a][y][r];
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-                const int m = mt + er + 8 * jj, n = nt + ec;
-                const float4 c = *reinterpret_cast<const float4*>(wlds + (er + 8 * jj) * XEPL + ec);
-                if (m < g.M && n < g.N) *reinterpret_cast<float4*>(out + (size_t)m * g.ldc + n) = c;
-            }
+            PECLR_STORE_SLAB_TILE(wlds, i, kh, er, ec, acc[a][y], out, g.ldc, mt, nt, 0, g.M, g.N);
         }
 }
 
-constexpr int PF_SKINNY = 0;                                 // (tag of the 64-wide tiles in the launch table below; the first form's PF is 1 for every tile)
+#undef PECLR_STORE_SLAB_TILE
+#undef PECLR_WAVE_UNIFORM_RSRC
+#undef PECLR_SPLIT_STORE_QUAD
+#undef PECLR_X6T_ROLES
+#undef PECLR_X6T_FRAGS
+#undef PECLR_X6W_WAVE_ROLES
+#undef PECLR_X6W_LANE_ROLES
+#undef PECLR_X6W_FRAGS
+
 struct TilePick { int mt, nt, wgm; };
 // 1x1: workgroup tile 32 wgm mt x 256 / wgm nt.  64-wide sides (layer1) get tiles that are 64 wide on that side.
 inline TilePick pick_tile(int M, int N) {
@@ -889,6 +878,21 @@ inline TilePick pick_tile(int M, int N) {
 }
 inline int tile_m(const TilePick& t) { return 32 * t.wgm * t.mt; }
 inline int tile_n(const TilePick& t) { return 32 * (8 / t.wgm) * t.nt; }
+
+// 3x3: one of the nine-tap kernels, as its WGM = 2 (64 rows of dY's channels per workgroup) or WGM = 4 (128) instantiation
+typedef void (*X6WKernel)(X6TArgs);
+inline void launch_x6w(X6WKernel k2, X6WKernel k4, const X6TArgs& g, int n_slabs, hipStream_t s) {
+    if (g.M <= 64) hipLaunchKernelGGL(k2, dim3(((g.M + 63) / 64) * ((g.N + 63) / 64), n_slabs), dim3(512), 0, s, g);
+    else hipLaunchKernelGGL(k4, dim3(((g.M + 127) / 128) * ((g.N + 63) / 64), n_slabs), dim3(512), 0, s, g);
+}
+// 1x1: one tile in the form the caller has chosen.  stride 2: the first form with GEO; x6t2: the re-scheduled loop, with two register
+// sets (PF2) for the skinny (64-wide) tiles -- a template argument, so that each tile exists in one second form only
+template <int MT, int NT, int WGM, bool SKINNY>
+void launch_x6t(int stride, bool x6t2, dim3 grid, const X6TArgs& g, hipStream_t s) {
+    if (stride == 2) hipLaunchKernelGGL((gemm_x6t_kernel<MT, NT, WGM, true, 1>), grid, dim3(512), 0, s, g);
+    else if (x6t2) hipLaunchKernelGGL((gemm_x6t2_kernel<MT, NT, WGM, SKINNY>), grid, dim3(512), 0, s, g);
+    else hipLaunchKernelGGL((gemm_x6t_kernel<MT, NT, WGM, false, 1>), grid, dim3(512), 0, s, g);
+}
 
 }  // namespace
 }  // namespace peclr
@@ -933,19 +937,16 @@ static int gemm_x6t_host(int M, int N, int K, const float* A, int lda, const flo
         // (32-bit buffer offsets); PECLR_X6W2=0 keeps the first form for A/B runs
         static const bool x6w2 = getenv("PECLR_X6W2") ? atoi(getenv("PECLR_X6W2")) != 0 : true;
         if (x6w2 && stride == 1 && H * W <= X6W2_MAX_HW && H * W >= TK && K > 2 * (W + 2) && (long)(K + W + 2) * (lda > ldb ? lda : ldb) * 4 < 0x7fffffffL) {
-            if (M <= 64) hipLaunchKernelGGL(gemm_x6w2_kernel<2>, dim3(((M + 63) / 64) * ((N + 63) / 64), n_slabs), dim3(512), 0, s, g);
-            else hipLaunchKernelGGL(gemm_x6w2_kernel<4>, dim3(((M + 127) / 128) * ((N + 63) / 64), n_slabs), dim3(512), 0, s, g);
+            launch_x6w(gemm_x6w2_kernel<2>, gemm_x6w2_kernel<4>, g, n_slabs, s);
             return launch_status();
         }
         // ... its stride-2 arm: output images of at most 28 x 28 pixels (four table bytes per tap and pixel), X below 1 GiB (2^30 marks "no row")
         if (x6w2 && stride == 2 && H * W <= X6W2_S2_MAX_HW && H * W >= TK && (long)(K + 2 * TK) * lda * 4 < 0x7fffffffL &&
             4L * (K + 2 * H * W) * ldb * 4 < 0x3fffffffL) {
-            if (M <= 64) hipLaunchKernelGGL((gemm_x6w2_kernel<2, true>), dim3(((M + 63) / 64) * ((N + 63) / 64), n_slabs), dim3(512), 0, s, g);
-            else hipLaunchKernelGGL((gemm_x6w2_kernel<4, true>), dim3(((M + 127) / 128) * ((N + 63) / 64), n_slabs), dim3(512), 0, s, g);
+            launch_x6w(gemm_x6w2_kernel<2, true>, gemm_x6w2_kernel<4, true>, g, n_slabs, s);
             return launch_status();
         }
-        if (M <= 64) hipLaunchKernelGGL(gemm_x6w_kernel<2>, dim3(((M + 63) / 64) * ((N + 63) / 64), n_slabs), dim3(512), 0, s, g);
-        else hipLaunchKernelGGL(gemm_x6w_kernel<4>, dim3(((M + 127) / 128) * ((N + 63) / 64), n_slabs), dim3(512), 0, s, g);
+        launch_x6w(gemm_x6w_kernel<2>, gemm_x6w_kernel<4>, g, n_slabs, s);
         return launch_status();
     }
     const TilePick t = pick_tile(M, N);
@@ -953,26 +954,19 @@ static int gemm_x6t_host(int M, int N, int K, const float* A, int lda, const flo
     // the re-scheduled loop (gemm_x6t2_kernel): stride 1, operands below 2 GiB (32-bit buffer offsets); PECLR_X6T2=0 keeps the first form
     static const bool x6t2_on = getenv("PECLR_X6T2") ? atoi(getenv("PECLR_X6T2")) != 0 : true;
     const bool x6t2 = x6t2_on && stride == 1 && (long)(K + 2 * TK) * (lda > ldb ? lda : ldb) * 4 < 0x7fffffffL;
-#define PECLR_LAUNCH(MT_, NT_, WGM_, PF_)                                                                            \
-    do {                                                                                                             \
-        if (stride == 2) hipLaunchKernelGGL((gemm_x6t_kernel<MT_, NT_, WGM_, true, 1>), grid, dim3(512), 0, s, g);   \
-        else if (x6t2) hipLaunchKernelGGL((gemm_x6t2_kernel<MT_, NT_, WGM_, (PF_) == PF_SKINNY>), grid, dim3(512), 0, s, g); \
-        else hipLaunchKernelGGL((gemm_x6t_kernel<MT_, NT_, WGM_, false, 1>), grid, dim3(512), 0, s, g);              \
-    } while (0)
     if (t.wgm == 2) {
-        if (t.nt == 2) PECLR_LAUNCH(1, 2, 2, PF_SKINNY);
-        else PECLR_LAUNCH(1, 1, 2, PF_SKINNY);
+        if (t.nt == 2) launch_x6t<1, 2, 2, /*skinny=*/true>(stride, x6t2, grid, g, s);
+        else launch_x6t<1, 1, 2, /*skinny=*/true>(stride, x6t2, grid, g, s);
     } else if (t.nt == 1) {
-        if (t.mt == 2) PECLR_LAUNCH(2, 1, 4, PF_SKINNY);
-        else PECLR_LAUNCH(1, 1, 4, PF_SKINNY);
+        if (t.mt == 2) launch_x6t<2, 1, 4, /*skinny=*/true>(stride, x6t2, grid, g, s);
+        else launch_x6t<1, 1, 4, /*skinny=*/true>(stride, x6t2, grid, g, s);
     } else if (t.mt == 2 && t.nt == 4) {                       // 256 x 256: the first form is the faster one (see gemm_x6t2_kernel)
         if (stride == 2) hipLaunchKernelGGL((gemm_x6t_kernel<2, 4, 4, true, 1>), grid, dim3(512), 0, s, g);
         else hipLaunchKernelGGL((gemm_x6t_kernel<2, 4, 4, false, 1>), grid, dim3(512), 0, s, g);
     }
-    else if (t.mt == 2) PECLR_LAUNCH(2, 2, 4, 1);
-    else if (t.nt == 4) PECLR_LAUNCH(1, 4, 4, 1);
-    else PECLR_LAUNCH(1, 2, 4, 1);
-#undef PECLR_LAUNCH
+    else if (t.mt == 2) launch_x6t<2, 2, 4, /*skinny=*/false>(stride, x6t2, grid, g, s);
+    else if (t.nt == 4) launch_x6t<1, 4, 4, /*skinny=*/false>(stride, x6t2, grid, g, s);
+    else launch_x6t<1, 2, 4, /*skinny=*/false>(stride, x6t2, grid, g, s);
     return launch_status();
 }
 

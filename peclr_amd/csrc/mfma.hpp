@@ -19,6 +19,12 @@ __device__ __forceinline__ f32x16 mma_f16(const uint4& a, const uint4& b, f32x16
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
 }
 
+// ---- the six products of the exact bf16 triple (x == h + m + l: planes 0, 1, 2; m.l, l.m and l.l are dropped): product pr is
+// plane X6_PA[pr] of the first operand times plane X6_QB[pr] of the second -- l.h, h.l, m.m, m.h, h.m, h.h, smallest first.  An
+// accumulator receives them in THIS order: the order is part of the numerical contract (it fixes the rounding of every fp32
+// result, and the kernels that exist in two forms are tested for bit equality).
+constexpr int X6_PA[6] = {2, 0, 1, 1, 0, 0}, X6_QB[6] = {0, 2, 1, 0, 1, 0};
+
 // ---- per-format pieces of the 16-bit kernels: MFMA, 16-bit -> fp32, fp32 pair -> packed word (round to nearest even)
 struct BF16 {
     static constexpr int io = PECLR_DTYPE_BF16;
