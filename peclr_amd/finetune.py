@@ -14,10 +14,14 @@
     model.export("rn50_finetuned.pth")                                 # tools/pred_freihand.py --model_path loads it
 
 Nothing in a step synchronises with the host, so `Trainer(hip_graph=True)` records forward, backward and the fused optimiser
-as one hipGraph.  Single process and fp32 only: `setup()` refuses anything else.
+as one hipGraph.  Single process only.  Precision is the trainer's: fp32, or bf16 / fp16 (16) with the precision split of
+`FreiHANDPredictor` -- the backbone up to the pooled fp32 features under `torch.autocast` on the 16-bit convolution kernels,
+head, losses, metrics and lifting in fp32 / float64 as before; fp16 adds the trainer's `DeviceLossScaler`, which decides a
+skipped step inside the fused optimiser launch, so the 16-bit step is one hipGraph too.  `setup()` refuses anything else.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Dict, List, Optional
 
@@ -25,8 +29,9 @@ import torch
 from torch import Tensor
 
 from . import _capi
+from . import bn2d as _bn2d
 from .module import BaseModel
-from .pose import RN25DwMLPref
+from .pose import FreiHANDPredictor, RN25DwMLPref
 from .pose_loss import LOSS_NAMES, PoseLoss
 from .pose_metrics import step_metrics
 from .port import encoder_entries, get_latest_checkpoint
@@ -38,6 +43,9 @@ VAL_KEYS = tuple(f"{n}_val" for n in LOSS_NAMES + METRIC_NAMES) + ("loss",)
 EVALUATE_KEYS = ("Mean_EPE_3D", "Median_EPE_3D", "AUC", "Mean_EPE_3D_procrustes", "Median_EPE_3D_procrustes", "auc_procrustes")
 # encoder.features[i] of a pretraining checkpoint -> the torchvision name the pose model's backbone uses (encoder.py)
 _FEATURES = {"0": "conv1", "1": "bn1", "4": "layer1", "5": "layer2", "6": "layer3", "7": "layer4"}
+# the trainer's spellings of a precision -> ours; the autocast dtype of the 16-bit ones
+_PRECISIONS = {"fp32": "fp32", 32: "fp32", "32": "fp32", "bf16": "bf16", "fp16": "fp16", 16: "fp16", "16": "fp16"}
+_AUTOCAST = {"bf16": torch.bfloat16, "fp16": torch.float16}
 
 
 class SupervisedPose(BaseModel):
@@ -47,13 +55,28 @@ class SupervisedPose(BaseModel):
     `RN25DwMLPref`, and the state_dict keys are "model." + the reference's `RN_25D_wMLPref` keys, in its order.
 
     evaluator: an optional `PoseEvaluator`; `validation_step` then also feeds it (`update_25d`) and `validation_epoch_end`
-    adds the reference's evaluate() metrics to `validation_metrics_epoch` and resets it."""
+    adds the reference's evaluate() metrics to `validation_metrics_epoch` and resets it.
 
-    def __init__(self, config, evaluator=None):
+    fold_bn (16-bit precisions only; always off in fp32): `validation_step` applies the eval-mode BatchNorm layers of the
+    bottleneck blocks in the convolution epilogues (`bn2d.fold_plan`), as `FreiHANDPredictor` does; None = its
+    `FOLD_BN_DEFAULT`.
+
+    precision: "fp32" until `setup()` has read the trainer's, then "fp32" | "bf16" | "fp16"."""
+
+    def __init__(self, config, evaluator=None, fold_bn=None):
         super().__init__(config)
         self.model = RN25DwMLPref(config.backend_model)
         self.loss = PoseLoss(config.loss_weights)
         self.evaluator = evaluator
+        self._fold_bn_arg = fold_bn
+        self.precision = "fp32"
+
+    @property
+    def fold_bn(self) -> bool:
+        """What `validation_step` folds at the present precision."""
+        if self.precision == "fp32":
+            return False
+        return FreiHANDPredictor.FOLD_BN_DEFAULT if self._fold_bn_arg is None else bool(self._fold_bn_arg)
 
     # ---- paths
     def enable_hip(self) -> "SupervisedPose":
@@ -92,7 +115,10 @@ class SupervisedPose(BaseModel):
 
     def validation_step(self, batch: Dict[str, Tensor], batch_idx: int) -> Dict[str, Tensor]:
         """Eval mode, no gradient: the one-launch evaluation head.  Returns the training keys with the `_val` suffix
-        (`loss_2d_val` ... `EPE_median_3d_val`), then `loss`.  The 3D joints are lifted from the 2.5D prediction with the
+        (`loss_2d_val` ... `EPE_median_3d_val`), then `loss`.  In a 16-bit run the backbone runs under the run's autocast, with
+        eval BatchNorm folded into the convolution epilogues when `fold_bn` says so; `Trainer.fit` calls this outside its own
+        autocast, so the module enters both itself.  In fp32 it enters neither: the launches are those of before.
+        The 3D joints are lifted from the 2.5D prediction with the
         CLOSED-FORM root depth (`z_root_calc=None`), as the reference's evaluate() lifts them: validation `loss_3d_val` and
         the 3D metrics use that depth, while the training step uses the MLP-refined `zroot`."""
         self._need_hip_kernels("validation_step")
@@ -100,7 +126,8 @@ class SupervisedPose(BaseModel):
             raise RuntimeError("SupervisedPose.validation_step runs in eval mode (call .eval() first): in train mode the forward "
                                "pass would update the BatchNorm running statistics")
         with torch.no_grad():
-            kp25d = self.model(batch["image"], batch["K"])["kp25d"].contiguous()
+            with self._eval_precision():
+                kp25d = self.model(batch["image"], batch["K"])["kp25d"].contiguous()
             total, losses = self.loss(kp25d, batch, z_root_calc=None)
             kp3d = joints25d_to_3d(kp25d, batch["scale"], batch["K"])
             metrics = step_metrics(kp25d, batch["joints"], kp3d, batch["joints3D"])
@@ -109,6 +136,15 @@ class SupervisedPose(BaseModel):
         self.plot_params = {"prediction": kp25d, "ground_truth": batch["joints"], "input": batch["image"]}
         return {**{f"{n}_val": losses[n] for n in LOSS_NAMES},
                 **{f"{n}_val": m for n, m in zip(METRIC_NAMES, metrics.unbind(0))}, "loss": total}
+
+    def _eval_precision(self):
+        """Context of the validation forward: nothing in fp32; the autocast dtype and the fold switch of a 16-bit run."""
+        if self.precision == "fp32":
+            return contextlib.nullcontext()
+        stack = contextlib.ExitStack()
+        stack.enter_context(torch.autocast("cuda", dtype=_AUTOCAST[self.precision]))
+        stack.enter_context(_bn2d.routing(fold_eval_bn=self.fold_bn))
+        return stack
 
     def validation_epoch_end(self, outputs: List[dict]):
         """The epoch means of the step dicts and, with an evaluator, the metrics of evaluate() over everything it was fed
@@ -124,9 +160,17 @@ class SupervisedPose(BaseModel):
         if self.trainer.world_size > 1:
             raise RuntimeError("SupervisedPose is single-process only: the trainer's data-parallel path reads the pretraining "
                                f"batch keys (world_size = {self.trainer.world_size})")
-        precision = getattr(self.trainer, "precision", "fp32")
-        if precision not in ("fp32", 32, "32"):
-            raise RuntimeError(f"SupervisedPose trains in fp32 only, the trainer asks for precision {precision!r}")
+        asked = getattr(self.trainer, "precision", "fp32")
+        precision = None if isinstance(asked, bool) or not isinstance(asked, (str, int)) else _PRECISIONS.get(asked)
+        if precision is None:
+            raise RuntimeError(f"SupervisedPose trains in fp32, bf16 or fp16 (16), the trainer asks for precision {asked!r}; "
+                               "without the HIP kernels it trains in fp32 only")
+        m = self.model
+        if precision != "fp32" and not (m.backend_model.bn1.hip and m.hip_training):
+            raise RuntimeError(f"the trainer asks for precision {asked!r}, but without the HIP kernels SupervisedPose trains in fp32 "
+                               "only: the 16-bit step runs on the in-tree 16-bit convolution kernels and has no stock-torch arm -- "
+                               "call .to(device).enable_hip() before Trainer.attach / fit")
+        self.precision = precision
         super().setup(stage)
 
     # ---- weights in, weights out

@@ -1,8 +1,11 @@
-"""Time of one supervised fine-tuning step of the 2.5D pose model (ResNet-50, B = 128, 224 x 224, fp32): forward, the four
-losses, the step metrics, backward and the fused Adam step -- `SupervisedPose` on the HIP kernels, issued eagerly and replayed
-from the one hipGraph `Trainer.capture_step_graph` records, against the stock-torch step of the same model (tools/
-stock_pose_step.py: no `enable_hip*`, same optimiser) in the same run on the same machine.  And the step-metrics launch
-(`peclr_pose_step_metrics_f32`, both pairs) against the torch composition of calculate_metrics for two pairs.
+"""Time of one supervised fine-tuning step of the 2.5D pose model (ResNet-50, B = 128, 224 x 224): forward, the four losses, the
+step metrics, backward and the fused Adam step -- `SupervisedPose` on the HIP kernels in fp32, bf16 and fp16 (the backbone under
+the trainer's autocast on the 16-bit convolution kernels; fp16 with the `DeviceLossScaler` inside the optimiser launch), each
+issued eagerly and replayed from the one hipGraph `Trainer.capture_step_graph` records, against the stock-torch step of the same
+model (tools/stock_pose_step.py: no `enable_hip*`, same optimiser) in fp32 and under torch's autocast (fp16: with
+`torch.amp.GradScaler`), all in the same run on the same machine.  Then one `validation_step` at the same batch: fp32, and
+16-bit with the eval BatchNorm layers as passes of their own and folded into the convolution epilogues.  And the step-metrics
+launch (`peclr_pose_step_metrics_f32`, both pairs) against the torch composition of calculate_metrics for two pairs.
 
 Warm; a run is ITERS back-to-back steps timed by device events and, around the same steps, by the wall clock with the device
 waited for; the arms alternate run by run; median, minimum and maximum over the runs.  What the figures are: for the whole
@@ -10,7 +13,7 @@ step the device is busy for tens of milliseconds per step, so every figure is DE
 the host cannot issue fast enough).  For the metrics the eager figures are LAUNCH-ISSUE RATES -- the device finishes each launch
 before the host has issued the next -- and only the figures from a hipGraph (each composition captured once) are device time.
 
-    python tools/pose_finetune_timing.py [--batch 128] [--size 224] [--iters 10] [--runs 5]
+    python tools/pose_finetune_timing.py [--precision fp32 bf16 fp16] [--batch 128] [--size 224] [--iters 10] [--runs 5]
 """
 import argparse
 import copy
@@ -56,6 +59,8 @@ def _report(title, fns, iters, runs, base):
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--precision", nargs="+", choices=("fp32", "bf16", "fp16"), default=["fp32", "bf16", "fp16"],
+                    help="the precisions whose arms are timed (fp32 is the comparison base of the 16-bit ones: keep it)")
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--size", type=int, default=224)
     ap.add_argument("--iters", type=int, default=10)
@@ -66,7 +71,7 @@ def main(argv=None):
     import torch
 
     from peclr_amd import SupervisedAugmenter, SupervisedPose, Trainer, step_metrics, supervised_config
-    from stock_pose_step import StockPose, metrics as torch_metrics
+    from stock_pose_step import StockPose, metrics as torch_metrics, use_torch_grad_scaler
 
     b, size, dev = args.batch, args.size, "cuda"
     g = np.random.default_rng(0)
@@ -84,17 +89,7 @@ def main(argv=None):
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
         torch.manual_seed(0)
-        hip = SupervisedPose(cfg).to(dev).train()
-        stock = StockPose(cfg).to(dev).to(memory_format=torch.channels_last).train()
-        stock.load_state_dict(hip.state_dict())
-        graph_m = copy.deepcopy(hip).enable_hip()
-        hip.enable_hip()
-        t_graph = Trainer(max_epochs=1).attach(graph_m)
-        t_graph.zero_grad()
-        t_graph.capture_step_graph(batch, warmup=2)
-        t_hip, t_stock = Trainer(max_epochs=1).attach(hip), Trainer(max_epochs=1).attach(stock)
-        for t in (t_hip, t_stock):
-            t.zero_grad()
+        first = SupervisedPose(cfg).to(dev).train()
         count = [0]
 
         def eager(trainer):
@@ -103,12 +98,52 @@ def main(argv=None):
                 return trainer.training_micro_step(batch, count[0])
             return step
 
-        med = _report("fine-tuning step", {"HIP kernels, eager": eager(t_hip), "HIP kernels, hipGraph replay": t_graph.replay_step,
-                                           "stock torch operators, eager": eager(t_stock)}, args.iters, args.runs, base)
-        for name in ("HIP kernels, eager", "HIP kernels, hipGraph replay"):
-            print(json.dumps(dict(base, what=f"fine-tuning step: stock torch operators, eager / {name}, medians by device events",
-                                  ratio=round(med["stock torch operators, eager"] / med[name], 2))), flush=True)
-        t_graph.close()
+        # every graph is captured before the first eager step of the process (Trainer.capture_step_graph)
+        fns, graphs, eager_arms = {}, [], []
+        for p in args.precision:
+            graph_m = copy.deepcopy(first).enable_hip()
+            t_graph = Trainer(max_epochs=1, precision=p).attach(graph_m)
+            t_graph.zero_grad()
+            t_graph.capture_step_graph(batch, warmup=2)
+            graphs.append(t_graph)
+            fns[f"HIP kernels {p}, hipGraph replay"] = t_graph.replay_step
+        for p in args.precision:
+            hip = copy.deepcopy(first).enable_hip()
+            stock = StockPose(cfg).to(dev).to(memory_format=torch.channels_last).train()
+            stock.load_state_dict(first.state_dict())
+            t_hip = Trainer(max_epochs=1, precision=p).attach(hip)
+            t_stock = use_torch_grad_scaler(Trainer(max_epochs=1, precision=p).attach(stock))
+            for t in (t_hip, t_stock):
+                t.zero_grad()
+            fns[f"HIP kernels {p}, eager"] = eager(t_hip)
+            fns[f"stock torch operators {p}, eager"] = eager(t_stock)
+        med = _report("fine-tuning step", fns, args.iters, args.runs, base)
+        for p in args.precision:
+            for other in dict.fromkeys(("fp32", p)):
+                for base_arm in (f"stock torch operators {other}, eager", f"HIP kernels {other}, eager", f"HIP kernels {other}, hipGraph replay"):
+                    for name in (f"HIP kernels {p}, eager", f"HIP kernels {p}, hipGraph replay"):
+                        if base_arm in med and base_arm != name and (other != p or base_arm.startswith("stock")):
+                            print(json.dumps(dict(base, what=f"fine-tuning step: {base_arm} / {name}, medians by device events",
+                                                  ratio=round(med[base_arm] / med[name], 2))), flush=True)
+        for t in graphs:
+            t.close()
+        del fns, graphs
+
+        # ---- one validation step: fp32, and 16-bit with the eval BatchNorm layers unfolded and folded
+        vals = {}
+        for p in args.precision:
+            for fold in ((False,) if p == "fp32" else (False, True)):
+                vm = SupervisedPose(cfg, fold_bn=fold).to(dev).enable_hip()
+                vm.load_state_dict(first.state_dict())
+                Trainer(max_epochs=1, precision=p).attach(vm.eval())
+                name = "HIP kernels fp32" if p == "fp32" else f"HIP kernels {p}, BatchNorm {'folded' if fold else 'unfolded'}"
+                vals[name] = (lambda m: lambda: m.validation_step(batch, 0))(vm)
+        med = _report("validation step", vals, args.iters, args.runs, base)
+        for name in vals:
+            if name != "HIP kernels fp32" and "HIP kernels fp32" in med:
+                print(json.dumps(dict(base, what=f"validation step: HIP kernels fp32 / {name}, medians by device events",
+                                      ratio=round(med["HIP kernels fp32"] / med[name], 2))), flush=True)
+        del vals
 
         # ---- the metrics launch against the torch composition, two pairs
         p1, t1 = batch["joints"] + torch.randn_like(batch["joints"]) * 4, batch["joints"]

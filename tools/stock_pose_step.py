@@ -2,11 +2,18 @@
 tools/finetune_synthetic.py and tools/pose_finetune_timing.py: the model's stock forward (no `enable_hip*`), cal_l1_loss and
 cal_3d_loss over convert_2_5D_to_3D with `torch.inverse`, and calculate_metrics, each from its formula.  `StockPose` is
 `SupervisedPose` with that composition as its `training_step` / `validation_step`; everything else (optimiser, schedule,
-hooks) is inherited, so the two arms differ in the kernels of the step alone."""
+hooks) is inherited, so the two arms differ in the kernels of the step alone.
+
+In a 16-bit run (`Trainer(precision="bf16" | 16)`) it is the stock 16-bit arm: the trainer's `torch.autocast` around the stock
+forward -- torch's autocast also runs `fc` and the MLP's Linear layers in 16 bits -- and, for fp16, `torch.amp.GradScaler`
+(`use_torch_grad_scaler`).  `SupervisedPose.setup` refuses 16 bits without the HIP kernels; this arm exists to be compared against."""
+import contextlib
+
 import torch
 
 from peclr_amd import SupervisedPose
-from peclr_amd.finetune import METRIC_NAMES
+from peclr_amd.finetune import _AUTOCAST, _PRECISIONS, METRIC_NAMES
+from peclr_amd.module import BaseModel
 from peclr_amd.pose_loss import LOSS_NAMES
 
 
@@ -42,7 +49,22 @@ def metrics(pred, truth, pred2, truth2):
     return out
 
 
+def use_torch_grad_scaler(trainer):
+    """fp16: torch's own GradScaler around the optimiser, instead of the `DeviceLossScaler` the trainer attaches to the fused one
+    (call after `attach`, before the first step)."""
+    if trainer.precision == "fp16":
+        trainer._scaler = torch.amp.GradScaler("cuda")
+    return trainer
+
+
 class StockPose(SupervisedPose):
+    def setup(self, stage):
+        self.precision = _PRECISIONS[self.trainer.precision]
+        BaseModel.setup(self, stage)
+
+    def _autocast(self):
+        return contextlib.nullcontext() if self.precision == "fp32" else torch.autocast("cuda", dtype=_AUTOCAST[self.precision])
+
     def _values(self, out, batch, z_root, kp3d, suffix):
         ls = losses(out["kp25d"], batch, z_root)
         with torch.no_grad():
@@ -60,7 +82,9 @@ class StockPose(SupervisedPose):
 
     def validation_step(self, batch, batch_idx):
         with torch.no_grad():
-            out = self.model(batch["image"], batch["K"])
+            with self._autocast():
+                out = self.model(batch["image"], batch["K"])
+            out = {k: v.float() for k, v in out.items()}
             kp3d = lift(out["kp25d"], batch["scale"], batch["K"])
             if self.evaluator is not None:
                 self.evaluator.update_25d(out["kp25d"].contiguous(), batch["scale"], batch["K"], batch["joints3D"])
