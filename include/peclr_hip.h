@@ -700,6 +700,13 @@ int peclr_conv_h_bnact(int dtype, int NB, int H, int W, int Cin, int Cout, int t
 int peclr_wgrad3_h_slabs(int M, int N, int images, int H, int W);
 int peclr_wgrad3_h(int dtype, int M, int N, int images, int H, int W, const void* A, const void* B, float* slabs, int n_slabs,
                    const void* zeros, peclr_stream_t stream);
+/* ... and the same for rows of 63 <= W <= 512 pixels (narrower ones are refused here: PECLR_ERR_SHAPE / 0 slabs): every image is
+ * cut into ceil(W / 61) column segments of near-equal width, each a pseudo-image of the padded space whose rows carry the
+ * neighbouring segments' columns of X (zero outside the image) as halo slots, so the same ring holds two padded rows of any
+ * width.  Same operands, slab layout and fixed-order reduction as peclr_wgrad3_h. */
+int peclr_wgrad3w_h_slabs(int M, int N, int images, int H, int W);
+int peclr_wgrad3w_h(int dtype, int M, int N, int images, int H, int W, const void* A, const void* B, float* slabs, int n_slabs,
+                    const void* zeros, peclr_stream_t stream);
 int peclr_wgrad_h_slabs(int M, int N, int K);
 int peclr_wgrad_h(int dtype, int M, int N, int K, const void* A, int lda, const void* B, int ldb, float* slabs, int n_slabs,
                   int stride, int Ho, int Wo, const void* zeros, peclr_stream_t stream);

@@ -114,6 +114,8 @@ SIGNATURES = {
     "peclr_conv3x3_s2_dgrad_h": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P]),
     "peclr_wgrad3_h_slabs": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "peclr_wgrad3_h": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P]),
+    "peclr_wgrad3w_h_slabs": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "peclr_wgrad3w_h": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P]),
     "peclr_wgrad_h_slabs": (c_int, [c_int, c_int, c_int]),
     "peclr_wgrad_h": (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "peclr_lars_sumsq_f32": (c_int, [_P, _P, c_int, _P, _P, c_int, _P, _P]),
@@ -907,12 +909,16 @@ def conv_h_bnact(x: torch.Tensor, planes: torch.Tensor, cout: int, scale_shift: 
     return y
 
 
+WGRAD3_MAX_W, WGRAD3W_MAX_W = 62, 512      # widest row of peclr_wgrad3_h (one ring) and of peclr_wgrad3w_h (column segments)
+
+
 def wgrad_h_ok(gy: torch.Tensor, x: torch.Tensor, taps: int, stride: int) -> bool:
     """Does peclr_wgrad_h take this weight gradient?  (1x1 convolutions, stride 1 or 2, channel counts multiples of 32.)"""
     cout, cin = gy.shape[1], x.shape[1]
-    if taps == 9:       # 3x3 / padding 1 / stride 1 (peclr_wgrad3_h); the stride-2 ones stay on MIOpen (faster there)
+    if taps == 9:       # 3x3 / padding 1 / stride 1 (peclr_wgrad3_h, rows wider than 62 pixels: peclr_wgrad3w_h); the stride-2 ones
+        #                 stay on MIOpen (faster there)
         return (stride == 1 and cout % 64 == 0 and cin % 64 == 0 and gy.dtype in _HALF_IO and x.dtype == gy.dtype
-                and x.shape[2] == stride * gy.shape[2] and x.shape[3] == stride * gy.shape[3] and gy.shape[3] <= 62
+                and x.shape[2] == stride * gy.shape[2] and x.shape[3] == stride * gy.shape[3] and gy.shape[3] <= WGRAD3W_MAX_W
                 and gy.shape[0] * gy.shape[2] * gy.shape[3] >= 512)
     return (taps == 1 and stride in (1, 2) and cout % 32 == 0 and cin % 32 == 0 and gy.dtype in _HALF_IO and x.dtype == gy.dtype
             and gy.shape[0] * gy.shape[2] * gy.shape[3] >= 32
@@ -921,7 +927,7 @@ def wgrad_h_ok(gy: torch.Tensor, x: torch.Tensor, taps: int, stride: int) -> boo
 
 def wgrad_h(gy: torch.Tensor, x: torch.Tensor, taps: int = 1, stride: int = 1, tag: str = "conv1x1_wgrad") -> torch.Tensor:
     """dW [Cout, taps * Cin] (fp32) of a 1x1 (taps = 1) or 3x3 / padding-1 (taps = 9) convolution, stride 1 or 2, from 16-bit NHWC
-    activations gy [N, Cout, Ho, Wo], x [N, Cin, H, W] (peclr_wgrad_h / peclr_wgrad3_h +
+    activations gy [N, Cout, Ho, Wo], x [N, Cin, H, W] (peclr_wgrad_h / peclr_wgrad3_h / peclr_wgrad3w_h +
     peclr_slab_reduce_f32: fixed-order split-K, deterministic)."""
     if not wgrad_h_ok(gy, x, taps, stride):
         raise PeclrHipError(f"wgrad_h: unsupported problem gy {tuple(gy.shape)} x {tuple(x.shape)} taps {taps} stride {stride}")
@@ -931,13 +937,16 @@ def wgrad_h(gy: torch.Tensor, x: torch.Tensor, taps: int = 1, stride: int = 1, t
     gp, xp = _nhwc_ptr(gy, "wgrad_h gy", gy.dtype), _nhwc_ptr(x, "wgrad_h x", gy.dtype)
     k = nb * ho * wo
     if taps == 9:
-        ns = lib().peclr_wgrad3_h_slabs(cout, cin, nb, ho, wo)
+        if wo <= WGRAD3_MAX_W:
+            entry, kernel, ns = "peclr_wgrad3_h", "wgrad3_h_kernel", lib().peclr_wgrad3_h_slabs(cout, cin, nb, ho, wo)
+        else:
+            entry, kernel, ns = "peclr_wgrad3w_h", "wgrad3_hw_kernel", lib().peclr_wgrad3w_h_slabs(cout, cin, nb, ho, wo)
         if ns < 1:
             raise PeclrHipError(f"wgrad_h: unsupported 3x3 shape M={cout} N={cin} {nb} x {ho} x {wo}")
         slabs = torch.empty((ns, cout, 9 * cin), device=gy.device, dtype=torch.float32)
-        _launch("conv3x3_wgrad" if tag == "conv1x1_wgrad" else tag, "peclr_wgrad3_h",
+        _launch("conv3x3_wgrad" if tag == "conv1x1_wgrad" else tag, entry,
                 io, cout, cin, nb, ho, wo, gp, xp, slabs.data_ptr(), ns, _hzeros(gy.device, gy.dtype).data_ptr(), _stream(),
-                nbytes=2 * k * (cout + cin) + 4 * ns * cout * 9 * cin, flops=18 * cout * cin * k, kernel="wgrad3_h_kernel")
+                nbytes=2 * k * (cout + cin) + 4 * ns * cout * 9 * cin, flops=18 * cout * cin * k, kernel=kernel)
     else:
         ns = lib().peclr_wgrad_h_slabs(cout, cin, k)
         if ns < 1:

@@ -149,6 +149,9 @@ class Routing:
     # by the BatchNorm pass that produced it); anything else runs the six-product kernels as before
     x6_pair: bool = dataclasses.field(default_factory=lambda: _env_flag("PECLR_X6_PAIR"))
     wgrad16: bool = dataclasses.field(default_factory=lambda: _env_flag("PECLR_WGRAD16"))              # ... and their weight gradients
+    # ... the 3x3 ones of rows wider than 62 pixels too (inputs above 248 px: peclr_wgrad3w_h, column segments; off: MIOpen there.
+    # On: 0.39 - 0.58 of MIOpen's time at layer1 of 448 and 256 px inputs, bf16 and fp16: profiles/wgrad3_wide_timing.txt)
+    wgrad16_wide: bool = dataclasses.field(default_factory=lambda: _env_flag("PECLR_WGRAD16_WIDE"))
     stem_wgrad: bool = dataclasses.field(default_factory=lambda: _env_flag("PECLR_STEM_WGRAD"))        # ... and its weight gradient
     stem: bool = dataclasses.field(default_factory=lambda: _env_flag("PECLR_STEM"))                    # the 7x7 / stride-2 stem forward in-tree (csrc/stem.hip)
     # 16-bit prediction: the eval-mode BatchNorm layers of the bottleneck blocks folded into the 16-bit convolutions' epilogues
@@ -1125,7 +1128,9 @@ def _wgrad_h(gy: Tensor, x: Tensor, conv, stride: int):
     (+ its cast to fp32)."""
     w = conv.weight
     taps = w.shape[2] * w.shape[3]
-    if ROUTING.wgrad16 and w.is_contiguous(memory_format=torch.channels_last) and _capi.wgrad_h_ok(gy, x, taps, stride):
+    wide = taps == 9 and gy.shape[3] > _capi.WGRAD3_MAX_W              # rows the one-ring kernel refuses: `wgrad16_wide`
+    if (ROUTING.wgrad16 and (ROUTING.wgrad16_wide or not wide) and w.is_contiguous(memory_format=torch.channels_last)
+            and _capi.wgrad_h_ok(gy, x, taps, stride)):
         return _on_side_stream(w, (gy, x), lambda: _like_param(_capi.wgrad_h(gy, x, taps, stride), w, taps))     # [Cout, taps * Cin] fp32
     return _conv_wgrad(gy, x, w, conv.stride, conv.padding, w)
 

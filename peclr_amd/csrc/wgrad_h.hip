@@ -290,8 +290,8 @@ inline void magic_div(unsigned d, unsigned& m, unsigned& sh) {
 }
 
 // RINGP: slots of the X ring (power of two >= 2 * roundup(W + 2, 32) + 96: the k-step's 32 slots, lead and lag of the taps, and
-// the group in flight; 256 slots = 32 KiB serve W <= 62, i.e. every 3x3 of ResNet at 224 x 224 -- wider rows stay on MIOpen:
-// a 512-slot ring would leave the 64 KiB an LDS-DMA can address)
+// the group in flight; 256 slots = 32 KiB serve W <= 62, i.e. every 3x3 of ResNet at 224 x 224 -- a 512-slot ring would leave
+// the 64 KiB an LDS-DMA can address, so wider rows are cut into column segments that fit: wgrad3_hw_kernel below)
 // Stride 2 (g.s2): output pixel (oh, ow) meets input pixel (2 oh + a - 1, 2 ow + b - 1) under tap (a, b).  Split X into its four
 // parity planes X_pq[i][j] = X[2 i + p][2 j + q] (each H x W, like dY): tap row a reads plane p = (a != 1) at row shift -1 (a = 0)
 // or 0, columns alike -- so plane (1, 1) serves the four corner taps, (1, 0) and (0, 1) two taps each, (0, 0) the centre, all with
@@ -406,6 +406,140 @@ __global__ __launch_bounds__(256, 2) void wgrad3_h_kernel(W3Args g) {
     }
 }
 
+// ---- the same for rows of 63 pixels and more: a COLUMN-SEGMENTED padded space.  Every image is cut into nseg = ceil(W / 61)
+// column segments of near-equal width (seg_base, + 1 for the first seg_extra), and each (image, segment) is a PSEUDO-IMAGE of
+// the padded space: a zero row in front, then H rows of S = (widest segment) + 2 slots -- slot 0 the image column LEFT of the
+// segment, slots 1 .. Ws the segment's own, slot Ws + 1 the column RIGHT of it, the rest (a segment one narrower than the widest)
+// zero.  The operands differ in what a halo slot holds: dY's are zero (every output pixel is summed in exactly one segment), X's
+// are the neighbouring segment's real pixels, zero only outside the image.  Tap (a, b) of slot p is X's slot
+// p + (a - 1) S + (b - 1) for every p, as above; 35 <= S + 1 <= 64, so lead and lag are 64 slots and the 256-slot ring serves any
+// width (2 - 6 % more slots than wgrad3_h_kernel's space would have: 4.5 % at 112 x 112).  Ring, stages, waits, fragment reads and
+// slab store are wgrad3_h_kernel's (a sibling and not a template arm of it: any change to that kernel's text, even wrapping its
+// body in a function, moved its register allocation); only the slot -> address map of the DMA lanes differs.
+struct W3WArgs {
+    const h16_t* A;                      // dY [images * H * W][lda]
+    const h16_t* B;                      // X  [images * H * W][ldb]
+    float* slabs;                        // [n_slabs][M][9 * N]
+    int M, N, lda, ldb;
+    int H, W, images;
+    int S, nseg, seg_base, seg_extra;
+    int P;                               // padded slots: images * nseg * (H + 1) * S
+    int pchunk;                          // padded slots per slab (multiple of 32)
+    const h16_t* zeros;
+    unsigned m_hs, s_hs, m_s, s_s, m_seg, s_seg;     // magic_div by (H + 1) S, by S, by nseg
+};
+
+template <bool F16>
+__global__ __launch_bounds__(256, 2) void wgrad3_hw_kernel(W3WArgs g) {
+    constexpr int RINGP = 256, L = 64;                   // ring slots; lead / lag of the ring around the current k-step
+    constexpr int NSA = 3;
+    constexpr int ASZ = 2 * 2048;
+    constexpr int RB = RINGP * 64;
+    constexpr int R0 = 0;
+    constexpr int A0 = 2 * RB;
+    static_assert(A0 + NSA * ASZ <= 65536 && (RB & (RB - 1)) == 0, "LDS-DMA targets below 64 KiB; power-of-two ring");
+    static_assert(RINGP >= 2 * L + 32 + 3 * 32, "k-step, lead, lag, and the groups in flight");
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[A0 + NSA * ASZ];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    typedef __attribute__((address_space(3))) unsigned char* lptr_t;
+    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(__UINTPTR_TYPE__)(lptr_t)lds);
+    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+    const int S = g.S, HS = (g.H + 1) * S;
+    const int ntn = g.N / 64;
+    const int m0 = (int)(blockIdx.x / ntn) * 64, n0 = (int)(blockIdx.x % ntn) * 64;
+    const int p_begin = blockIdx.y * g.pchunk;
+    const int p_end = min(g.P, p_begin + g.pchunk);
+    const int nk = (p_end - p_begin + 31) / 32;
+    const int mblk = wave >> 1, nblk = wave & 1;
+
+    f32x16 acc[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+
+    // DMA roles as in wgrad3_h_kernel.  Slot p = (pseudo-image q, row hh, slot ww): image q / nseg, segment q % nseg, image row
+    // hh - 1, image column (segment's first) + ww - 1.  dY is live in its own columns 1 <= ww <= Ws only, X also in the two
+    // halo slots where that column exists in the image.
+    const int dblk = wave_s >> 1, dhalf = wave_s & 1;
+    const int lch = 8 * (lane & 3);
+    auto src_of = [&](const h16_t* base, int ld, int ch0, int p, bool live, bool halo) -> const h16_t* {
+        const int q = (int)(__umulhi((unsigned)p, g.m_hs) >> g.s_hs), rem = p - q * HS;          // (p < 0: garbage, not used)
+        const int hh = (int)(__umulhi((unsigned)rem, g.m_s) >> g.s_s), ww = rem - hh * S;
+        const int img = (int)(__umulhi((unsigned)q, g.m_seg) >> g.s_seg), seg = q - img * g.nseg;
+        const int ws = g.seg_base + (seg < g.seg_extra ? 1 : 0);
+        const int col = seg * g.seg_base + min(seg, g.seg_extra) + ww - 1;
+        const bool slot = halo ? ww <= ws + 1 && col >= 0 && col < g.W : ww >= 1 && ww <= ws;
+        const bool real = live && p >= 0 && img < g.images && hh >= 1 && slot;
+        const size_t row = ((size_t)img * g.H + (hh - 1)) * g.W + col;
+        return real ? base + row * ld + ch0 + lch : g.zeros + lch;
+    };
+    auto issue_a = [&](int t) {                           // dY slots [p_begin + 32 t, + 32) -> stage t % NSA
+        const int p = p_begin + 32 * t + 16 * dhalf + (lane >> 2);
+        lds_dma16(src_of(g.A, g.lda, m0 + 32 * dblk, p, p < p_end, false), lds0 + A0 + (t % NSA) * ASZ + dblk * 2048 + dhalf * 1024);
+    };
+    auto issue_x = [&](int u) {                           // ring group u: X slots [p_begin - L + 32 u, + 32)
+        const int p = p_begin - L + 32 * u + 16 * dhalf + (lane >> 2);
+        const unsigned slot0 = (unsigned)(32 * u + 16 * dhalf) & (RINGP - 1);
+        lds_dma16(src_of(g.B, g.ldb, n0 + 32 * dblk, p, true, true), lds0 + R0 + dblk * RB + slot0 * 64);
+    };
+    constexpr int G0 = 2 * L / 32 + 1;                    // groups the first step needs
+    issue_a(0);
+    for (int u = 0; u < G0; ++u) issue_x(u);
+    if (nk > 1) { issue_x(G0); issue_a(1); }
+    const int ll = lane & 15, gq = lane >> 4;
+    const int fpix = 8 * (gq >> 1) + (ll >> 2);
+    const int fch = (16 * (gq & 1) + 4 * (ll & 3)) * 2;
+    for (int t = 0; t < nk; ++t) {
+        // landed: dY(t) and ring groups <= t + G0 - 1; younger than those: dY(t + 1) [1 DMA] and ring group t + G0 [1 DMA]
+        if (t + 1 < nk) wait_vmcnt<2>();
+        else wait_vmcnt<0>();
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        if (t + 1 < nk) issue_x(t + G0 + 1);              // (the ring slot group it overwrites was last read in step t - 1 at the latest)
+        if (t + 2 < nk) issue_a(t + 2);
+        const unsigned char* sa = lds + A0 + (t % NSA) * ASZ + mblk * 2048 + fch;
+        const unsigned xor_ = (unsigned)(nblk * RB + fch);
+        const unsigned xb64 = (unsigned)(32 * t + L + fpix) * 64u;
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            const uint4 af = tr_frag(sa + (kk * 16 + fpix) * 64);
+#pragma unroll
+            for (int tap = 0; tap < 9; ++tap) {
+                const int shift = (tap / 3 - 1) * S + (tap % 3 - 1);
+                typedef __attribute__((address_space(3))) s16x4* lp;
+                const unsigned t0 = xb64 + (unsigned)((kk * 16 + shift) * 64);
+                const unsigned a0 = (t0 & (unsigned)(RB - 64)) | xor_, a1 = ((t0 + 256u) & (unsigned)(RB - 64)) | xor_;
+                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(lds + a0));
+                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(lds + a1));
+                const uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
+                acc[tap] = wmma<F16>(af, make_uint4(l2.x, l2.y, h2.x, h2.y), acc[tap]);
+            }
+        }
+    }
+    float* slab = g.slabs + (size_t)blockIdx.y * g.M * 9 * g.N;
+    const int i = lane & 31, kh = lane >> 5;
+    const int mb = m0 + 32 * mblk, nb = n0 + 32 * nblk;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) slab[(size_t)(mb + mfma32_row(r, kh)) * (9 * g.N) + tap * g.N + nb + i] = acc[tap][r];
+}
+
+// the column segments of a W-pixel row (W >= 63), and the padded slots of the whole problem (0: too many for the magic divisions,
+// which take 31-bit numbers -- the ring reads a little past P)
+struct W3Seg { int nseg, base, extra, S; long P; };
+W3Seg wide_segments(int images, int H, int W) {
+    W3Seg s;
+    s.nseg = (W + 60) / 61;
+    s.base = W / s.nseg; s.extra = W % s.nseg;
+    s.S = s.base + (s.extra ? 1 : 0) + 2;
+    s.P = (long)images * s.nseg * (H + 1) * s.S;
+    if (s.P > 0x7fffffffL / 2) s.P = 0;
+    return s;
+}
+constexpr int W3W_MIN_W = 63, W3W_MAX_W = 512;           // narrower rows belong to peclr_wgrad3_h; the widest row the tests cover
+
 }  // namespace
 }  // namespace peclr
 
@@ -444,6 +578,46 @@ extern "C" int peclr_wgrad3_h(int dtype, int M, int N, int images, int H, int W,
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (dtype == PECLR_DTYPE_F16) hipLaunchKernelGGL((wgrad3_h_kernel<true, 256, false>), grid, dim3(256), 0, s, g);
     else hipLaunchKernelGGL((wgrad3_h_kernel<false, 256, false>), grid, dim3(256), 0, s, g);
+    return launch_status();
+}
+
+// The same for rows of 63 .. 512 pixels (wgrad3_hw_kernel).  Slab policy as above, on the segmented slot count.
+extern "C" int peclr_wgrad3w_h_slabs(int M, int N, int images, int H, int W) {
+    if (M <= 0 || N <= 0 || images <= 0 || H <= 0 || M % 64 || N % 64 || W < W3W_MIN_W || W > W3W_MAX_W) return 0;
+    const long P = wide_segments(images, H, W).P;
+    if (P <= 0) return 0;
+    const long tiles = (long)(M / 64) * (N / 64);
+    long s = (512 + tiles - 1) / tiles;
+    const long max_s = (P + 16 * 32 - 1) / (16 * 32);
+    if (s > max_s) s = max_s;
+    if (s < 1) s = 1;
+    const long pchunk = ((P + s - 1) / s + 31) / 32 * 32;
+    return (int)((P + pchunk - 1) / pchunk);
+}
+
+extern "C" int peclr_wgrad3w_h(int dtype, int M, int N, int images, int H, int W, const void* A, const void* B, float* slabs,
+                               int n_slabs, const void* zeros, peclr_stream_t stream) {
+    if (!A || !B || !slabs || !zeros) return PECLR_ERR_NULL;
+    if (M <= 0 || N <= 0 || images <= 0 || H <= 0 || M % 64 || N % 64 || W < W3W_MIN_W || W > W3W_MAX_W) return PECLR_ERR_SHAPE;
+    const W3Seg sg = wide_segments(images, H, W);
+    if (sg.P <= 0) return PECLR_ERR_SHAPE;
+    if (!aligned16(A) || !aligned16(B) || !aligned16(slabs) || !aligned16(zeros)) return PECLR_ERR_ALIGN;
+    if (n_slabs != peclr_wgrad3w_h_slabs(M, N, images, H, W)) return PECLR_ERR_WORKSPACE;
+    if (dtype != PECLR_DTYPE_BF16 && dtype != PECLR_DTYPE_F16) return PECLR_ERR_UNSUPPORTED;
+    W3WArgs g;
+    g.A = static_cast<const h16_t*>(A); g.B = static_cast<const h16_t*>(B); g.slabs = slabs;
+    g.M = M; g.N = N; g.lda = M; g.ldb = N; g.H = H; g.W = W; g.images = images;
+    g.S = sg.S; g.nseg = sg.nseg; g.seg_base = sg.base; g.seg_extra = sg.extra;
+    g.P = (int)sg.P;
+    g.pchunk = ((g.P + n_slabs - 1) / n_slabs + 31) / 32 * 32;
+    g.zeros = static_cast<const h16_t*>(zeros);
+    magic_div((unsigned)((H + 1) * sg.S), g.m_hs, g.s_hs);
+    magic_div((unsigned)sg.S, g.m_s, g.s_s);
+    magic_div((unsigned)sg.nseg, g.m_seg, g.s_seg);
+    const dim3 grid((M / 64) * (N / 64), n_slabs);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (dtype == PECLR_DTYPE_F16) hipLaunchKernelGGL((wgrad3_hw_kernel<true>), grid, dim3(256), 0, s, g);
+    else hipLaunchKernelGGL((wgrad3_hw_kernel<false>), grid, dim3(256), 0, s, g);
     return launch_status();
 }
 
