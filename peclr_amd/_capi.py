@@ -940,7 +940,7 @@ def wgrad_h(gy: torch.Tensor, x: torch.Tensor, taps: int = 1, stride: int = 1, t
         if wo <= WGRAD3_MAX_W:
             entry, kernel, ns = "peclr_wgrad3_h", "wgrad3_h_kernel", lib().peclr_wgrad3_h_slabs(cout, cin, nb, ho, wo)
         else:
-            entry, kernel, ns = "peclr_wgrad3w_h", "wgrad3_hw_kernel", lib().peclr_wgrad3w_h_slabs(cout, cin, nb, ho, wo)
+            entry, kernel, ns = "peclr_wgrad3w_h", "wgrad3_h_kernel (segments)", lib().peclr_wgrad3w_h_slabs(cout, cin, nb, ho, wo)
         if ns < 1:
             raise PeclrHipError(f"wgrad_h: unsupported 3x3 shape M={cout} N={cin} {nb} x {ho} x {wo}")
         slabs = torch.empty((ns, cout, 9 * cin), device=gy.device, dtype=torch.float32)

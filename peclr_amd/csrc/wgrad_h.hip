@@ -193,6 +193,17 @@ WPlan wgrad_plan(int M, int N) {
     if (forced > 0) p.target = forced;
     return p;
 }
+
+// one MB x NB block tile: format x (stride 2 | two stages | four stages -- of the 4 x 4 tile only: 2 x 8 / 8 x 2 would need 80 KiB)
+template <int MB, int NB>
+void wgrad_h_launch(const WArgs& g, dim3 grid, hipStream_t s, bool f16, bool deep) {
+    void (*k)(WArgs);
+    if (g.stride == 2) k = f16 ? wgrad_h_kernel<true, MB, NB, true> : wgrad_h_kernel<false, MB, NB, true>;
+    else k = f16 ? wgrad_h_kernel<true, MB, NB, false> : wgrad_h_kernel<false, MB, NB, false>;
+    if constexpr (MB == 4 && NB == 4)
+        if (deep) k = f16 ? wgrad_h_kernel<true, 4, 4, false, 4> : wgrad_h_kernel<false, 4, 4, false, 4>;
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, s, g);
+}
 }  // namespace
 
 extern "C" int peclr_wgrad_h_slabs(int M, int N, int K) {
@@ -229,27 +240,9 @@ extern "C" int peclr_wgrad_h(int dtype, int M, int N, int K, const void* A, int 
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool f16 = dtype == PECLR_DTYPE_F16;
     const bool deep = stride == 1 && wgrad_plan(M, N).stages == 4;
-#define PECLR_LAUNCH(MB_, NB_)                                                                                      \
-    do {                                                                                                            \
-        if (f16) { if (stride == 2) hipLaunchKernelGGL((wgrad_h_kernel<true, MB_, NB_, true>), grid, dim3(256), 0, s, g); \
-                   else if (deep) hipLaunchKernelGGL((wgrad_h_kernel<true, MB_, NB_, false, 4>), grid, dim3(256), 0, s, g); \
-                   else hipLaunchKernelGGL((wgrad_h_kernel<true, MB_, NB_, false>), grid, dim3(256), 0, s, g); }     \
-        else { if (stride == 2) hipLaunchKernelGGL((wgrad_h_kernel<false, MB_, NB_, true>), grid, dim3(256), 0, s, g); \
-               else if (deep) hipLaunchKernelGGL((wgrad_h_kernel<false, MB_, NB_, false, 4>), grid, dim3(256), 0, s, g); \
-               else hipLaunchKernelGGL((wgrad_h_kernel<false, MB_, NB_, false>), grid, dim3(256), 0, s, g); }        \
-    } while (0)
-#define PECLR_LAUNCH2(MB_, NB_)                                                                                     \
-    do {                                                                                                            \
-        if (f16) { if (stride == 2) hipLaunchKernelGGL((wgrad_h_kernel<true, MB_, NB_, true>), grid, dim3(256), 0, s, g); \
-                   else hipLaunchKernelGGL((wgrad_h_kernel<true, MB_, NB_, false>), grid, dim3(256), 0, s, g); }     \
-        else { if (stride == 2) hipLaunchKernelGGL((wgrad_h_kernel<false, MB_, NB_, true>), grid, dim3(256), 0, s, g); \
-               else hipLaunchKernelGGL((wgrad_h_kernel<false, MB_, NB_, false>), grid, dim3(256), 0, s, g); }        \
-    } while (0)
-    if (t.mb == 8) PECLR_LAUNCH2(8, 2);
-    else if (t.mb == 2) PECLR_LAUNCH2(2, 8);
-    else PECLR_LAUNCH(4, 4);
-#undef PECLR_LAUNCH
-#undef PECLR_LAUNCH2
+    if (t.mb == 8) wgrad_h_launch<8, 2>(g, grid, s, f16, deep);
+    else if (t.mb == 2) wgrad_h_launch<2, 8>(g, grid, s, f16, deep);
+    else wgrad_h_launch<4, 4>(g, grid, s, f16, deep);
     return launch_status();
 }
 
@@ -264,10 +257,31 @@ extern "C" int peclr_wgrad_h(int dtype, int M, int N, int K, const void* A, int 
 // line): dY as k-step tiles, X into a RING of slots that every k-step advances by 32 -- each X element is fetched once and
 // serves all nine taps through transposing reads (ds_read_b64_tr_b16) at the taps' slot offsets.
 // Workgroup: 64 output x 64 input channels x 9 taps; wave = 32 x 32 x 9 (nine accumulators).
+//
+// The ring has RINGP = 256 slots (a power of two >= 2 * roundup(row pitch + 1, 32) + 96: the k-step's 32 slots, lead and lag of
+// the taps, and the groups in flight): 32 KiB serve W <= 62, i.e. every 3x3 of ResNet at 224 x 224 (W3Args); a 512-slot ring
+// would leave the 64 KiB an LDS-DMA can address.  Rows of 63 pixels and more run over a COLUMN-SEGMENTED padded space instead
+// (W3WArgs): every image is cut into nseg = ceil(W / 61) column segments of near-equal width (seg_base, + 1 for the first
+// seg_extra), and each (image, segment) is a PSEUDO-IMAGE of the padded space: a zero row in front, then H rows of
+// S = (widest segment) + 2 slots -- slot 0 the image column LEFT of the segment, slots 1 .. Ws the segment's own, slot Ws + 1 the
+// column RIGHT of it, the rest (a segment one narrower than the widest) zero.  There the operands differ in what a halo slot
+// holds: dY's are zero (every output pixel is summed in exactly one segment), X's are the neighbouring segment's real pixels,
+// zero only outside the image.  Tap (a, b) of slot p is X's slot p + (a - 1) S + (b - 1) for every p, as above; 35 <= S + 1 <= 64,
+// so lead and lag are 64 slots and the 256-slot ring serves any width (2 - 6 % more slots than the un-segmented space would
+// have: 4.5 % at 112 x 112).
+// Both spaces run through ONE kernel, wgrad3_h_kernel<F16, Args>: ring, stages, waits, fragment reads and slab store are
+// written once, and only the slot -> address map of the DMA lanes (src_of) has an arm per space, chosen by Args::wide.  All
+// four instantiations are, instruction for instruction, what two separate kernels compiled to
+// (profiles/isa_identity_wgrad_h.txt).  What that takes: the row pitch comes from an overload per argument struct
+// (row_pitch), and the lead L is a `const int` whose initialiser is a constant expression in the segmented instantiation, so
+// that the lambdas do not capture it and G0 folds; assigning L from a runtime temporary under `if constexpr` was still correct
+// but cost the segmented kernel three scalar instructions in its prologue and one SGPR.  The field order of each struct is the
+// kernel-argument layout: keep it.
 namespace peclr {
 namespace {
 
 struct W3Args {
+    static constexpr bool wide = false;
     const h16_t* A;                      // dY [images * H * W][lda]
     const h16_t* B;                      // X  [images * H * W][ldb]
     float* slabs;                        // [n_slabs][M][9 * N]
@@ -276,9 +290,23 @@ struct W3Args {
     int P;                               // padded slots: images * (H + 1) * (W + 1)
     int pchunk;                          // padded slots per slab (multiple of 32)
     const h16_t* zeros;
-    int s2;                              // stride 2: H x W are the OUTPUT pixels (dY), X holds 2H x 2W; blockIdx.z = parity plane of X
     unsigned m_hw, s_hw, m_w, s_w;       // p / ((H + 1)(W + 1)) = mulhi(p, m_hw) >> s_hw for 0 <= p < 2^31; likewise / (W + 1)
 };
+struct W3WArgs {
+    static constexpr bool wide = true;
+    const h16_t* A;                      // dY [images * H * W][lda]
+    const h16_t* B;                      // X  [images * H * W][ldb]
+    float* slabs;                        // [n_slabs][M][9 * N]
+    int M, N, lda, ldb;
+    int H, W, images;
+    int S, nseg, seg_base, seg_extra;
+    int P;                               // padded slots: images * nseg * (H + 1) * S
+    int pchunk;                          // padded slots per slab (multiple of 32)
+    const h16_t* zeros;
+    unsigned m_hs, s_hs, m_s, s_s, m_seg, s_seg;     // magic_div by (H + 1) S, by S, by nseg
+};
+__device__ __forceinline__ int row_pitch(const W3Args& g) { return g.W + 1; }     // slots per row of the padded space
+__device__ __forceinline__ int row_pitch(const W3WArgs& g) { return g.S; }
 
 // exact division of a 31-bit number by d >= 2 as a multiply-high and a shift (the loop's two DMA addresses per step took two
 // integer divisions each: ~60 vector instructions next to 18 products)
@@ -289,16 +317,10 @@ inline void magic_div(unsigned d, unsigned& m, unsigned& sh) {
     sh = l - 1;
 }
 
-// RINGP: slots of the X ring (power of two >= 2 * roundup(W + 2, 32) + 96: the k-step's 32 slots, lead and lag of the taps, and
-// the group in flight; 256 slots = 32 KiB serve W <= 62, i.e. every 3x3 of ResNet at 224 x 224 -- a 512-slot ring would leave
-// the 64 KiB an LDS-DMA can address, so wider rows are cut into column segments that fit: wgrad3_hw_kernel below)
-// Stride 2 (g.s2): output pixel (oh, ow) meets input pixel (2 oh + a - 1, 2 ow + b - 1) under tap (a, b).  Split X into its four
-// parity planes X_pq[i][j] = X[2 i + p][2 j + q] (each H x W, like dY): tap row a reads plane p = (a != 1) at row shift -1 (a = 0)
-// or 0, columns alike -- so plane (1, 1) serves the four corner taps, (1, 0) and (0, 1) two taps each, (0, 0) the centre, all with
-// shifts in {-1, 0}: the SAME padded space and ring, the plane picked by the addresses the DMA lanes fetch.  blockIdx.z = 2 p + q;
-// the four workgroups of a (tile, slab) write disjoint tap columns of the slab.
-template <bool F16, int RINGP, bool S2>
-__global__ __launch_bounds__(256, 2) void wgrad3_h_kernel(W3Args g) {
+template <bool F16, typename Args>
+__global__ __launch_bounds__(256, 2) void wgrad3_h_kernel(Args g) {
+    constexpr bool WIDE = Args::wide;
+    constexpr int RINGP = 256;                           // slots of the X ring
     constexpr int NSA = 3;                               // dY stages (two k-steps of run-ahead)
     constexpr int ASZ = 2 * 2048;                        // [2 blocks][32 slots][64 B]
     constexpr int RB = RINGP * 64;                       // ring: [2 blocks][RINGP slots][64 B], FIRST in the LDS: a slot's address is
@@ -310,8 +332,9 @@ __global__ __launch_bounds__(256, 2) void wgrad3_h_kernel(W3Args g) {
     typedef __attribute__((address_space(3))) unsigned char* lptr_t;
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(__UINTPTR_TYPE__)(lptr_t)lds);
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-    const int W1 = g.W + 1, HW1 = (g.H + 1) * W1;
-    const int L = (g.W + 2 + 31) / 32 * 32;              // lead / lag of the ring around the current k-step, in slots
+    const int S = row_pitch(g), HS = (g.H + 1) * S;
+    const int L = WIDE ? 64 : (g.W + 2 + 31) / 32 * 32;  // lead / lag of the ring around the current k-step, in slots (see above)
+    if constexpr (WIDE) static_assert(RINGP >= 2 * 64 + 32 + 3 * 32, "k-step, lead, lag, and the groups in flight");
     const int ntn = g.N / 64;
     const int m0 = (int)(blockIdx.x / ntn) * 64, n0 = (int)(blockIdx.x % ntn) * 64;
     const int p_begin = blockIdx.y * g.pchunk;
@@ -319,34 +342,47 @@ __global__ __launch_bounds__(256, 2) void wgrad3_h_kernel(W3Args g) {
     const int nk = (p_end - p_begin + 31) / 32;
     const int mblk = wave >> 1, nblk = wave & 1;
 
-    constexpr int NT = S2 ? 4 : 9;                        // accumulators: taps of the launch (stride 2: of the largest parity plane)
-    f32x16 acc[NT];
+    f32x16 acc[9];
 #pragma unroll
-    for (int t = 0; t < NT; ++t)
+    for (int t = 0; t < 9; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    const int pp = S2 ? (int)(blockIdx.z >> 1) : 0, pq = S2 ? (int)(blockIdx.z & 1) : 0;     // parity plane of X (stride 2)
 
     // DMA: this wave moves piece (block = wave >> 1, 16-slot half = wave & 1) of every 32-slot group; lane = slot (lane >> 2) of
-    // the half, channels 8 (lane & 3) .. + 7 of the block.  A padded slot p is real pixel (img, hh - 1, ww - 1) iff hh, ww >= 1.
+    // the half, channels 8 (lane & 3) .. + 7 of the block.
     const int dblk = wave_s >> 1, dhalf = wave_s & 1;
     const int lch = 8 * (lane & 3);
-    auto src_of = [&](const h16_t* base, int ld, int ch0, int p, bool live, bool plane = false) -> const h16_t* {
-        const int img = (int)(__umulhi((unsigned)p, g.m_hw) >> g.s_hw), rem = p - img * HW1;     // (p < 0: garbage, not used)
-        const int hh = (int)(__umulhi((unsigned)rem, g.m_w) >> g.s_w), ww = rem - hh * W1;
-        const bool real = live && p >= 0 && img < g.images && hh >= 1 && ww >= 1;
-        const size_t row = plane ? ((size_t)img * 2 * g.H + 2 * (hh - 1) + pp) * (2 * g.W) + 2 * (ww - 1) + pq
-                                 : ((size_t)img * g.H + (hh - 1)) * g.W + (ww - 1);
-        return real ? base + row * ld + ch0 + lch : g.zeros + lch;
+    auto src_of = [&](const h16_t* base, int ld, int ch0, int p, bool live, bool halo) -> const h16_t* {
+        if constexpr (WIDE) {
+            // slot p = (pseudo-image q, row hh, slot ww): image q / nseg, segment q % nseg, image row hh - 1, image column
+            // (segment's first) + ww - 1.  dY is live in its own columns 1 <= ww <= Ws only, X (halo) also in the two halo
+            // slots where that column exists in the image.
+            const int q = (int)(__umulhi((unsigned)p, g.m_hs) >> g.s_hs), rem = p - q * HS;          // (p < 0: garbage, not used)
+            const int hh = (int)(__umulhi((unsigned)rem, g.m_s) >> g.s_s), ww = rem - hh * S;
+            const int img = (int)(__umulhi((unsigned)q, g.m_seg) >> g.s_seg), seg = q - img * g.nseg;
+            const int ws = g.seg_base + (seg < g.seg_extra ? 1 : 0);
+            const int col = seg * g.seg_base + min(seg, g.seg_extra) + ww - 1;
+            const bool slot = halo ? ww <= ws + 1 && col >= 0 && col < g.W : ww >= 1 && ww <= ws;
+            const bool real = live && p >= 0 && img < g.images && hh >= 1 && slot;
+            const size_t row = ((size_t)img * g.H + (hh - 1)) * g.W + col;
+            return real ? base + row * ld + ch0 + lch : g.zeros + lch;
+        } else {
+            // slot p is real pixel (img, hh - 1, ww - 1) iff hh, ww >= 1, for either operand
+            const int img = (int)(__umulhi((unsigned)p, g.m_hw) >> g.s_hw), rem = p - img * HS;      // (p < 0: garbage, not used)
+            const int hh = (int)(__umulhi((unsigned)rem, g.m_w) >> g.s_w), ww = rem - hh * S;
+            const bool real = live && p >= 0 && img < g.images && hh >= 1 && ww >= 1;
+            const size_t row = ((size_t)img * g.H + (hh - 1)) * g.W + (ww - 1);
+            return real ? base + row * ld + ch0 + lch : g.zeros + lch;
+        }
     };
     auto issue_a = [&](int t) {                           // dY slots [p_begin + 32 t, + 32) -> stage t % NSA
         const int p = p_begin + 32 * t + 16 * dhalf + (lane >> 2);
-        lds_dma16(src_of(g.A, g.lda, m0 + 32 * dblk, p, p < p_end), lds0 + A0 + (t % NSA) * ASZ + dblk * 2048 + dhalf * 1024);
+        lds_dma16(src_of(g.A, g.lda, m0 + 32 * dblk, p, p < p_end, false), lds0 + A0 + (t % NSA) * ASZ + dblk * 2048 + dhalf * 1024);
     };
     auto issue_x = [&](int u) {                           // ring group u: X slots [p_begin - L + 32 u, + 32)
         const int p = p_begin - L + 32 * u + 16 * dhalf + (lane >> 2);
         const unsigned slot0 = (unsigned)(32 * u + 16 * dhalf) & (RINGP - 1);
-        lds_dma16(src_of(g.B, g.ldb, n0 + 32 * dblk, p, true, S2), lds0 + R0 + dblk * RB + slot0 * 64);
+        lds_dma16(src_of(g.B, g.ldb, n0 + 32 * dblk, p, true, true), lds0 + R0 + dblk * RB + slot0 * 64);
     };
     // k-step t reads ring groups t .. t + 2 L / 32 (slots [32 t, 32 t + 32 + 2 L) relative to p_begin - L); groups are issued two
     // steps ahead of their first use
@@ -369,138 +405,6 @@ __global__ __launch_bounds__(256, 2) void wgrad3_h_kernel(W3Args g) {
         const unsigned char* sa = lds + A0 + (t % NSA) * ASZ + mblk * 2048 + fch;
         const unsigned xor_ = (unsigned)(nblk * RB + fch);            // (block base + this lane's channel bytes: bits the mask clears)
         const unsigned xb64 = (unsigned)(32 * t + L + fpix) * 64u;    // byte offset (before the wrap) of this lane's first pixel at shift 0
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const uint4 af = tr_frag(sa + (kk * 16 + fpix) * 64);
-#pragma unroll
-            for (int tap = 0; tap < NT; ++tap) {
-                int shift = (tap / 3 - 1) * W1 + (tap % 3 - 1);
-                if constexpr (S2) {                       // accumulator `tap` < 4 = (ia, ib): filter row a = pp ? 2 ia : 1 at shift (pp && !ia ? -1 : 0)
-                    if (tap >= (1 + pp) * (1 + pq)) continue;
-                    const int ia = tap / (1 + pq), ib = tap - ia * (1 + pq);
-                    shift = (pp && ia == 0 ? -W1 : 0) + (pq && ib == 0 ? -1 : 0);
-                }
-                typedef __attribute__((address_space(3))) s16x4* lp;
-                const unsigned t0 = xb64 + (unsigned)((kk * 16 + shift) * 64);
-                const unsigned a0 = (t0 & (unsigned)(RB - 64)) | xor_, a1 = ((t0 + 256u) & (unsigned)(RB - 64)) | xor_;
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(lds + a0));
-                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(lds + a1));
-                const uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-                acc[tap] = wmma<F16>(af, make_uint4(l2.x, l2.y, h2.x, h2.y), acc[tap]);
-            }
-        }
-    }
-    float* slab = g.slabs + (size_t)blockIdx.y * g.M * 9 * g.N;
-    const int i = lane & 31, kh = lane >> 5;
-    const int mb = m0 + 32 * mblk, nb = n0 + 32 * nblk;
-#pragma unroll
-    for (int tap = 0; tap < NT; ++tap) {
-        int ftap = tap;                                   // filter tap this accumulator belongs to
-        if constexpr (S2) {
-            if (tap >= (1 + pp) * (1 + pq)) continue;
-            const int ia = tap / (1 + pq), ib = tap - ia * (1 + pq);
-            ftap = 3 * (pp ? 2 * ia : 1) + (pq ? 2 * ib : 1);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) slab[(size_t)(mb + mfma32_row(r, kh)) * (9 * g.N) + ftap * g.N + nb + i] = acc[tap][r];
-    }
-}
-
-// ---- the same for rows of 63 pixels and more: a COLUMN-SEGMENTED padded space.  Every image is cut into nseg = ceil(W / 61)
-// column segments of near-equal width (seg_base, + 1 for the first seg_extra), and each (image, segment) is a PSEUDO-IMAGE of
-// the padded space: a zero row in front, then H rows of S = (widest segment) + 2 slots -- slot 0 the image column LEFT of the
-// segment, slots 1 .. Ws the segment's own, slot Ws + 1 the column RIGHT of it, the rest (a segment one narrower than the widest)
-// zero.  The operands differ in what a halo slot holds: dY's are zero (every output pixel is summed in exactly one segment), X's
-// are the neighbouring segment's real pixels, zero only outside the image.  Tap (a, b) of slot p is X's slot
-// p + (a - 1) S + (b - 1) for every p, as above; 35 <= S + 1 <= 64, so lead and lag are 64 slots and the 256-slot ring serves any
-// width (2 - 6 % more slots than wgrad3_h_kernel's space would have: 4.5 % at 112 x 112).  Ring, stages, waits, fragment reads and
-// slab store are wgrad3_h_kernel's (a sibling and not a template arm of it: any change to that kernel's text, even wrapping its
-// body in a function, moved its register allocation); only the slot -> address map of the DMA lanes differs.
-struct W3WArgs {
-    const h16_t* A;                      // dY [images * H * W][lda]
-    const h16_t* B;                      // X  [images * H * W][ldb]
-    float* slabs;                        // [n_slabs][M][9 * N]
-    int M, N, lda, ldb;
-    int H, W, images;
-    int S, nseg, seg_base, seg_extra;
-    int P;                               // padded slots: images * nseg * (H + 1) * S
-    int pchunk;                          // padded slots per slab (multiple of 32)
-    const h16_t* zeros;
-    unsigned m_hs, s_hs, m_s, s_s, m_seg, s_seg;     // magic_div by (H + 1) S, by S, by nseg
-};
-
-template <bool F16>
-__global__ __launch_bounds__(256, 2) void wgrad3_hw_kernel(W3WArgs g) {
-    constexpr int RINGP = 256, L = 64;                   // ring slots; lead / lag of the ring around the current k-step
-    constexpr int NSA = 3;
-    constexpr int ASZ = 2 * 2048;
-    constexpr int RB = RINGP * 64;
-    constexpr int R0 = 0;
-    constexpr int A0 = 2 * RB;
-    static_assert(A0 + NSA * ASZ <= 65536 && (RB & (RB - 1)) == 0, "LDS-DMA targets below 64 KiB; power-of-two ring");
-    static_assert(RINGP >= 2 * L + 32 + 3 * 32, "k-step, lead, lag, and the groups in flight");
-    __shared__ __attribute__((aligned(1024))) unsigned char lds[A0 + NSA * ASZ];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    typedef __attribute__((address_space(3))) unsigned char* lptr_t;
-    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(__UINTPTR_TYPE__)(lptr_t)lds);
-    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-    const int S = g.S, HS = (g.H + 1) * S;
-    const int ntn = g.N / 64;
-    const int m0 = (int)(blockIdx.x / ntn) * 64, n0 = (int)(blockIdx.x % ntn) * 64;
-    const int p_begin = blockIdx.y * g.pchunk;
-    const int p_end = min(g.P, p_begin + g.pchunk);
-    const int nk = (p_end - p_begin + 31) / 32;
-    const int mblk = wave >> 1, nblk = wave & 1;
-
-    f32x16 acc[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-
-    // DMA roles as in wgrad3_h_kernel.  Slot p = (pseudo-image q, row hh, slot ww): image q / nseg, segment q % nseg, image row
-    // hh - 1, image column (segment's first) + ww - 1.  dY is live in its own columns 1 <= ww <= Ws only, X also in the two
-    // halo slots where that column exists in the image.
-    const int dblk = wave_s >> 1, dhalf = wave_s & 1;
-    const int lch = 8 * (lane & 3);
-    auto src_of = [&](const h16_t* base, int ld, int ch0, int p, bool live, bool halo) -> const h16_t* {
-        const int q = (int)(__umulhi((unsigned)p, g.m_hs) >> g.s_hs), rem = p - q * HS;          // (p < 0: garbage, not used)
-        const int hh = (int)(__umulhi((unsigned)rem, g.m_s) >> g.s_s), ww = rem - hh * S;
-        const int img = (int)(__umulhi((unsigned)q, g.m_seg) >> g.s_seg), seg = q - img * g.nseg;
-        const int ws = g.seg_base + (seg < g.seg_extra ? 1 : 0);
-        const int col = seg * g.seg_base + min(seg, g.seg_extra) + ww - 1;
-        const bool slot = halo ? ww <= ws + 1 && col >= 0 && col < g.W : ww >= 1 && ww <= ws;
-        const bool real = live && p >= 0 && img < g.images && hh >= 1 && slot;
-        const size_t row = ((size_t)img * g.H + (hh - 1)) * g.W + col;
-        return real ? base + row * ld + ch0 + lch : g.zeros + lch;
-    };
-    auto issue_a = [&](int t) {                           // dY slots [p_begin + 32 t, + 32) -> stage t % NSA
-        const int p = p_begin + 32 * t + 16 * dhalf + (lane >> 2);
-        lds_dma16(src_of(g.A, g.lda, m0 + 32 * dblk, p, p < p_end, false), lds0 + A0 + (t % NSA) * ASZ + dblk * 2048 + dhalf * 1024);
-    };
-    auto issue_x = [&](int u) {                           // ring group u: X slots [p_begin - L + 32 u, + 32)
-        const int p = p_begin - L + 32 * u + 16 * dhalf + (lane >> 2);
-        const unsigned slot0 = (unsigned)(32 * u + 16 * dhalf) & (RINGP - 1);
-        lds_dma16(src_of(g.B, g.ldb, n0 + 32 * dblk, p, true, true), lds0 + R0 + dblk * RB + slot0 * 64);
-    };
-    constexpr int G0 = 2 * L / 32 + 1;                    // groups the first step needs
-    issue_a(0);
-    for (int u = 0; u < G0; ++u) issue_x(u);
-    if (nk > 1) { issue_x(G0); issue_a(1); }
-    const int ll = lane & 15, gq = lane >> 4;
-    const int fpix = 8 * (gq >> 1) + (ll >> 2);
-    const int fch = (16 * (gq & 1) + 4 * (ll & 3)) * 2;
-    for (int t = 0; t < nk; ++t) {
-        // landed: dY(t) and ring groups <= t + G0 - 1; younger than those: dY(t + 1) [1 DMA] and ring group t + G0 [1 DMA]
-        if (t + 1 < nk) wait_vmcnt<2>();
-        else wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (t + 1 < nk) issue_x(t + G0 + 1);              // (the ring slot group it overwrites was last read in step t - 1 at the latest)
-        if (t + 2 < nk) issue_a(t + 2);
-        const unsigned char* sa = lds + A0 + (t % NSA) * ASZ + mblk * 2048 + fch;
-        const unsigned xor_ = (unsigned)(nblk * RB + fch);
-        const unsigned xb64 = (unsigned)(32 * t + L + fpix) * 64u;
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             const uint4 af = tr_frag(sa + (kk * 16 + fpix) * 64);
@@ -540,13 +444,8 @@ W3Seg wide_segments(int images, int H, int W) {
 }
 constexpr int W3W_MIN_W = 63, W3W_MAX_W = 512;           // narrower rows belong to peclr_wgrad3_h; the widest row the tests cover
 
-}  // namespace
-}  // namespace peclr
-
-extern "C" int peclr_wgrad3_h_slabs(int M, int N, int images, int H, int W) {
-    if (M <= 0 || N <= 0 || images <= 0 || H <= 0 || W <= 0 || M % 64 || N % 64 || W > 62) return 0;
-    const long P = (long)images * (H + 1) * (W + 1);
-    const long tiles = (long)(M / 64) * (N / 64);
+// slabs of P padded slots under `tiles` 64 x 64 channel tiles, either space
+int w3_slabs(long P, long tiles) {
     long s = (512 + tiles - 1) / tiles;                  // two workgroups per CU
     const long max_s = (P + 16 * 32 - 1) / (16 * 32);    // at least sixteen k-steps per slab (the ring warm-up is 3 - 9 groups)
     if (s > max_s) s = max_s;
@@ -555,72 +454,77 @@ extern "C" int peclr_wgrad3_h_slabs(int M, int N, int images, int H, int W) {
     return (int)((P + pchunk - 1) / pchunk);
 }
 
+// what both entry points check, in the order that decides a bad call's error code; `shape_ok`: the entry point's own predicate
+int w3_check(const void* A, const void* B, const float* slabs, const void* zeros, bool shape_ok, int n_slabs, int want_slabs,
+             int dtype) {
+    if (!A || !B || !slabs || !zeros) return PECLR_ERR_NULL;
+    if (!shape_ok) return PECLR_ERR_SHAPE;
+    if (!aligned16(A) || !aligned16(B) || !aligned16(slabs) || !aligned16(zeros)) return PECLR_ERR_ALIGN;
+    if (n_slabs != want_slabs) return PECLR_ERR_WORKSPACE;
+    if (dtype != PECLR_DTYPE_BF16 && dtype != PECLR_DTYPE_F16) return PECLR_ERR_UNSUPPORTED;
+    return PECLR_OK;
+}
+
+// the fields both argument structs have (g.P and the address map's own are the caller's), and the launch
+template <typename Args>
+int w3_launch(Args& g, int dtype, int M, int N, int images, int H, int W, const void* A, const void* B, float* slabs, int n_slabs,
+              const void* zeros, peclr_stream_t stream) {
+    g.A = static_cast<const h16_t*>(A); g.B = static_cast<const h16_t*>(B); g.slabs = slabs;
+    g.M = M; g.N = N; g.lda = M; g.ldb = N; g.H = H; g.W = W; g.images = images;
+    g.pchunk = ((g.P + n_slabs - 1) / n_slabs + 31) / 32 * 32;
+    g.zeros = static_cast<const h16_t*>(zeros);
+    const dim3 grid((M / 64) * (N / 64), n_slabs);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (dtype == PECLR_DTYPE_F16) hipLaunchKernelGGL((wgrad3_h_kernel<true, Args>), grid, dim3(256), 0, s, g);
+    else hipLaunchKernelGGL((wgrad3_h_kernel<false, Args>), grid, dim3(256), 0, s, g);
+    return launch_status();
+}
+
+}  // namespace
+}  // namespace peclr
+
+extern "C" int peclr_wgrad3_h_slabs(int M, int N, int images, int H, int W) {
+    if (M <= 0 || N <= 0 || images <= 0 || H <= 0 || W <= 0 || M % 64 || N % 64 || W > 62) return 0;
+    return w3_slabs((long)images * (H + 1) * (W + 1), (long)(M / 64) * (N / 64));
+}
+
 // dW slabs [n_slabs][Cout][9 * Cin] of a 3x3 / padding-1 / stride-1 convolution from 16-bit NHWC activations dY [images, H, W,
 // Cout], X [images, H, W, Cin].
 extern "C" int peclr_wgrad3_h(int dtype, int M, int N, int images, int H, int W, const void* A, const void* B, float* slabs,
                               int n_slabs, const void* zeros, peclr_stream_t stream) {
-    if (!A || !B || !slabs || !zeros) return PECLR_ERR_NULL;
-    if (M <= 0 || N <= 0 || images <= 0 || H <= 0 || W <= 0 || M % 64 || N % 64 || W > 62) return PECLR_ERR_SHAPE;
-    if ((long)images * (H + 1) * (W + 1) > 0x7fffffffL / 2) return PECLR_ERR_SHAPE;
-    if (!aligned16(A) || !aligned16(B) || !aligned16(slabs) || !aligned16(zeros)) return PECLR_ERR_ALIGN;
-    if (n_slabs != peclr_wgrad3_h_slabs(M, N, images, H, W)) return PECLR_ERR_WORKSPACE;
-    if (dtype != PECLR_DTYPE_BF16 && dtype != PECLR_DTYPE_F16) return PECLR_ERR_UNSUPPORTED;
+    const bool shape_ok = !(M <= 0 || N <= 0 || images <= 0 || H <= 0 || W <= 0 || M % 64 || N % 64 || W > 62) &&
+                          !((long)images * (H + 1) * (W + 1) > 0x7fffffffL / 2);
+    if (const int e = w3_check(A, B, slabs, zeros, shape_ok, n_slabs, peclr_wgrad3_h_slabs(M, N, images, H, W), dtype)) return e;
     W3Args g;
-    g.A = static_cast<const h16_t*>(A); g.B = static_cast<const h16_t*>(B); g.slabs = slabs;
-    g.M = M; g.N = N; g.lda = M; g.ldb = N; g.H = H; g.W = W; g.images = images;
     g.P = images * (H + 1) * (W + 1);
-    g.pchunk = ((g.P + n_slabs - 1) / n_slabs + 31) / 32 * 32;
-    g.zeros = static_cast<const h16_t*>(zeros);
     magic_div((unsigned)((H + 1) * (W + 1)), g.m_hw, g.s_hw);
     magic_div((unsigned)(W + 1), g.m_w, g.s_w);
-    g.s2 = 0;
-    const dim3 grid((M / 64) * (N / 64), n_slabs);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == PECLR_DTYPE_F16) hipLaunchKernelGGL((wgrad3_h_kernel<true, 256, false>), grid, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL((wgrad3_h_kernel<false, 256, false>), grid, dim3(256), 0, s, g);
-    return launch_status();
+    return w3_launch(g, dtype, M, N, images, H, W, A, B, slabs, n_slabs, zeros, stream);
 }
 
-// The same for rows of 63 .. 512 pixels (wgrad3_hw_kernel).  Slab policy as above, on the segmented slot count.
+// The same for rows of 63 .. 512 pixels (the column-segmented space).  Slab policy as above, on the segmented slot count.
 extern "C" int peclr_wgrad3w_h_slabs(int M, int N, int images, int H, int W) {
     if (M <= 0 || N <= 0 || images <= 0 || H <= 0 || M % 64 || N % 64 || W < W3W_MIN_W || W > W3W_MAX_W) return 0;
     const long P = wide_segments(images, H, W).P;
     if (P <= 0) return 0;
-    const long tiles = (long)(M / 64) * (N / 64);
-    long s = (512 + tiles - 1) / tiles;
-    const long max_s = (P + 16 * 32 - 1) / (16 * 32);
-    if (s > max_s) s = max_s;
-    if (s < 1) s = 1;
-    const long pchunk = ((P + s - 1) / s + 31) / 32 * 32;
-    return (int)((P + pchunk - 1) / pchunk);
+    return w3_slabs(P, (long)(M / 64) * (N / 64));
 }
 
 extern "C" int peclr_wgrad3w_h(int dtype, int M, int N, int images, int H, int W, const void* A, const void* B, float* slabs,
                                int n_slabs, const void* zeros, peclr_stream_t stream) {
-    if (!A || !B || !slabs || !zeros) return PECLR_ERR_NULL;
-    if (M <= 0 || N <= 0 || images <= 0 || H <= 0 || M % 64 || N % 64 || W < W3W_MIN_W || W > W3W_MAX_W) return PECLR_ERR_SHAPE;
-    const W3Seg sg = wide_segments(images, H, W);
-    if (sg.P <= 0) return PECLR_ERR_SHAPE;
-    if (!aligned16(A) || !aligned16(B) || !aligned16(slabs) || !aligned16(zeros)) return PECLR_ERR_ALIGN;
-    if (n_slabs != peclr_wgrad3w_h_slabs(M, N, images, H, W)) return PECLR_ERR_WORKSPACE;
-    if (dtype != PECLR_DTYPE_BF16 && dtype != PECLR_DTYPE_F16) return PECLR_ERR_UNSUPPORTED;
+    const bool dims_ok = !(M <= 0 || N <= 0 || images <= 0 || H <= 0 || M % 64 || N % 64 || W < W3W_MIN_W || W > W3W_MAX_W);
+    const W3Seg sg = dims_ok ? wide_segments(images, H, W) : W3Seg{};
+    if (const int e = w3_check(A, B, slabs, zeros, dims_ok && !(sg.P <= 0), n_slabs, peclr_wgrad3w_h_slabs(M, N, images, H, W), dtype))
+        return e;
     W3WArgs g;
-    g.A = static_cast<const h16_t*>(A); g.B = static_cast<const h16_t*>(B); g.slabs = slabs;
-    g.M = M; g.N = N; g.lda = M; g.ldb = N; g.H = H; g.W = W; g.images = images;
     g.S = sg.S; g.nseg = sg.nseg; g.seg_base = sg.base; g.seg_extra = sg.extra;
     g.P = (int)sg.P;
-    g.pchunk = ((g.P + n_slabs - 1) / n_slabs + 31) / 32 * 32;
-    g.zeros = static_cast<const h16_t*>(zeros);
     magic_div((unsigned)((H + 1) * sg.S), g.m_hs, g.s_hs);
     magic_div((unsigned)sg.S, g.m_s, g.s_s);
     magic_div((unsigned)sg.nseg, g.m_seg, g.s_seg);
-    const dim3 grid((M / 64) * (N / 64), n_slabs);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == PECLR_DTYPE_F16) hipLaunchKernelGGL((wgrad3_hw_kernel<true>), grid, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL((wgrad3_hw_kernel<false>), grid, dim3(256), 0, s, g);
-    return launch_status();
+    return w3_launch(g, dtype, M, N, images, H, W, A, B, slabs, n_slabs, zeros, stream);
 }
 
-// (The 3x3 / padding-1 / STRIDE-2 weight gradient through the same ring -- four parity planes of X, template argument S2 of
-// wgrad3_h_kernel -- was exported as peclr_wgrad3_s2_h in round 4; correct, but 171 - 196 us against MIOpen's 137 - 150 at
-// ResNet-50's three shapes, so nothing routed to it: un-exported in round 5.  The kernel keeps the template argument.)
+// (A 3x3 / padding-1 / STRIDE-2 arm of wgrad3_h_kernel -- X as four parity planes through the same ring -- was exported as
+// peclr_wgrad3_s2_h in round 4 and un-exported in round 5: correct, but slower than MIOpen at ResNet-50's three shapes.  The arm
+// is gone; its derivation and measurement are in DESIGN.md, "`wgrad3_h` after the same look at its loop".)

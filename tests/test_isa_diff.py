@@ -77,6 +77,46 @@ def test_one_changed_resource_number_is_found():
     assert not same and verdict.startswith("identical") and rows[0].lstrip().startswith("!=") and "152|153" in rows[0]
 
 
+# a kernel renamed on purpose (two kernels folded into one template): the names differ after demangling too, so it takes --pair
+FOLDED_SYM = "_ZN5peclr12_GLOBAL__N_12k2INS_4BF16ENS0_5ArgsWEEEvi"
+FOLDED = dict(DEMANGLED, **{FOLDED_SYM: "void peclr::(anonymous namespace)::k2<peclr::BF16, peclr::(anonymous namespace)::ArgsW>(int)"})
+PAIR = [("void k<BF16>(int)", "k2<BF16, ArgsW>")]                       # (NEW as an unambiguous part of the name)
+
+
+def demangle_folded(symbols):
+    return {s: FOLDED[s] for s in symbols}
+
+
+def test_pair_compares_a_renamed_kernel_with_its_counterpart():
+    new = snippet(FOLDED_SYM, 5, "0123456789abcdef", "folded")
+    verdict, rows, same = isa_diff.compare(OLD, new, demangle_folded)
+    assert not same and verdict.startswith("DIFFERENT function lists")   # unpaired: one-sided on both sides
+    verdict, rows, same = isa_diff.compare(OLD, new, demangle_folded, pairs=PAIR)
+    assert same and verdict.startswith("identical (1 functions, 1 kernels)")
+    assert rows[0] == "  paired: a's void k<BF16>(int) = b's void k2<BF16, ArgsW>(int)"
+    assert len(rows) == 2 and "152|152" in rows[1] and rows[1].endswith("void k2<BF16, ArgsW>(int)")
+
+
+def test_pair_still_finds_a_changed_instruction_and_a_changed_resource():
+    verdict, rows, same = isa_diff.compare(OLD, snippet(FOLDED_SYM, 5, "0", "x", last="s_nop 0"), demangle_folded, pairs=PAIR)
+    assert not same and verdict.startswith("DIFFERENT: void k2<BF16, ArgsW>(int)")
+    assert "a: s_endpgm" in verdict and "b: s_nop 0" in verdict
+    verdict, rows, same = isa_diff.compare(OLD, snippet(FOLDED_SYM, 5, "0", "x", vgpr=153), demangle_folded, pairs=PAIR)
+    assert not same and verdict.startswith("identical") and rows[1].lstrip().startswith("!=") and "152|153" in rows[1]
+
+
+def test_unmatched_pair_is_an_error():
+    import pytest
+    new = snippet(FOLDED_SYM, 5, "0", "x")
+    for pairs in ([("void nothing<BF16>(int)", "k2<BF16, ArgsW>")],      # a has no such function
+                  [("void k<BF16>(int)", "k3")],                          # b has none
+                  PAIR + [("k7", "k8")]):                                 # neither side has
+        with pytest.raises(ValueError, match="--pair"):
+            isa_diff.compare(OLD, new, demangle_folded, pairs=pairs)
+    seen = set()                                                          # (one file of several: left to the caller, who collects)
+    assert isa_diff.compare(OLD, new, demangle_folded, pairs=PAIR + [("k7", "k8")], applied=seen)[2] and seen == set(PAIR)
+
+
 def test_missing_kernel_is_found():
     other = dict(DEMANGLED)
     other[NEW_SYM] = "void peclr::(anonymous namespace)::k<peclr::F16>(int)"

@@ -1,4 +1,4 @@
-"""peclr_wgrad3w_h (csrc/wgrad_h.hip, wgrad3_hw_kernel): the 16-bit 3x3 / padding-1 / stride-1 weight gradient for rows wider
+"""peclr_wgrad3w_h (csrc/wgrad_h.hip, wgrad3_h_kernel<F16, W3WArgs>): the 16-bit 3x3 / padding-1 / stride-1 weight gradient for rows wider
 than 62 pixels -- every image cut into column segments, each a pseudo-image of the padded pixel space whose halo slots hold
 zero for dY and the neighbouring segment's pixels for X -- against float64 on the SAME 16-bit inputs (`-m gpu`).  The bar is
 test_wgrad3_h_matches_float64's (tests/test_conv_h_gpu.py): fp32 accumulation of exact 16-bit products,
@@ -152,7 +152,7 @@ def test_wide_weight_gradient_in_a_graph(capi, dtype, shape):
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_layer1_bottleneck_takes_the_wide_kernel(dtype):
     """One layer1 bottleneck on the fused path under autocast, 2 x 256 x 64 x 64: with ROUTING.wgrad16_wide conv2's weight
-    gradient is ONE conv3x3_wgrad launch of wgrad3_hw_kernel, agrees with the MIOpen route (the field off) within the 8 ULP the
+    gradient is ONE conv3x3_wgrad launch on wgrad3_h_kernel's segmented route, agrees with the MIOpen route (the field off) within the 8 ULP the
     block tests of tests/test_conv_h_gpu.py allow a 16-bit weight gradient, and is bit-identical from run to run."""
     from peclr_amd import _capi
     from peclr_amd import bn2d as B
@@ -184,7 +184,7 @@ def test_layer1_bottleneck_takes_the_wide_kernel(dtype):
         return net.conv2.weight.grad.detach().clone(), kernels
 
     wide, kernels = run(True)
-    assert kernels == ["wgrad3_hw_kernel"], kernels
+    assert kernels == ["wgrad3_h_kernel (segments)"], kernels
     again, _ = run(True)
     assert torch.equal(wide, again)
     stock, kernels = run(False)

@@ -35,7 +35,7 @@ EXPECT = {
     # (convolution tags: the fp32 six-product kernels, or -- 16-bit runs -- conv_h / wgrad_h kernels)
     "conv1x1_dgrad_add": ("gemm_", "conv_h_kernel"), "conv1x1_dgrad_add_x6": "gemm_x6", "conv1x1_fwd": ("gemm_x6", "conv_h_kernel"),
     "conv1x1_dgrad": ("gemm_x6", "conv_h_kernel"), "conv1x1_wgrad": ("gemm_x6", "wgrad_h_kernel"), "conv3x3_fwd": ("gemm_x6p", "conv_h_kernel"),
-    "conv3x3_dgrad": ("gemm_x6p", "conv_h_kernel"), "conv3x3_wgrad": ("gemm_x6w", "wgrad3_h_kernel", "wgrad3_hw_kernel", "wgrad_x6r_kernel"), "gemm_x6p": "gemm_x6p",
+    "conv3x3_dgrad": ("gemm_x6p", "conv_h_kernel"), "conv3x3_wgrad": ("gemm_x6w", "wgrad3_h_kernel", "wgrad_x6r_kernel"), "gemm_x6p": "gemm_x6p",
     "gemm_x6t": "gemm_x6t", "conv3x3_x6p": "gemm_x6p", "conv_s2_fwd": ("gemm_x6p", "conv_h_kernel"), "conv_s2_dgrad": ("gemm_x6p", "conv_h_kernel"),
     "conv3x3_s2_dgrad": ("gemm_x6p", "conv_h_kernel"), "conv_s2_x6p": "gemm_x6p", "wgrad_slab_reduce": "slab_reduce", "x6_pack": ("x6_pack_kernel", "x6_pair_kernel"),
     "x6_absmax": ("x6_absmax_kernel", "x6_pair_kernel<false>"),

@@ -1,5 +1,5 @@
 """Time of the 16-bit 3x3 / stride-1 weight gradient of rows wider than 62 pixels, the two routes `bn2d._wgrad_h` chooses between
-with `ROUTING.wgrad16_wide`: in-tree (`_capi.wgrad_h`: wgrad3_hw_kernel + the fixed-order slab reduction, fp32 out) against
+with `ROUTING.wgrad16_wide`: in-tree (`_capi.wgrad_h`: wgrad3_h_kernel over column segments + the fixed-order slab reduction, fp32 out) against
 MIOpen (`bn2d._conv_wgrad`: the 16-bit weight gradient + its cast to fp32), same process, same operands.  Warm; a window is ITERS
 back-to-back calls between two device events; the two routes alternate window by window, one window of each is thrown away;
 median, minimum and maximum over the windows.  The field defaults on only if the in-tree median is not above MIOpen's at every
@@ -59,7 +59,7 @@ def main(argv=None):
             gy = torch.randn(nb, cout, h, w, device="cuda", generator=g).to(dtype).contiguous(memory_format=torch.channels_last)
             weight = torch.zeros(cout, cin, 3, 3, device="cuda").contiguous(memory_format=torch.channels_last)
             assert _capi.wgrad_h_ok(gy, x, 9, 1) and w > _capi.WGRAD3_MAX_W, shape
-            fns = {"in-tree (wgrad3_hw_kernel + slab reduce)": lambda: _capi.wgrad_h(gy, x, 9, 1),
+            fns = {"in-tree (wgrad3_h_kernel, segments + slab reduce)": lambda: _capi.wgrad_h(gy, x, 9, 1),
                    "MIOpen (16-bit weight gradient + cast to fp32)": lambda: B._conv_wgrad(gy, x, weight, (1, 1), (1, 1), weight)}
             ours, theirs = (fn() for fn in fns.values())
             ours = ours.view(cout, 3, 3, cin).permute(0, 3, 1, 2)
