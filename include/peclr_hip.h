@@ -707,6 +707,13 @@ int peclr_wgrad3_h(int dtype, int M, int N, int images, int H, int W, const void
 int peclr_wgrad3w_h_slabs(int M, int N, int images, int H, int W);
 int peclr_wgrad3w_h(int dtype, int M, int N, int images, int H, int W, const void* A, const void* B, float* slabs, int n_slabs,
                     const void* zeros, peclr_stream_t stream);
+/* ... and of the 16-bit 3x3 / padding-1 / STRIDE-2 convolutions: dY [images, Ho, Wo, M = Cout], X [images, 2 Ho, 2 Wo, N = Cin]
+ * (the OUTPUT size is passed).  X goes through LDS as its four parity planes, each in the padded space of dY's geometry, where
+ * every tap is a uniform non-positive shift of one plane; one workgroup owns all nine taps of a 64 x 32 channel tile.
+ * M, N multiples of 64, 1 <= Wo <= 62; same slab layout, error codes and fixed-order reduction as peclr_wgrad3_h. */
+int peclr_wgrad3s2_h_slabs(int M, int N, int images, int Ho, int Wo);          /* 0: shape refused */
+int peclr_wgrad3s2_h(int dtype, int M, int N, int images, int Ho, int Wo, const void* dY, const void* X, float* slabs, int n_slabs,
+                     const void* zeros, peclr_stream_t stream);
 int peclr_wgrad_h_slabs(int M, int N, int K);
 int peclr_wgrad_h(int dtype, int M, int N, int K, const void* A, int lda, const void* B, int ldb, float* slabs, int n_slabs,
                   int stride, int Ho, int Wo, const void* zeros, peclr_stream_t stream);

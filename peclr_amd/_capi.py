@@ -116,6 +116,8 @@ SIGNATURES = {
     "peclr_wgrad3_h": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P]),
     "peclr_wgrad3w_h_slabs": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "peclr_wgrad3w_h": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P]),
+    "peclr_wgrad3s2_h_slabs": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "peclr_wgrad3s2_h": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P]),
     "peclr_wgrad_h_slabs": (c_int, [c_int, c_int, c_int]),
     "peclr_wgrad_h": (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "peclr_lars_sumsq_f32": (c_int, [_P, _P, c_int, _P, _P, c_int, _P, _P]),
@@ -955,6 +957,42 @@ def wgrad_h(gy: torch.Tensor, x: torch.Tensor, taps: int = 1, stride: int = 1, t
         _launch(tag, "peclr_wgrad_h", io, cout, cin, k, gp, cout, xp, cin, slabs.data_ptr(), ns, stride, ho, wo,
                 _hzeros(gy.device, gy.dtype).data_ptr(), _stream(),
                 nbytes=2 * k * (cout + cin) + 4 * ns * cout * cin, flops=2 * cout * cin * k, kernel="wgrad_h_kernel")
+    return _sum_slabs(slabs, "wgrad_slab_reduce")
+
+
+WGRAD3_S2_MAX_WO = 62                      # widest OUTPUT row of peclr_wgrad3s2_h (the lead of its 192-slot rings)
+
+
+def wgrad3_s2_h_ok(gy: torch.Tensor, x: torch.Tensor) -> bool:
+    """Does peclr_wgrad3s2_h take this 3x3 / padding-1 / stride-2 weight gradient?  (16-bit channels_last operands of one format,
+    channel counts multiples of 64, even input sizes, output rows of up to 62 pixels -- and at least 512 output pixels, the
+    minimum of the stride-1 3x3 route: not a tuning knob, nothing widens it.)"""
+    if gy.dim() != 4 or x.dim() != 4:
+        return False
+    nb, cout, ho, wo = gy.shape
+    return (gy.dtype in _HALF_IO and x.dtype == gy.dtype and x.shape[0] == nb and cout % 64 == 0 and x.shape[1] % 64 == 0
+            and cout > 0 and x.shape[1] > 0 and ho >= 1 and 1 <= wo <= WGRAD3_S2_MAX_WO and x.shape[2] == 2 * ho and x.shape[3] == 2 * wo
+            and nb * ho * wo >= 512 and nb * (ho + 1) * (wo + 1) <= 0x7FFFFFFF // 2
+            and gy.is_contiguous(memory_format=torch.channels_last) and x.is_contiguous(memory_format=torch.channels_last))
+
+
+def wgrad3_s2_h(gy: torch.Tensor, x: torch.Tensor, tag: str = "conv3x3_wgrad") -> torch.Tensor:
+    """dW [Cout, 9 * Cin] (fp32) of a 3x3 / padding-1 / stride-2 convolution from 16-bit NHWC activations gy [N, Cout, Ho, Wo],
+    x [N, Cin, 2 Ho, 2 Wo] (peclr_wgrad3s2_h: the four parity planes of x through LDS rings, all nine taps in one workgroup +
+    peclr_slab_reduce_f32: fixed-order split-K, deterministic)."""
+    if not wgrad3_s2_h_ok(gy, x):
+        raise PeclrHipError(f"wgrad3_s2_h: unsupported problem gy {gy.dtype} {tuple(gy.shape)} x {x.dtype} {tuple(x.shape)}")
+    io = _half_io(gy, "wgrad3_s2_h gy")
+    nb, cout, ho, wo = gy.shape
+    cin = x.shape[1]
+    gp, xp = _nhwc_ptr(gy, "wgrad3_s2_h gy", gy.dtype), _nhwc_ptr(x, "wgrad3_s2_h x", gy.dtype)
+    ns = lib().peclr_wgrad3s2_h_slabs(cout, cin, nb, ho, wo)
+    if ns < 1:
+        raise PeclrHipError(f"wgrad3_s2_h: unsupported shape M={cout} N={cin} {nb} x {ho} x {wo}")
+    k = nb * ho * wo
+    slabs = torch.empty((ns, cout, 9 * cin), device=gy.device, dtype=torch.float32)
+    _launch(tag, "peclr_wgrad3s2_h", io, cout, cin, nb, ho, wo, gp, xp, slabs.data_ptr(), ns, _hzeros(gy.device, gy.dtype).data_ptr(),
+            _stream(), nbytes=2 * k * (cout + 4 * cin) + 4 * ns * cout * 9 * cin, flops=18 * cout * cin * k, kernel="wgrad3_h_s2_kernel")
     return _sum_slabs(slabs, "wgrad_slab_reduce")
 
 

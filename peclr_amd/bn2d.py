@@ -152,6 +152,11 @@ class Routing:
     # ... the 3x3 ones of rows wider than 62 pixels too (inputs above 248 px: peclr_wgrad3w_h, column segments; off: MIOpen there.
     # On: 0.39 - 0.58 of MIOpen's time at layer1 of 448 and 256 px inputs, bf16 and fp16: profiles/wgrad3_wide_timing.txt)
     wgrad16_wide: bool = dataclasses.field(default_factory=lambda: _env_flag("PECLR_WGRAD16_WIDE"))
+    # ... the 3x3 / stride-2 ones that open layers 2 - 4 too (peclr_wgrad3s2_h, parity planes; off: MIOpen's atomic split-K there).
+    # Opt-in: over C2's three shapes 352 against MIOpen's 397 us in bf16 but 360 against 345 in fp16, and the default's rule asks for both
+    # formats (profiles/wgrad3_s2_timing.txt; the bf16 step is 0.07 ms faster with it: profiles/wgrad3_s2_step_ab.txt).  What it buys
+    # besides: a 16-bit step without atomics (bit-reproducible), without an aten convolution and without a find-db entry
+    wgrad16_s2: bool = dataclasses.field(default_factory=lambda: _env_flag("PECLR_WGRAD16_S2", "0"))
     stem_wgrad: bool = dataclasses.field(default_factory=lambda: _env_flag("PECLR_STEM_WGRAD"))        # ... and its weight gradient
     stem: bool = dataclasses.field(default_factory=lambda: _env_flag("PECLR_STEM"))                    # the 7x7 / stride-2 stem forward in-tree (csrc/stem.hip)
     # 16-bit prediction: the eval-mode BatchNorm layers of the bottleneck blocks folded into the 16-bit convolutions' epilogues
@@ -1132,6 +1137,10 @@ def _wgrad_h(gy: Tensor, x: Tensor, conv, stride: int):
     if (ROUTING.wgrad16 and (ROUTING.wgrad16_wide or not wide) and w.is_contiguous(memory_format=torch.channels_last)
             and _capi.wgrad_h_ok(gy, x, taps, stride)):
         return _on_side_stream(w, (gy, x), lambda: _like_param(_capi.wgrad_h(gy, x, taps, stride), w, taps))     # [Cout, taps * Cin] fp32
+    # the 3x3 / stride-2 ones that open layers 2 - 4 (peclr_wgrad3s2_h; `force` does not widen the predicate)
+    if (ROUTING.wgrad16 and ROUTING.wgrad16_s2 and taps == 9 and w.shape[2] == 3 and stride == 2 and tuple(conv.padding) == (1, 1)
+            and w.is_contiguous(memory_format=torch.channels_last) and _capi.wgrad3_s2_h_ok(gy, x)):
+        return _on_side_stream(w, (gy, x), lambda: _like_param(_capi.wgrad3_s2_h(gy, x), w, taps))
     return _conv_wgrad(gy, x, w, conv.stride, conv.padding, w)
 
 

@@ -525,6 +525,227 @@ extern "C" int peclr_wgrad3w_h(int dtype, int M, int N, int images, int H, int W
     return w3_launch(g, dtype, M, N, images, H, W, A, B, slabs, n_slabs, zeros, stream);
 }
 
-// (A 3x3 / padding-1 / STRIDE-2 arm of wgrad3_h_kernel -- X as four parity planes through the same ring -- was exported as
-// peclr_wgrad3_s2_h in round 4 and un-exported in round 5: correct, but slower than MIOpen at ResNet-50's three shapes.  The arm
-// is gone; its derivation and measurement are in DESIGN.md, "`wgrad3_h` after the same look at its loop".)
+// ---- 3x3 / padding-1 / STRIDE-2 weight gradient, 16-bit:  dW[co][a][b][ci] = sum over output pixels (img, oh, ow) of
+// dY[img, oh, ow, co] * X[img, 2 oh + a - 1, 2 ow + b - 1, ci], X of 2 Ho x 2 Wo pixels.
+//
+// X is seen as four PARITY PLANES (row parity pr, column parity pc), each an Ho x Wo image: plane pixel (i, j) is X pixel
+// (2 i + pr, 2 j + pc).  Tap row a = 0 meets the odd rows at plane row oh - 1, a = 1 the even rows at oh, a = 2 the odd rows at oh;
+// columns alike.  With every plane in the padded space of wgrad3_h_kernel at dY's geometry -- (Ho + 1) x (Wo + 1) slots per
+// image, zero row and zero column in front -- tap (a, b) of dY's slot p is slot p - (a == 0)(Wo + 1) - (b == 0) of plane
+// (a != 1, b != 1), for every p: (even, even) serves one tap, (even, odd) and (odd, even) two each, (odd, odd) four.  No shift is
+// positive (H = 2 Ho, W = 2 Wo: the bottom and right padding is never met), so a ring needs a lead L = roundup(Wo + 2, 32) and no
+// lag: the k-step's 32 slots + L <= 64 + the three groups in flight = 192 slots.
+// Workgroup: 64 output x 32 input channels x 9 taps, one ring of 192 slots x 64 B per plane (4 x 12 KiB, all filled by
+// LDS-DMA, with the four dY stages 64 KiB: what an LDS-DMA can address; two workgroups per CU; three k-steps of run-ahead).  The ring is not a
+// power of two: a slot's wrap is one subtract and one unsigned minimum where wgrad3_h_kernel has an AND and an OR.
+// Every k-step's dY tile is staged once and feeds all nine taps.  Wave = (32 output channels, 16-slot half of the k-step) x 32
+// input channels x 9 taps: nine accumulators and nine products per wave and step, all four waves the same work whatever the
+// 4 / 2 / 2 / 1 split of the planes; the two halves of the contraction meet once, behind the loop, through the LDS that the rings
+// leave (a + b in fp32: one order), and each wave of a pair stores half the taps.
+namespace peclr {
+namespace {
+
+struct W3S2Args {
+    const h16_t* A;                      // dY [images * Ho * Wo][lda]
+    const h16_t* B;                      // X  [images * 2 Ho * 2 Wo][ldb]
+    float* slabs;                        // [n_slabs][M][9 * N]
+    int M, N, lda, ldb;
+    int Ho, Wo, images;
+    int P;                               // padded slots: images * (Ho + 1) * (Wo + 1)
+    int pchunk;                          // padded slots per slab (multiple of 32)
+    const h16_t* zeros;
+    unsigned m_hw, s_hw, m_w, s_w;       // magic_div by (Ho + 1)(Wo + 1), by (Wo + 1)
+    int rows, gsplit;                    // XCD rows: (slab, one of gsplit groups of input-channel tiles); see s2_rows
+};
+
+template <bool F16>
+__global__ __launch_bounds__(256, 2) void wgrad3_h_s2_kernel(W3S2Args g) {
+    constexpr int RINGP = 192;                           // slots of each plane's ring: six 32-slot groups
+    constexpr int NG = RINGP / 32;
+    constexpr int AHEAD = 3;                             // k-steps of run-ahead of the DMAs
+    constexpr int NSA = AHEAD + 1;                       // dY stages
+    constexpr int ASZ = 2 * 2048;                        // [2 blocks][32 slots][64 B]
+    constexpr int RB = RINGP * 64;                       // one plane's ring: [RINGP slots][64 B] (one 32-channel block)
+    constexpr int A0 = 4 * RB;                           // dY stages behind the four rings
+    static_assert(A0 + NSA * ASZ <= 65536, "LDS-DMA targets below 64 KiB");
+    static_assert(RINGP >= 32 + 64 + AHEAD * 32, "k-step, lead, and the groups in flight");
+    static_assert(2 * 5 * 4096 <= A0 && 2 * 4 * 4096 <= A0, "the exchange of the two k-halves fits the rings");
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[A0 + NSA * ASZ];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    typedef __attribute__((address_space(3))) unsigned char* lptr_t;
+    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(__UINTPTR_TYPE__)(lptr_t)lds);
+    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+    const int S = g.Wo + 1, HS = (g.Ho + 1) * S;
+    const int L = (g.Wo + 2 + 31) / 32 * 32;             // lead of the rings in front of the current k-step, in slots: 32 or 64
+    // the workgroups of one row -- every 64-channel tile of dY against one group of 32-channel tiles of X, same slab -- run on
+    // ONE XCD, side by side: what they share (each dY tile npg times, each X tile M / 64 times) comes from that XCD's L2
+    const int npg = g.N / 32 / g.gsplit;                 // input-channel tiles per group
+    const XcdTile xt = xcd_tile(blockIdx.x, (g.M / 64) * npg);
+    if (xt.row_block >= g.rows) return;
+    const int slab_i = xt.row_block / g.gsplit;
+    const int m0 = (xt.col_tile / npg) * 64, n0 = ((xt.row_block % g.gsplit) * npg + xt.col_tile % npg) * 32;
+    const int p_begin = slab_i * g.pchunk;
+    const int p_end = min(g.P, p_begin + g.pchunk);
+    const int nk = (p_end - p_begin + 31) / 32;
+    const int mblk = wave_s >> 1, khalf = wave_s & 1;
+
+    f32x16 acc[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+
+    // DMA: of every 32-slot group this wave moves dY's piece (block = wave >> 1, 16-slot half = wave & 1) and the same half of the
+    // planes (wave >> 1) and (wave >> 1) + 2; lane = slot (lane >> 2) of the half, channels 8 (lane & 3) .. + 7 of the block.
+    const int dblk = wave_s >> 1, dhalf = wave_s & 1;
+    const int lch = 8 * (lane & 3);
+    // slot p = (img, hh, ww) is output pixel / plane pixel (img, hh - 1, ww - 1) iff hh, ww >= 1
+    auto src_of = [&](const h16_t* base, int ld, int ch0, int p, bool live, int plane) -> const h16_t* {
+        const int img = (int)(__umulhi((unsigned)p, g.m_hw) >> g.s_hw), rem = p - img * HS;          // (p < 0: garbage, not used)
+        const int hh = (int)(__umulhi((unsigned)rem, g.m_w) >> g.s_w), ww = rem - hh * S;
+        const bool real = live && p >= 0 && img < g.images && hh >= 1 && ww >= 1;
+        size_t row;
+        if (plane < 0) row = ((size_t)img * g.Ho + (hh - 1)) * g.Wo + (ww - 1);                      // dY
+        else row = ((size_t)img * 2 * g.Ho + 2 * (hh - 1) + (plane >> 1)) * (2 * g.Wo) + 2 * (ww - 1) + (plane & 1);
+        return real ? base + row * ld + ch0 + lch : g.zeros + lch;
+    };
+    auto issue_a = [&](int t) {                           // dY slots [p_begin + 32 t, + 32) -> stage t % NSA
+        const int p = p_begin + 32 * t + 16 * dhalf + (lane >> 2);
+        lds_dma16(src_of(g.A, g.lda, m0 + 32 * dblk, p, p < p_end, -1), lds0 + A0 + (t % NSA) * ASZ + dblk * 2048 + dhalf * 1024);
+    };
+    auto issue_x = [&](int u) {                           // ring group u of this wave's two planes: X slots [p_begin - L + 32 u, + 32)
+        const int p = p_begin - L + 32 * u + 16 * dhalf + (lane >> 2);
+        const unsigned slot0 = (unsigned)(32 * (u % NG) + 16 * dhalf);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int plane = dblk + 2 * j;
+            lds_dma16(src_of(g.B, g.ldb, n0, p, true, plane), lds0 + plane * RB + slot0 * 64);
+        }
+    };
+    // k-step t reads ring groups t .. t + L / 32 (slots [32 t, 32 t + 32 + L) relative to p_begin - L).  What step s adds to step
+    // s - 1's needs -- ring group G0 + s - 1 [2 DMAs], then dY(s) [1 DMA] -- is issued AHEAD steps before it
+    const int G0 = L / 32 + 1;                            // groups the first step needs: 2 or 3
+    issue_a(0);
+    for (int u = 0; u < G0; ++u) issue_x(u);
+    for (int s = 1; s < AHEAD; ++s)
+        if (s < nk) { issue_x(G0 + s - 1); issue_a(s); }
+    const int ll = lane & 15, gq = lane >> 4;
+    const int fpix = 8 * (gq >> 1) + (ll >> 2);           // slot of this source lane inside a 16-slot k-extent (+ 4 for the second read)
+    const int fch = (16 * (gq & 1) + 4 * (ll & 3)) * 2;
+    for (int t = 0; t < nk; ++t) {
+        // landed: dY(t) and ring groups <= t + G0 - 1; younger than those: what the steps t + 1 .. t + AHEAD - 1 that exist add
+        static_assert(AHEAD == 3, "the waits below");
+        if (t + 2 < nk) wait_vmcnt<6>();
+        else if (t + 1 < nk) wait_vmcnt<3>();
+        else wait_vmcnt<0>();
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        // (the ring group it overwrites, t + G0 + AHEAD - 1 - NG <= t - 1, was last read in step t - 1, the dY stage too)
+        if (t + AHEAD < nk) { issue_x(t + G0 + AHEAD - 1); issue_a(t + AHEAD); }
+        const uint4 af = tr_frag(lds + A0 + (t % NSA) * ASZ + mblk * 2048 + fch + (khalf * 16 + fpix) * 64);
+        // this lane's first pixel at shift -L, before the wrap: < 160 + 64 + 32 + 4, i.e. below 2 RINGP
+        const unsigned x0 = (unsigned)(32 * (t % NG) + khalf * 16 + fpix);
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int plane = (tap / 3 != 1 ? 2 : 0) + (tap % 3 != 1 ? 1 : 0);
+            const int shift = L - (tap / 3 == 0 ? S : 0) - (tap % 3 == 0 ? 1 : 0);       // >= 0: S + 1 <= L
+            typedef __attribute__((address_space(3))) s16x4* lp;
+            const unsigned c0 = x0 + (unsigned)shift, c1 = c0 + 4u;
+            const unsigned w0 = min(c0, c0 - (unsigned)RINGP), w1 = min(c1, c1 - (unsigned)RINGP);
+            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(lds + plane * RB + fch + w0 * 64u));
+            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(lds + plane * RB + fch + w1 * 64u));
+            const uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
+            acc[tap] = wmma<F16>(af, make_uint4(l2.x, l2.y, h2.x, h2.y), acc[tap]);
+        }
+    }
+    // the two k-halves of a 32-channel block of dY meet: the odd wave hands taps 0 .. 4 to the even one, then the even wave
+    // taps 5 .. 8 to the odd one ([wave pair][tap][register][lane] floats where the rings were)
+    float* xch = reinterpret_cast<float*>(lds) + mblk * (5 * 1024) + lane;
+    __syncthreads();                                     // (every wave has read its last fragments)
+    if (khalf) {
+#pragma unroll
+        for (int tap = 0; tap < 5; ++tap)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) xch[tap * 1024 + r * 64] = acc[tap][r];
+    }
+    __syncthreads();
+    if (!khalf) {
+#pragma unroll
+        for (int tap = 0; tap < 5; ++tap)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[tap][r] += xch[tap * 1024 + r * 64];
+    }
+    __syncthreads();
+    if (!khalf) {
+#pragma unroll
+        for (int tap = 5; tap < 9; ++tap)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) xch[(tap - 5) * 1024 + r * 64] = acc[tap][r];
+    }
+    __syncthreads();
+    if (khalf) {
+#pragma unroll
+        for (int tap = 5; tap < 9; ++tap)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[tap][r] += xch[(tap - 5) * 1024 + r * 64];
+    }
+    float* slab = g.slabs + (size_t)slab_i * g.M * 9 * g.N;
+    const int i = lane & 31, kh = lane >> 5;
+    const int mb = m0 + 32 * mblk;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap)
+        if ((tap >= 5) == (khalf != 0)) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) slab[(size_t)(mb + mfma32_row(r, kh)) * (9 * g.N) + tap * g.N + n0 + i] = acc[tap][r];
+        }
+}
+
+constexpr int W3S2_MAX_WO = 62;                          // Wo + 2 <= 64: the lead the 192-slot rings have room for
+
+// padded slots of the stride-2 problem (0: a size the entry points refuse)
+long s2_slots(int M, int N, int images, int Ho, int Wo) {
+    if (M <= 0 || N <= 0 || images <= 0 || Ho <= 0 || Wo <= 0 || M % 64 || N % 64 || Wo > W3S2_MAX_WO) return 0;
+    const long P = (long)images * (Ho + 1) * (Wo + 1);
+    return P > 0x7fffffffL / 2 ? 0 : P;
+}
+
+// Rows of the XCD-aware tile order (xcd_tile): a slab's tiles as one row where the slabs alone fill the eight XCDs evenly,
+// else the input-channel tiles of a slab in 2, 4, .. groups until the rows are a multiple of eight (or the tiles run out)
+int s2_gsplit(int n_slabs, int ntn) {
+    int gs = 1;
+    while ((n_slabs * gs) % 8 && ntn % (2 * gs) == 0) gs *= 2;
+    return gs;
+}
+
+}  // namespace
+}  // namespace peclr
+
+// Slab policy of peclr_wgrad3_h_slabs on the OUTPUT's padded slots, under the kernel's 64 x 32 channel tiles.
+extern "C" int peclr_wgrad3s2_h_slabs(int M, int N, int images, int Ho, int Wo) {
+    const long P = s2_slots(M, N, images, Ho, Wo);
+    if (P <= 0) return 0;
+    return w3_slabs(P, (long)(M / 64) * (N / 32));
+}
+
+// dW slabs [n_slabs][Cout][9 * Cin] of a 3x3 / padding-1 / stride-2 convolution from 16-bit NHWC activations dY [images, Ho, Wo,
+// Cout], X [images, 2 Ho, 2 Wo, Cin].
+extern "C" int peclr_wgrad3s2_h(int dtype, int M, int N, int images, int Ho, int Wo, const void* dY, const void* X, float* slabs,
+                                int n_slabs, const void* zeros, peclr_stream_t stream) {
+    const long P = s2_slots(M, N, images, Ho, Wo);
+    if (const int e = w3_check(dY, X, slabs, zeros, P > 0, n_slabs, peclr_wgrad3s2_h_slabs(M, N, images, Ho, Wo), dtype)) return e;
+    W3S2Args g;
+    g.A = static_cast<const h16_t*>(dY); g.B = static_cast<const h16_t*>(X); g.slabs = slabs;
+    g.M = M; g.N = N; g.lda = M; g.ldb = N; g.Ho = Ho; g.Wo = Wo; g.images = images;
+    g.P = (int)P;
+    g.pchunk = ((g.P + n_slabs - 1) / n_slabs + 31) / 32 * 32;
+    g.zeros = static_cast<const h16_t*>(zeros);
+    magic_div((unsigned)((Ho + 1) * (Wo + 1)), g.m_hw, g.s_hw);
+    magic_div((unsigned)(Wo + 1), g.m_w, g.s_w);
+    g.gsplit = s2_gsplit(n_slabs, N / 32);
+    g.rows = n_slabs * g.gsplit;
+    const dim3 grid((unsigned)((g.rows + 7) / 8 * 8 * ((M / 64) * (N / 32) / g.gsplit)));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (dtype == PECLR_DTYPE_F16) hipLaunchKernelGGL(wgrad3_h_s2_kernel<true>, grid, dim3(256), 0, s, g);
+    else hipLaunchKernelGGL(wgrad3_h_s2_kernel<false>, grid, dim3(256), 0, s, g);
+    return launch_status();
+}
