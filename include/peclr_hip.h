@@ -772,6 +772,29 @@ int peclr_pose_head_f32(const float* feat, int B, int n_feat, const float* fc_w,
                         const double* T1, double* T2, int S, const double* scale, double* fh, int* status,
                         peclr_stream_t stream);
 
+/* The two ends of the same two-pass prediction for images of ANY size in one batch, with a left-hand flag per sample
+ * (csrc/predict.hip; host side: peclr_amd/predict.py, HandPosePredictor).  One launch each, no atomics, no host synchronisation.
+ *
+ * peclr_pose_crop_ragged_u8: peclr_pose_crop_u8 for a packed batch.  packed: total_bytes of u8, the images back to back and
+ *   unpadded (image starts need no alignment).  geom: DEVICE table [B][4] int64 = (byte offset of the image in packed, H, W,
+ *   flip), read by the kernel -- a captured launch sees whatever the table holds at replay.  T, K, table, S, out, k_out as
+ *   peclr_pose_crop_u8; sample b of out is, bit for bit, what that entry point writes for image b alone.  flip != 0: a tap at
+ *   source column sx reads column W - 1 - sx, i.e. the crop of img[:, ::-1] (left hands are mirrored into right hands before
+ *   the network sees them), and k_out = float32(T @ Kf) with Kf = F K M, the camera of the mirrored image looking at the mirrored
+ *   scene, formed in float64 with one product and one difference per entry: r[c] = (W - 1) K[2][c] - K[0][c];
+ *   Kf = [[-r[0], r[1], r[2]], [-K[1][0], K[1][1], K[1][2]], [-K[2][0], K[2][1], K[2][2]]].
+ *   That offset + 3 H W <= total_bytes for every row is the caller's to guarantee; a row for which it does not hold (or with
+ *   H < 1 or W < 1) is treated as an empty image -- every tap outside -- and nothing is read through it.
+ * peclr_pose_unmap: after pass 2.  out64 [B][64] (the 2D keypoints of joint j at [3j], [3j + 1], crop pixels), T2 [B][3][3]
+ *   float64, geom as above, kp3d_in [B][21][3] float32, fh [B][21][3] float64 (peclr_pose_head_f32's pass-2 outputs; none is
+ *   written).  Out: kp2d_src [B][21][2] float64, the keypoints in SOURCE pixels: with mi = cv's invertAffineTransform(T2[:2]),
+ *   u = mi[0] x + mi[1] y + mi[2], v = mi[3] x + mi[4] y + mi[5] (float64, left to right, no contraction), and
+ *   u = (W - 1) - u for flip; kp3d [B][21][3] float32 and xyz [B][21][3] float64: copies of kp3d_in and fh, X negated for flip. */
+int peclr_pose_crop_ragged_u8(const uint8_t* packed, int64_t total_bytes, int B, const int64_t* geom, const double* T,
+                              const double* K, const float* table, int S, float* out, float* k_out, peclr_stream_t stream);
+int peclr_pose_unmap(const float* out64, const double* T2, const int64_t* geom, const float* kp3d_in, const double* fh, int B,
+                     double* kp2d_src, float* kp3d, double* xyz, peclr_stream_t stream);
+
 /* The same head in train mode -- BatchNorm1d on batch statistics, running statistics updated on the device -- and its exact
  * backward (csrc/pose_train.hip; host side: peclr_amd/pose.py, PoseHeadTrain).  fp32 with the batch reductions of BatchNorm
  * in float64, every reduction in a fixed order, no

@@ -131,6 +131,8 @@ SIGNATURES = {
     "peclr_pose_crop_u8": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P]),
     "peclr_pose_head_f32": (c_int, [_P, c_int, c_int, _P, _P, _P, c_float, c_float, _P, c_int, c_float, _P, _P, _P, _P, c_int,
                                     _P, _P, _P, _P]),
+    "peclr_pose_crop_ragged_u8": (c_int, [_P, c_int64, c_int, _P, _P, _P, _P, c_int, _P, _P, _P]),
+    "peclr_pose_unmap": (c_int, [_P, _P, _P, _P, _P, c_int, _P, _P, _P, _P]),
     "peclr_pose_head_train_fwd_f32": (c_int, [_P, c_int, c_int, _P, _P, _P, c_float, c_float, c_float, c_float, _P, _P, _P, c_int,
                                               c_float, _P, _P, _P, _P, _P]),
     "peclr_pose_head_train_bwd_f32": (c_int, [_P, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -1700,6 +1702,57 @@ def pose_head(feat: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, mlp, b
             _ptr(scale, torch.float64, "pose_head scale"), fh.data_ptr() if fh is not None else None,
             _ptr(status, torch.int32, "pose_head status"), _stream(), nbytes=4 * b * (nf + 64 + 63 + 64) + 4 * 64 * nf)
     return out64, kp3d, T2, fh, status
+
+
+# ------------------------------------------------------------------ the same prediction for images of any size (peclr_amd/predict.py)
+POSE_GEOM_COLS = 4   # a row of the device table: byte offset into the packed buffer, H, W, flip
+
+
+def _pose_geom_ptr(geom, what):
+    if (not geom.is_cuda or geom.dtype != torch.int64 or geom.dim() != 2 or geom.shape[1] != POSE_GEOM_COLS or geom.shape[0] < 1
+            or not geom.is_contiguous()):
+        raise PeclrHipError(f"{what}: geom must be a contiguous [B,{POSE_GEOM_COLS}] int64 HIP tensor (offset, H, W, flip), got "
+                            f"{geom.dtype} {tuple(geom.shape)} on {geom.device} (peclr_amd has no CPU path)")
+    return geom.data_ptr(), int(geom.shape[0])
+
+
+def pose_crop_ragged(data: torch.Tensor, geom: torch.Tensor, T: torch.Tensor, K: Optional[torch.Tensor], table: torch.Tensor,
+                     size: int):
+    """`pose_crop` for a packed batch: data 1-D uint8 (the images back to back), geom [B,4] int64 ON THE DEVICE = (byte offset, H,
+    W, flip) per sample -> (float32 [B,3,size,size] channels_last, float32 K' [B,3,3] or None).  flip: the crop of
+    img[:, ::-1] and K' = T @ Kf (include/peclr_hip.h).  That every row lies inside `data` is the caller's to check (the table
+    is on the device); the kernel reads nothing through a row that does not.  One launch."""
+    if not data.is_cuda or data.dtype != torch.uint8 or data.dim() != 1 or data.numel() < 1 or not data.is_contiguous():
+        raise PeclrHipError(f"pose_crop_ragged: data must be a contiguous 1-D uint8 HIP tensor, got {data.dtype} "
+                            f"{tuple(data.shape)} on {data.device} (peclr_amd has no CPU path)")
+    gp, b = _pose_geom_ptr(geom, "pose_crop_ragged")
+    tp, kp = _mat_ptr(T, b, torch.float64, "T"), _mat_ptr(K, b, torch.float64, "K")
+    if tuple(table.shape) != (3, 256):
+        raise PeclrHipError("pose_crop_ragged: table must be [3,256] float32")
+    out = torch.empty((b, 3, size, size), device=data.device, dtype=torch.float32, memory_format=torch.channels_last)
+    k_out = torch.empty((b, 3, 3), device=data.device, dtype=torch.float32) if K is not None else None
+    _launch("pose_crop_ragged", "peclr_pose_crop_ragged_u8", data.data_ptr(), data.numel(), b, gp, tp, kp,
+            _ptr(table, what="pose_crop_ragged table"), size, out.data_ptr(), k_out.data_ptr() if k_out is not None else None,
+            _stream(), nbytes=data.numel() + b * size * size * 12)
+    return out, k_out
+
+
+def pose_unmap(out64: torch.Tensor, T2: torch.Tensor, geom: torch.Tensor, kp3d: torch.Tensor, fh: torch.Tensor):
+    """The pass-2 outputs back into the sample's own frame: out64 [B,64] float32, T2 [B,3,3] float64, geom as `pose_crop_ragged`,
+    kp3d [B,21,3] float32, fh [B,21,3] float64 -> (kp2d_src [B,21,2] float64 in source pixels, kp3d, xyz: copies with X negated
+    for flip).  The inputs are not written.  One launch."""
+    gp, b = _pose_geom_ptr(geom, "pose_unmap")
+    for t, shape, what in ((out64, (b, 64), "out64"), (kp3d, (b, 21, 3), "kp3d"), (fh, (b, 21, 3), "fh")):
+        if tuple(t.shape) != shape:
+            raise PeclrHipError(f"pose_unmap: {what} must be {list(shape)}, got {tuple(t.shape)}")
+    dev = out64.device
+    kp2d_src = torch.empty((b, 21, 2), device=dev, dtype=torch.float64)
+    kp3d_out = torch.empty((b, 21, 3), device=dev, dtype=torch.float32)
+    xyz = torch.empty((b, 21, 3), device=dev, dtype=torch.float64)
+    _launch("pose_unmap", "peclr_pose_unmap", _ptr(out64, what="pose_unmap out64"), _mat_ptr(T2, b, torch.float64, "T2"), gp,
+            _ptr(kp3d, what="pose_unmap kp3d"), _ptr(fh, torch.float64, "pose_unmap fh"), b, kp2d_src.data_ptr(),
+            kp3d_out.data_ptr(), xyz.data_ptr(), _stream(), nbytes=b * (64 * 4 + 72 + 63 * 24 + 42 * 8))
+    return kp2d_src, kp3d_out, xyz
 
 
 # ------------------------------------------------------------------ the same head in train mode, with its backward

@@ -11,6 +11,7 @@
 //
 // The work is small (the head is ~0.13 MFLOP per image); the point is one launch per stage, no intermediate tensors and no
 // host round trip between the two passes.
+#include "affine.hpp"
 #include "common.hpp"
 #include "pose_head.hpp"
 #include "warp_u8.hpp"
@@ -22,16 +23,6 @@ namespace {
 using namespace pose_head;  // the stages shared with the training head (pose_train.hip)
 
 constexpr int CX = 64, CY = 4;  // crop: one thread per output pixel, consecutive lanes = consecutive x
-
-// cv::invertAffineTransform of the 2x3 forward matrix (imgwarp.cpp), [a11 a12 b1 a21 a22 b2]
-__device__ __forceinline__ void invert_affine(const double* m, double* mi) {
-    double d = m[0] * m[4] - m[1] * m[3];
-    d = d != 0.0 ? 1.0 / d : 0.0;
-    const double a11 = m[4] * d, a22 = m[0] * d, a12 = m[1] * -d, a21 = m[3] * -d;
-    mi[0] = a11, mi[1] = a12, mi[3] = a21, mi[4] = a22;
-    mi[2] = -a11 * m[2] - a12 * m[5];
-    mi[5] = -a21 * m[2] - a22 * m[5];
-}
 
 __global__ __launch_bounds__(CX* CY) void pose_crop_kernel(const uint8_t* __restrict__ images, int H, int W,
                                                            const double* __restrict__ T, const double* __restrict__ K,

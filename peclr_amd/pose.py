@@ -329,14 +329,14 @@ class FreiHANDPredictor:
 
     def __init__(self, model: RN25DwMLPref, crop_size: int = CROP_SIZE, bbox_scale: float = BBOX_SCALE, precision="fp32", fold_bn=None):
         if isinstance(precision, bool) or not isinstance(precision, (str, int)) or precision not in self.PRECISIONS:
-            raise ValueError(f"FreiHANDPredictor: precision must be one of 'fp32', 32, 'bf16', 'fp16', 16 -- got {precision!r}")
+            raise ValueError(f"{type(self).__name__}: precision must be one of 'fp32', 32, 'bf16', 'fp16', 16 -- got {precision!r}")
         self.autocast_dtype = self.PRECISIONS[precision]
         self.fold_bn = self.autocast_dtype is not None and (self.FOLD_BN_DEFAULT if fold_bn is None else bool(fold_bn))
         self.model, self.size = model, crop_size
         self.T1 = initial_transform(crop_size, bbox_scale)
         self.device = model.backend_model.fc.weight.device
         if self.device.type != "cuda":
-            raise _capi.PeclrHipError("FreiHANDPredictor: the model must be on a HIP device (peclr_amd has no CPU path)")
+            raise _capi.PeclrHipError(f"{type(self).__name__}: the model must be on a HIP device (peclr_amd has no CPU path)")
         self._table = torch.from_numpy(normalisation_table()).to(self.device)
         self._T1 = torch.from_numpy(self.T1).reshape(1, 3, 3).to(self.device)
         self.last = None

@@ -274,17 +274,20 @@ class PoseEvaluator:
                            if bits & bit]
                     raise FloatingPointError(f"pose evaluation failed for {what} {bad.tolist()}: {', '.join(why)}")
         n = filled[0]
-        if n == 0:
+        if n == 0 and not filled[1]:
             raise RuntimeError("PoseEvaluator.compute: no samples")
         cast = _NP[self.dtype]
-        counts = counts.reshape(2, NUM_JOINTS, -1)
-        out = {"Mean_EPE_3D": cast(stats[0]), "Median_EPE_3D": cast(stats[1]),
-               "AUC": float(np.mean(auc_from_counts(counts[0], n, self.thresholds))),
-               "Mean_EPE_3D_procrustes": cast(stats[2]), "Median_EPE_3D_procrustes": cast(stats[3]),
-               "auc_procrustes": float(np.mean(auc_from_counts(counts[1], n, self.thresholds)))}
+        out = {}
+        if n:                                            # (a 2D-only protocol, YouTube-3D-Hands', feeds update_2d alone)
+            counts = counts.reshape(2, NUM_JOINTS, -1)
+            out = {"Mean_EPE_3D": cast(stats[0]), "Median_EPE_3D": cast(stats[1]),
+                   "AUC": float(np.mean(auc_from_counts(counts[0], n, self.thresholds))),
+                   "Mean_EPE_3D_procrustes": cast(stats[2]), "Median_EPE_3D_procrustes": cast(stats[3]),
+                   "auc_procrustes": float(np.mean(auc_from_counts(counts[1], n, self.thresholds)))}
         if self._dist_2d is not None and filled[1]:
             out["Mean_EPE_2D"], out["Median_EPE_2D"] = cast(stats[4]), cast(stats[5])
-        out["pck"], out["pck_procrustes"] = curve_from_counts(counts[0], n), curve_from_counts(counts[1], n)
+        if n:
+            out["pck"], out["pck_procrustes"] = curve_from_counts(counts[0], n), curve_from_counts(counts[1], n)
         out["thresholds"] = self.thresholds.copy()
         return out
 
