@@ -635,6 +635,33 @@ int peclr_augment_resize_color_norm_ragged_ext(const uint8_t* crops, int B, int 
                                                const float* stdv, int channels_last, float* out,
                                                peclr_stream_t stream);
 
+/* LEFT HANDS (TwoViewAugmenter / SupervisedAugmenter with is_left): the reference's loader turns a left hand into a right
+ * one before augmentation (youtube_loader.py:151-155, cv2.flip(img, 1)).  Here the stage that reads the caller's images
+ * reads the flagged samples mirrored -- column W - 1 - c for column c -- and everything else (warp coordinates and weights,
+ * border tests, reflect-101 columns, the cut-out box, the blur taps) is in the mirrored image's coordinates: the sample
+ * comes out as img[:, ::-1] would through the entry points above, bit for bit, and no flipped copy exists anywhere.
+ *
+ * mirror : device [B] ints, one per SAMPLE (not per view), non-zero = read mirrored.  Its own pointer: geom keeps its
+ *          PECLR_AUG_GEOM_INT64S columns.  One batch mixes left and right hands in one launch per stage.
+ * The mirror is applied ONCE, by the stage that reads the caller's images: a batch that runs stage 0 calls
+ * peclr_augment_pre_*mirror_u8 and then the plain warp on the per-view sources (which hold the mirrored image already); a
+ * batch without stage 0 calls peclr_augment_warp_crop_*mirror_u8.  Stage 2 never sees the caller's images.  The other
+ * arguments are those of the entry point without `_mirror`, whose kernels are untouched. */
+int peclr_augment_warp_crop_mirror_u8(const uint8_t* images, int B, int H, int W, int n_views,
+                                      const double* params, const int* mirror, uint8_t* crops,
+                                      peclr_stream_t stream);
+int peclr_augment_pre_mirror_u8(const uint8_t* images, int B, int H, int W, int n_views,
+                                const int* ext, const int* coefs, int kx, int ky, const int* mirror,
+                                uint8_t* srcs, uint16_t* blur_tmp, peclr_stream_t stream);
+int peclr_augment_pre_ragged_mirror_u8(const uint8_t* images, int B, int n_views, const int64_t* geom,
+                                       int64_t total_bytes, int max_h, int max_w, const int* ext,
+                                       const int* coefs, int max_kx, int max_ky, const int* mirror,
+                                       uint8_t* srcs, uint16_t* blur_tmp, peclr_stream_t stream);
+int peclr_augment_warp_crop_ragged_mirror_u8(const uint8_t* images, int B, int n_views,
+                                             const int64_t* geom, const double* params,
+                                             const int64_t* wins, int max_cw, int max_ch,
+                                             const int* mirror, uint8_t* crops, peclr_stream_t stream);
+
 /* ---- 16-bit convolutions of the residual blocks (bf16 / fp16 autocast: BASELINE configs C3 / C5 and the reference's own
  * `precision: 16`, training_config.json:9, peclr_training.py:78-79), csrc/conv_h.hip.  They replace MIOpen's 16-bit
  * convolution kernels behind torchvision's Bottleneck / BasicBlock (resnet_model.py:15) -- forward and input gradient of the
@@ -891,6 +918,16 @@ int peclr_joints25d_to_3d(const float* joints25d, const float* scale, const floa
 int peclr_supervised_labels(const float* K, const float* joints3d, const double* T, const float* joints_raw, int B, int use_palm,
                             float* joints, float* k_out, float* scale, float* joints3d_out, float* joints3d_recreated,
                             float* joints_raw_out, float* t_out, peclr_stream_t stream);
+/* peclr_supervised_labels_mirror: peclr_supervised_labels with mirror_w [B] ints per sample: 0 = the sample as stored,
+ *   W > 0 = the LEFT hand of an image of width W, labelled as the right hand of img[:, ::-1].  For such a sample, before
+ *   anything else: K <- fl32(Kf), Kf = F K M the camera of the mirrored image looking at the mirrored scene (the predictor's
+ *   rule, csrc/predict.hip: row 0 <- (W - 1) row 2 - row 0, then column 0 negated; float64 from the float32 K, the product
+ *   being exact, and ONE rounding), and joints3d / joints_raw get X negated.  From there it is peclr_supervised_labels (one
+ *   shared kernel body) on those values; a sample with 0 comes out as from peclr_supervised_labels. */
+int peclr_supervised_labels_mirror(const float* K, const float* joints3d, const double* T, const float* joints_raw,
+                                   const int* mirror_w, int B, int use_palm, float* joints, float* k_out, float* scale,
+                                   float* joints3d_out, float* joints3d_recreated, float* joints_raw_out, float* t_out,
+                                   peclr_stream_t stream);
 
 /* The supervised losses of the 2.5D pose model with their gradients (reference src/models/utils.py: cal_l1_loss, cal_3d_loss,
  * through convert_2_5D_to_3D / get_root_depth), csrc/pose_loss.hip; host side: peclr_amd/pose_loss.py.  Inputs and emitted

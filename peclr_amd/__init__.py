@@ -13,11 +13,11 @@ from .pose_loss import PoseLoss, l1_loss, loss_3d, pose_losses
 from .pose_metrics import calculate_metrics, step_metrics
 from .port import (get_encoder_state_dict, get_latest_checkpoint, peclr_to_torchvision, restore_model,
                    save_checkpoint)
-from .supervised import SupervisedAugmenter, joints3d_to_25d, joints25d_to_3d, root_depth
+from .supervised import SupervisedAugmenter, joints3d_to_25d, joints25d_to_3d, mirror_camera, root_depth
 from .trainer import Trainer
 
 __all__ = ["Config", "hybrid2_config", "BaseModel", "SimCLR", "Hybrid2Model", "get_model",
            "peclr_to_torchvision", "get_encoder_state_dict", "get_latest_checkpoint", "save_checkpoint", "restore_model",
            "Trainer", "TwoViewAugmenter", "RaggedImages", "epe_statistics", "procrustes_transform", "pck_curves", "auc_joints",
-           "PoseEvaluator", "SupervisedAugmenter", "joints3d_to_25d", "joints25d_to_3d", "root_depth",
+           "PoseEvaluator", "SupervisedAugmenter", "joints3d_to_25d", "joints25d_to_3d", "root_depth", "mirror_camera",
            "pose_losses", "l1_loss", "loss_3d", "PoseLoss", "calculate_metrics", "step_metrics", "supervised_config", "SupervisedPose"]

@@ -83,6 +83,11 @@ SIGNATURES = {
     "peclr_augment_pre_ragged_u8": (c_int, [_P, c_int, c_int, _P, c_int64, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P]),
     "peclr_augment_warp_crop_ragged_u8": (c_int, [_P, c_int, c_int, _P, _P, _P, c_int, c_int, _P, _P]),
     "peclr_augment_resize_color_norm_ragged": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, _P, _P, c_int, _P, _P]),
+    "peclr_augment_warp_crop_mirror_u8": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "peclr_augment_pre_mirror_u8": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, _P]),
+    "peclr_augment_pre_ragged_mirror_u8": (c_int, [_P, c_int, c_int, _P, c_int64, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P,
+                                                   _P]),
+    "peclr_augment_warp_crop_ragged_mirror_u8": (c_int, [_P, c_int, c_int, _P, _P, _P, c_int, c_int, _P, _P, _P]),
     "peclr_augment_resize_color_norm_ragged_ext": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, c_int, c_uint64, c_uint32,
                                                            c_int, c_int, _P, _P, c_int, _P, _P]),
     "peclr_gemm_x6_f32": (c_int, [c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P]),
@@ -141,6 +146,7 @@ SIGNATURES = {
     "peclr_joints3d_to_25d": (c_int, [_P, _P, c_int, _P, _P, _P]),
     "peclr_joints25d_to_3d": (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P]),
     "peclr_supervised_labels": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "peclr_supervised_labels_mirror": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "peclr_pose_loss": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P]),
     "peclr_pose_loss_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, _P, _P, _P]),
     "peclr_pose_step_metrics_f32": (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P]),
@@ -1481,6 +1487,16 @@ class _AugExt:
         self.noise = (ext.data_ptr(), noise_table.data_ptr(), n_table, noise_seed & (2 ** 64 - 1), call & 0xFFFFFFFF)
 
 
+def _aug_mirror(mirror, b: int):
+    """The per-sample left-hand table (None, or int32 [B] on the device, non-zero = the image is read mirrored) -> its pointer."""
+    if mirror is None:
+        return None
+    if (not isinstance(mirror, torch.Tensor) or mirror.dtype != torch.int32 or tuple(mirror.shape) != (b,) or not mirror.is_cuda
+            or not mirror.is_contiguous()):
+        raise PeclrHipError(f"augment: mirror must be a contiguous [{b}] int32 HIP tensor")
+    return mirror.data_ptr()
+
+
 def _aug_out(v, b, out_hw, mean, std, channels_last, device):
     """The float32 [V*B,3,oh,ow] output and the tail of both resize entry points' arguments that writes it."""
     oh, ow = out_hw
@@ -1490,9 +1506,11 @@ def _aug_out(v, b, out_hw, mean, std, channels_last, device):
     return out, (oh, ow, ctypes.cast(mean_arr, c_void_p), ctypes.cast(std_arr, c_void_p), int(channels_last), out.data_ptr())
 
 
-def _augment_uniform(images, params, b, v, aug, ksize, out_hw, mean, std, channels_last):
+def _augment_uniform(images, params, b, v, aug, ksize, out_hw, mean, std, channels_last, mirror=None):
     """Both stages for same-size images -> (out, srcs or None, crops).  aug: `_AugExt` or None.  Stage 0 (sobel / cut-out /
-    blur), when `aug.ops` names it, writes per-view sources and the warp then runs once per view on them."""
+    blur), when `aug.ops` names it, writes per-view sources and the warp then runs once per view on them.  mirror: the
+    left-hand table's pointer or None; it goes to the ONE stage that reads `images` (stage 0 when it runs, else the warp),
+    whose log entry then names the mirrored kernel."""
     _, h, w, _ = images.shape
     dev, stream = images.device, _stream()
     crops = torch.empty((v, b, h, w, 3), device=dev, dtype=torch.uint8)
@@ -1504,15 +1522,23 @@ def _augment_uniform(images, params, b, v, aug, ksize, out_hw, mean, std, channe
         srcs = torch.empty((v, b, h, w, 3), device=dev, dtype=torch.uint8)
         tmp = torch.empty((v, b, h, w, 3), device=dev, dtype=torch.int16) if ops & AUG_EXT_BLUR else None
         blur_bytes = (kx + ky) * 3 if tmp is not None else 0
-        _launch("augment_pre", "peclr_augment_pre_u8", images.data_ptr(), b, h, w, v, aug.ext, aug.coefs, kx, ky,
-                srcs.data_ptr(), None if tmp is None else tmp.data_ptr(), stream,
-                nbytes=v * b * h * w * (3 + 3 + 4 * (3 if tmp is not None else 0)), flops=v * b * h * w * blur_bytes)
+        pre_tail = (srcs.data_ptr(), None if tmp is None else tmp.data_ptr(), stream)
+        pre_work = dict(nbytes=v * b * h * w * (3 + 3 + 4 * (3 if tmp is not None else 0)), flops=v * b * h * w * blur_bytes)
+        if mirror is None:
+            _launch("augment_pre", "peclr_augment_pre_u8", images.data_ptr(), b, h, w, v, aug.ext, aug.coefs, kx, ky, *pre_tail,
+                    **pre_work)
+        else:
+            _launch("augment_pre", "peclr_augment_pre_mirror_u8", images.data_ptr(), b, h, w, v, aug.ext, aug.coefs, kx, ky, mirror,
+                    *pre_tail, kernel="pre_rows_kernel<Mirrored>", **pre_work)
         for i in range(v):
             _launch("augment_warp_crop", "peclr_augment_warp_crop_u8", srcs[i].data_ptr(), b, h, w, 1, params[i].data_ptr(),
                     crops[i].data_ptr(), stream, nbytes=2 * b * h * w * 3)
-    else:
+    elif mirror is None:
         _launch("augment_warp_crop", "peclr_augment_warp_crop_u8", images.data_ptr(), b, h, w, v, params.data_ptr(), crops.data_ptr(),
                 stream, nbytes=2 * v * b * h * w * 3)
+    else:
+        _launch("augment_warp_crop", "peclr_augment_warp_crop_mirror_u8", images.data_ptr(), b, h, w, v, params.data_ptr(), mirror,
+                crops.data_ptr(), stream, nbytes=2 * v * b * h * w * 3, kernel="warp_crop_kernel<Mirrored>")
     head = (crops.data_ptr(), b, h, w, v, params.data_ptr())
     nbytes = v * b * (h * w * 3 + out_hw[0] * out_hw[1] * 12)
     if ops & AUG_EXT_POST:
@@ -1522,26 +1548,30 @@ def _augment_uniform(images, params, b, v, aug, ksize, out_hw, mean, std, channe
     return out, srcs, crops
 
 
-def augment_views(images: torch.Tensor, params: torch.Tensor, out_hw, mean, std, channels_last: bool = True):
+def augment_views(images: torch.Tensor, params: torch.Tensor, out_hw, mean, std, channels_last: bool = True,
+                  mirror: Optional[torch.Tensor] = None):
     """images [B,H,W,3] uint8 (HIP), params [V,B,16] float64 (HIP) -> float32 [V*B,3,out_h,out_w]
-    (channels_last storage if asked).  Two launches: rotate+crop window, then resize+colour+normalise."""
+    (channels_last storage if asked).  Two launches: rotate+crop window, then resize+colour+normalise.
+    mirror: None, or int32 [B] (HIP), non-zero = that sample's image is read mirrored (a left hand; include/peclr_hip.h) --
+    the same two launches, the warp through its `_mirror` entry point."""
     b, v = _aug_uniform_args(images, params)
-    out, _, crops = _augment_uniform(images, params, b, v, None, None, out_hw, mean, std, channels_last)
+    out, _, crops = _augment_uniform(images, params, b, v, None, None, out_hw, mean, std, channels_last, _aug_mirror(mirror, b))
     return out, crops
 
 
 def augment_views_ext(images: torch.Tensor, params: torch.Tensor, ext: torch.Tensor, coefs: torch.Tensor, ksize,
                       noise_table: torch.Tensor, n_table: int, noise_seed: int, call: int, ops: int, out_hw, mean, std,
-                      channels_last: bool = True):
+                      channels_last: bool = True, mirror: Optional[torch.Tensor] = None):
     """augment_views plus the reference's other five augmentations (peclr_amd/augment.py builds the inputs):
     ext [V,B,8] int32 records, coefs int32 Q8 blur taps, ksize (horizontal, vertical) blur lengths of the batch,
     noise_table int32 storage of n_table uint32 thresholds, the Philox key and call index, and `ops`, the OR of
     all records' bits (the stages it names are the only ones launched).  Stage 0 (sobel / cut-out / blur) writes
-    per-view sources, the warp then runs once per view on them.
+    per-view sources, the warp then runs once per view on them.  mirror: as augment_views; stage 0 mirrors when it runs
+    (srcs then hold the mirrored images and the warp reads them as they are), the warp otherwise.
     Returns (out, srcs or None, crops)."""
     b, v = _aug_uniform_args(images, params)
     aug = _AugExt(v, b, ext, coefs, noise_table, n_table, noise_seed, call, ops)
-    return _augment_uniform(images, params, b, v, aug, ksize, out_hw, mean, std, channels_last)
+    return _augment_uniform(images, params, b, v, aug, ksize, out_hw, mean, std, channels_last, _aug_mirror(mirror, b))
 
 
 # ---- the same for a batch whose images differ in size (include/peclr_hip.h: the geometry tables)
@@ -1580,7 +1610,7 @@ def _ragged_args(packed, geom, wins, params):
     return b, v, scratch
 
 
-def _augment_ragged(packed, geom, wins, params, b, v, scratch, aug, out_hw, mean, std, channels_last):
+def _augment_ragged(packed, geom, wins, params, b, v, scratch, aug, out_hw, mean, std, channels_last, mirror=None):
     """`_augment_uniform` for a packed batch (`_ragged_args` checked it) -> (out, srcs or None, crops)."""
     dev, stream = packed.device, _stream()
     total = packed.numel()
@@ -1597,15 +1627,25 @@ def _augment_ragged(packed, geom, wins, params, b, v, scratch, aug, out_hw, mean
         # (without the blur stage the lengths are not read: nothing to check)
         kx, ky = (int(geom[:, 3].max()), int(geom[:, 4].max())) if tmp is not None else (1, 1)
         blur_work = int(((geom[:, 3] + geom[:, 4]) * geom[:, 1] * geom[:, 2]).sum()) * 3 if tmp is not None else 0
-        _launch("augment_pre", "peclr_augment_pre_ragged_u8", packed.data_ptr(), b, v, geom_d.data_ptr(), total, int(geom[:, 1].max()),
-                int(geom[:, 2].max()), aug.ext, aug.coefs, kx, ky, srcs.data_ptr(), None if tmp is None else tmp.data_ptr(), stream,
-                nbytes=v * total * (1 + 1 + (4 if tmp is not None else 0)), flops=v * blur_work)
+        pre_head = (packed.data_ptr(), b, v, geom_d.data_ptr(), total, int(geom[:, 1].max()), int(geom[:, 2].max()), aug.ext, aug.coefs,
+                    kx, ky)
+        pre_tail = (srcs.data_ptr(), None if tmp is None else tmp.data_ptr(), stream)
+        pre_work = dict(nbytes=v * total * (1 + 1 + (4 if tmp is not None else 0)), flops=v * blur_work)
+        if mirror is None:
+            _launch("augment_pre", "peclr_augment_pre_ragged_u8", *pre_head, *pre_tail, **pre_work)
+        else:
+            _launch("augment_pre", "peclr_augment_pre_ragged_mirror_u8", *pre_head, mirror, *pre_tail,
+                    kernel="pre_rows_kernel<Mirrored>", **pre_work)
         for i in range(v):
             _launch("augment_warp_crop", "peclr_augment_warp_crop_ragged_u8", srcs[i].data_ptr(), b, 1, geom_d.data_ptr(), params[i].data_ptr(),
                     wins_d[i].data_ptr(), max_cw, max_ch, crops.data_ptr(), stream, nbytes=2 * int((wins[i, :, 2] * wins[i, :, 3]).sum()) * 3)
-    else:
+    elif mirror is None:
         _launch("augment_warp_crop", "peclr_augment_warp_crop_ragged_u8", packed.data_ptr(), b, v, geom_d.data_ptr(), params.data_ptr(),
                 wins_d.data_ptr(), max_cw, max_ch, crops.data_ptr(), stream, nbytes=2 * win_bytes)
+    else:
+        _launch("augment_warp_crop", "peclr_augment_warp_crop_ragged_mirror_u8", packed.data_ptr(), b, v, geom_d.data_ptr(),
+                params.data_ptr(), wins_d.data_ptr(), max_cw, max_ch, mirror, crops.data_ptr(), stream, nbytes=2 * win_bytes,
+                kernel="warp_crop_kernel<Mirrored>")
     head = (crops.data_ptr(), b, v, wins_d.data_ptr(), params.data_ptr())
     nbytes = win_bytes + v * b * out_hw[0] * out_hw[1] * 12
     if ops & AUG_EXT_POST:
@@ -1616,25 +1656,28 @@ def _augment_ragged(packed, geom, wins, params, b, v, scratch, aug, out_hw, mean
 
 
 def augment_views_ragged(packed: torch.Tensor, geom: torch.Tensor, wins: torch.Tensor, params: torch.Tensor, out_hw, mean,
-                         std, channels_last: bool = True):
+                         std, channels_last: bool = True, mirror: Optional[torch.Tensor] = None):
     """augment_views for images of different sizes: `packed` the 1-D uint8 HIP buffer of the images back to back,
     geom [B,5] / wins [V,B,4] the HOST int64 tables of include/peclr_hip.h (peclr_amd/augment.py builds them; they are
-    uploaded here), params [V,B,16] float64 (HIP).  The same two launches.
+    uploaded here), params [V,B,16] float64 (HIP).  The same two launches.  mirror: as augment_views.
     Returns (out, crops, wins): crops the packed scratch, `ragged_window(crops, wins, v, i)` a window of it."""
     b, v, scratch = _ragged_args(packed, geom, wins, params)
-    out, _, crops = _augment_ragged(packed, geom, wins, params, b, v, scratch, None, out_hw, mean, std, channels_last)
+    out, _, crops = _augment_ragged(packed, geom, wins, params, b, v, scratch, None, out_hw, mean, std, channels_last,
+                                    _aug_mirror(mirror, b))
     return out, crops, wins
 
 
 def augment_views_ragged_ext(packed: torch.Tensor, geom: torch.Tensor, wins: torch.Tensor, params: torch.Tensor,
                              ext: torch.Tensor, coefs: torch.Tensor, noise_table: torch.Tensor, n_table: int, noise_seed: int,
-                             call: int, ops: int, out_hw, mean, std, channels_last: bool = True):
+                             call: int, ops: int, out_hw, mean, std, channels_last: bool = True,
+                             mirror: Optional[torch.Tensor] = None):
     """augment_views_ext for images of different sizes (arguments as augment_views_ragged and augment_views_ext; the
     blur lengths are geom's, per sample).  Stage 0's per-view sources come back as srcs [V, total bytes] in the packed
-    layout (`ragged_image(srcs[v], geom, i)`).  Returns (out, srcs or None, crops, wins)."""
+    layout (`ragged_image(srcs[v], geom, i)`).  mirror: as augment_views_ext.  Returns (out, srcs or None, crops, wins)."""
     b, v, scratch = _ragged_args(packed, geom, wins, params)
     aug = _AugExt(v, b, ext, coefs, noise_table, n_table, noise_seed, call, ops)
-    return (*_augment_ragged(packed, geom, wins, params, b, v, scratch, aug, out_hw, mean, std, channels_last), wins)
+    return (*_augment_ragged(packed, geom, wins, params, b, v, scratch, aug, out_hw, mean, std, channels_last,
+                             _aug_mirror(mirror, b)), wins)
 
 
 # ------------------------------------------------------------------ 2.5D hand-pose model at evaluation time (peclr_amd/pose.py)
@@ -1946,20 +1989,27 @@ def joints25d_to_3d(joints25d: torch.Tensor, scale: torch.Tensor, K: torch.Tenso
 
 
 def supervised_labels(K: torch.Tensor, joints3d: torch.Tensor, T: torch.Tensor, use_palm: bool = False,
-                      joints_raw: Optional[torch.Tensor] = None):
+                      joints_raw: Optional[torch.Tensor] = None, mirror_w: Optional[torch.Tensor] = None):
     """K [B,3,3], joints3d [B,21,3] float32, T [B,3,3] float64 forward matrices, joints_raw [B,21,3] float32 or None -> dict of
-    float32 tensors: joints, K (= fl32(T) @ K), scale, joints3D, joints3D_recreated, joints_raw, T.  One launch."""
+    float32 tensors: joints, K (= fl32(T) @ K), scale, joints3D, joints3D_recreated, joints_raw, T.  One launch.
+    mirror_w: None, or int32 [B] (HIP): 0 = the sample as stored, W > 0 = a left hand in an image of width W, labelled as the
+    right hand of the mirrored image (K <- fl32(F K M), X of joints3d / joints_raw negated; include/peclr_hip.h)."""
     b = _label_batch(joints3d, "supervised_labels")
     kp, jp = _label_ptr(K, (b, 3, 3), "supervised_labels K"), _label_ptr(joints3d, (b, 21, 3), "supervised_labels joints3d")
     tp = _label_ptr(T, (b, 3, 3), "supervised_labels T", torch.float64)
     rp = _label_ptr(joints_raw, (b, 21, 3), "supervised_labels joints_raw")
+    mp = _label_ptr(mirror_w, (b,), "supervised_labels mirror_w", torch.int32)
     z = dict(device=joints3d.device, dtype=torch.float32)
     out = {"joints": torch.empty((b, 21, 3), **z), "K": torch.empty((b, 3, 3), **z), "scale": torch.empty((b,), **z),
            "joints3D": torch.empty((b, 21, 3), **z), "joints3D_recreated": torch.empty((b, 21, 3), **z),
            "joints_raw": torch.empty((b, 21, 3), **z), "T": torch.empty((b, 3, 3), **z)}
-    _launch("supervised_labels", "peclr_supervised_labels", kp, jp, tp, rp, b, int(bool(use_palm)),
-            *(out[k].data_ptr() for k in ("joints", "K", "scale", "joints3D", "joints3D_recreated", "joints_raw", "T")), _stream(),
-            nbytes=4 * b * (9 + 63 + 18 + 4 * 63 + 1 + 18))
+    outs = tuple(out[k].data_ptr() for k in ("joints", "K", "scale", "joints3D", "joints3D_recreated", "joints_raw", "T"))
+    nbytes = 4 * b * (9 + 63 + 18 + 4 * 63 + 1 + 18)
+    if mirror_w is None:
+        _launch("supervised_labels", "peclr_supervised_labels", kp, jp, tp, rp, b, int(bool(use_palm)), *outs, _stream(), nbytes=nbytes)
+    else:
+        _launch("supervised_labels", "peclr_supervised_labels_mirror", kp, jp, tp, rp, mp, b, int(bool(use_palm)), *outs, _stream(),
+                nbytes=nbytes + 4 * b, kernel="supervised_labels_kernel<mirror>")
     return out
 
 

@@ -23,6 +23,11 @@ NotImplementedError.  With it their draws join the reference's order and their p
 more device stages (see `TwoViewAugmenter.__init__`).  `resize` is required either way (without it
 the reference's crops have per-sample sizes and cannot be collated either).
 
+Left hands: the reference's YouTube-3D-Hands loader turns every left hand into a right one before augmentation
+(src/data_loader/youtube_loader.py:151-155: cv2.flip(img, 1) and x <- W - x).  Pass `is_left` and the flagged samples'
+images are READ mirrored inside the pixel stages (csrc/augment.hip; no flipped copy on the host or the device) while their
+joints follow the loader's rule; a batch mixes left and right hands in the same launches.
+
 The images of one batch may differ in size (the reference concatenates YouTube-3D-Hands frames, of whatever size
 the video had, with FreiHAND's 224 x 224, and augments each sample on its own): pass `RaggedImages`, or a list of
 HWC arrays, instead of one [B,H,W,3] tensor.  The draws, the launches and the emitted dict are the same; every
@@ -154,6 +159,31 @@ def _image_hw(image, i: int) -> Tuple[int, int]:
     if h < 1 or w < 1:
         raise ValueError(f"image {i}: empty ({h}x{w})")
     return h, w
+
+
+def check_is_left(is_left, b: int) -> Optional[List[bool]]:
+    """`is_left` of a batch of b samples -> a list of b bools (None stays None).  Accepts a sequence, NumPy array or tensor of
+    bools or of integers 0 / 1; anything else, or another length, raises.  No native call."""
+    if is_left is None:
+        return None
+    a = is_left.detach().cpu().numpy() if isinstance(is_left, Tensor) else np.asarray(is_left)
+    if a.ndim != 1 or a.shape[0] != b:
+        raise ValueError(f"is_left: expected {b} entries, one per sample, got shape {tuple(a.shape)}")
+    if a.dtype != np.bool_:
+        if not np.issubdtype(a.dtype, np.integer):
+            raise TypeError(f"is_left: expected bools or integers 0 / 1, got {a.dtype}")
+        if ((a != 0) & (a != 1)).any():
+            raise ValueError("is_left: integer entries must be 0 or 1")
+    return [bool(x) for x in a]
+
+
+def mirror_table(left: Optional[List[bool]], sizes: Sequence[Tuple[int, int]]) -> Optional[Tensor]:
+    """include/peclr_hip.h's per-sample table of a batch with left hands: int32 [B] (host), the image's width for a left
+    sample and 0 otherwise (the pixel stages read non-zero as "mirrored", the label kernel reads the width).  None when
+    no sample is left: such a batch takes the entry points without the table."""
+    if left is None or not any(left):
+        return None
+    return torch.tensor([int(hw[1]) if l else 0 for l, hw in zip(left, sizes)], dtype=torch.int32)
 
 
 class RaggedImages:
@@ -378,15 +408,22 @@ class TwoViewAugmenter:
         return ([*(view["minv"] if rot else [1.0, 0.0, 0.0, 0.0, 1.0, 0.0]), float(rot), *map(float, view["crop"]),
                  float(col), *((view["h"], view["s"], view["a"], view["b"]) if col else (1.0, 1.0, 1.0, 0.0))])
 
-    def sample_batch(self, joints25d: Tensor, image_hw: Union[Tuple[int, int], Sequence[Tuple[int, int]]]):
+    def sample_batch(self, joints25d: Tensor, image_hw: Union[Tuple[int, int], Sequence[Tuple[int, int]]], is_left=None):
         """Draws view 1 then view 2 for each sample in turn (the order a dataset iterates).  image_hw: one (H, W)
-        for the whole batch, or one per sample."""
+        for the whole batch, or one per sample.  is_left: per sample; the draws of a left sample read its joints, given in
+        the STORED image's coordinates, as x <- W - x in float32 -- the reference loader's rule (W, not W - 1: the mirrored
+        image's column of x is W - 1 - x, but the joints only place the crop window here, and drawing the windows the
+        reference draws is this project's contract)."""
         views: List[List[Dict]] = [[], []]
         if isinstance(image_hw[0], (int, np.integer)):
             image_hw = [tuple(image_hw)] * len(joints25d)
         elif len(image_hw) != len(joints25d):
             raise ValueError(f"{len(image_hw)} image sizes for {len(joints25d)} samples")
-        for j, hw in zip(joints25d, image_hw):
+        left = check_is_left(is_left, len(joints25d))
+        for i, (j, hw) in enumerate(zip(joints25d, image_hw)):
+            if left is not None and left[i]:
+                j = j.detach().to("cpu", torch.float32).clone()
+                j[:, 0] = int(hw[1]) - j[:, 0]
             for v in (0, 1):
                 views[v].append(self.sample_view(j, (int(hw[0]), int(hw[1]))))
         params = torch.tensor([[self.pack(w) for w in views[v]] for v in (0, 1)], dtype=torch.float64)
@@ -433,7 +470,7 @@ class TwoViewAugmenter:
                     raise ValueError(f"gaussian_blur: a {h}x{w} image needs kernels {blur_ksize((h, w))}, "
                                      f"longer than the device's {MAX_BLUR_KSIZE}")
 
-    def _call_ragged(self, images, joints25d: Tensor) -> Dict[str, Tensor]:
+    def _call_ragged(self, images, joints25d: Tensor, is_left=None) -> Dict[str, Tensor]:
         """Everything that can be refused is refused before the first device call."""
         if isinstance(images, RaggedImages):
             sizes = images.sizes
@@ -443,12 +480,15 @@ class TwoViewAugmenter:
         if len(joints25d) != b:
             raise ValueError(f"{b} images for {len(joints25d)} samples of joints")
         self._check_blur_sizes(sizes)
-        params, views = self.sample_batch(joints25d, sizes)
+        left = check_is_left(is_left, b)
+        params, views = self.sample_batch(joints25d, sizes, left)
         if not isinstance(images, RaggedImages):
             dev = next((im.device for im in images if isinstance(im, Tensor) and im.is_cuda), torch.device("cuda"))
             images = RaggedImages.from_list(images, dev)
         dev = images.device
         geom, wins = self.ragged_tables(sizes, images.offsets, views)
+        mirror = mirror_table(left, sizes)
+        lr = {} if mirror is None else {"mirror": mirror.to(dev, non_blocking=True)}  # no left hand: today's calls as they are
         rw, rh = self.params["resize_shape"]
         call = self.noise_call
         self.noise_call += 1
@@ -458,27 +498,36 @@ class TwoViewAugmenter:
                 ops |= self.ext_flags(view)
         if not ops:  # as in __call__: the recipe's two launches
             out = _capi.augment_views_ragged(images.data, geom, wins, params.to(dev, non_blocking=True), (rh, rw),
-                                             IMAGENET_MEAN, IMAGENET_STD, self.channels_last)[0]
+                                             IMAGENET_MEAN, IMAGENET_STD, self.channels_last, **lr)[0]
         else:
             ext, coefs = self.pack_ext(views)
             table, n_table = self.noise_table()
             out = _capi.augment_views_ragged_ext(images.data, geom, wins, params.to(dev, non_blocking=True),
                                                  ext.to(dev, non_blocking=True), coefs.to(dev, non_blocking=True),
                                                  table.to(dev, non_blocking=True), n_table, self.noise_seed, call, ops,
-                                                 (rh, rw), IMAGENET_MEAN, IMAGENET_STD, self.channels_last)[0]
+                                                 (rh, rw), IMAGENET_MEAN, IMAGENET_STD, self.channels_last, **lr)[0]
         batch = {"transformed_images": out, "transformed_image1": out[:b], "transformed_image2": out[b:]}
         batch.update({k: t.to(dev, non_blocking=True) for k, t in self.collate(views).items()})
+        if left is not None:
+            batch["is_left"] = torch.tensor(left, dtype=torch.bool).to(dev, non_blocking=True)
         return batch
 
     # ---- device: the batch
-    def __call__(self, images: Union[Tensor, RaggedImages, Sequence], joints25d: Tensor) -> Dict[str, Tensor]:
+    def __call__(self, images: Union[Tensor, RaggedImages, Sequence], joints25d: Tensor, is_left=None) -> Dict[str, Tensor]:
         """images: [B,H,W,3] uint8 on the HIP device (the reference's RGB HWC arrays, one size per
         batch), or -- for a batch whose images differ in size -- a `RaggedImages`, or a list / tuple of HWC uint8
-        arrays (packed and copied here); joints25d: [B,21,3] (any device; the parameter logic runs on the host)."""
+        arrays (packed and copied here); joints25d: [B,21,3] (any device; the parameter logic runs on the host).
+        is_left: None, or B bools (or integers 0 / 1): a flagged sample comes out as the reference loader's
+        (cv2.flip(img, 1), x <- W - x) would -- its image as stored, read mirrored on the device, its joints in the stored
+        image's coordinates (`sample_batch` has the rule).  The dict then also holds `is_left` (bool [B], device).  None or
+        all false launches exactly what a call without it launches."""
         if not isinstance(images, Tensor):
-            return self._call_ragged(images, joints25d)
+            return self._call_ragged(images, joints25d, is_left)
         b, h, w, _ = images.shape
-        params, views = self.sample_batch(joints25d, (h, w))
+        left = check_is_left(is_left, b)
+        params, views = self.sample_batch(joints25d, (h, w), left)
+        mirror = mirror_table(left, [(h, w)] * b)
+        lr = {} if mirror is None else {"mirror": mirror.to(images.device, non_blocking=True)}
         rw, rh = self.params["resize_shape"]
         call = self.noise_call
         self.noise_call += 1
@@ -488,7 +537,7 @@ class TwoViewAugmenter:
                 ops |= self.ext_flags(view)
         if not ops:  # none of the five drawn anywhere in the batch: exactly the recipe's two launches
             out, _ = _capi.augment_views(images, params.to(images.device, non_blocking=True), (rh, rw), IMAGENET_MEAN,
-                                         IMAGENET_STD, self.channels_last)
+                                         IMAGENET_STD, self.channels_last, **lr)
         else:
             if ops & EXT_BLUR and max(blur_ksize((h, w))) > MAX_BLUR_KSIZE:
                 raise ValueError(f"gaussian_blur: a {h}x{w} image needs kernels {blur_ksize((h, w))}, "
@@ -499,9 +548,11 @@ class TwoViewAugmenter:
             out = _capi.augment_views_ext(images, params.to(dev, non_blocking=True), ext.to(dev, non_blocking=True),
                                           coefs.to(dev, non_blocking=True), blur_ksize((h, w)),
                                           table.to(dev, non_blocking=True), n_table, self.noise_seed, call, ops,
-                                          (rh, rw), IMAGENET_MEAN, IMAGENET_STD, self.channels_last)[0]
+                                          (rh, rw), IMAGENET_MEAN, IMAGENET_STD, self.channels_last, **lr)[0]
         # both views are the halves of ONE buffer; `transformed_images` lets the model skip its cat(view1, view2)
         # (hybrid2_model.py:30-32) -- an extra "image" entry, which the reference's consumers of the dict ignore
         batch = {"transformed_images": out, "transformed_image1": out[:b], "transformed_image2": out[b:]}
         batch.update({k: t.to(images.device, non_blocking=True) for k, t in self.collate(views).items()})
+        if left is not None:
+            batch["is_left"] = torch.tensor(left, dtype=torch.bool).to(images.device, non_blocking=True)
         return batch

@@ -31,6 +31,11 @@
 // crop scratch is PACKED: the host knows every window before the launch, so window (view, sample) sits at its own byte
 // offset with its own width as row stride, and the scratch is the sum of the windows instead of V*B*H*W*3.
 //
+// LEFT HANDS (the *_mirror entry points): either source wrapped in `Mirrored<>` carries a per-sample table, and the stage that
+// reads the caller's images -- pre_rows_kernel when stage 0 runs, warp_crop_kernel otherwise, never both -- reads a flagged
+// sample's columns in reverse: the sample is processed exactly as img[:, ::-1] would be (what the reference's YouTube loader
+// feeds its augmenter for a left hand), in the same launch as its right-handed neighbours and without a flipped copy.
+//
 // Work per batch is tiny (B=128: ~40 MB read, ~50 MB written): these kernels exist to take the
 // cv2-on-CPU producer off the critical path, not to approach a roofline.  One thread per pixel,
 // consecutive lanes = consecutive x, so the float32 NHWC / NCHW stores coalesce.
@@ -111,7 +116,7 @@ struct WinGeom {
 // image(n): the source image of (view, sample) n = view * B + sample; view_off(n, g): the element offset of n's copy in
 // the per-view buffers `srcs` / `blur_tmp`; kRagged: grids are the batch maximum's, so blocks test their own extent.
 struct UniformSrc {
-    static constexpr bool kRagged = false;
+    static constexpr bool kRagged = false, kMirror = false;
     int B, H, W, kx, ky;
     __device__ __forceinline__ SrcGeom image(int n) const { return SrcGeom{(size_t)(n % B) * H * W * 3, H, W, kx, ky}; }
     __device__ __forceinline__ size_t view_off(int n, const SrcGeom&) const { return (size_t)n * H * W * 3; }
@@ -126,7 +131,7 @@ struct RaggedSrc {
     int B;
     const long long* __restrict__ geom;  // [B][NG]
     size_t total;                        // bytes of the packed source = elements of one view of srcs / blur_tmp
-    static constexpr bool kRagged = true;
+    static constexpr bool kRagged = true, kMirror = false;
     __device__ __forceinline__ SrcGeom image(int n) const {
         const long long* g = geom + (size_t)(n % B) * NG;
         // (the lengths are bounded on the host; the clamp only keeps a bad table inside the LDS arrays)
@@ -135,6 +140,24 @@ struct RaggedSrc {
     }
     __device__ __forceinline__ size_t view_off(int n, const SrcGeom& g) const { return (size_t)(n / B) * total + g.off; }
 };
+// A source with LEFT HANDS: `mirror` (one int per SAMPLE, non-zero = a left hand) says whose image the stage reads mirrored,
+// column W - 1 - c for column c.  The stage then works on img[:, ::-1] -- warp coordinates and weights, border tests, the
+// reflect-101 columns, the cut-out box, the blur taps and the stores are all in the mirrored image's coordinates -- without a
+// flipped copy.  The flag is uniform over a block.  A plain source (kMirror false) compiles to the code of before.
+template <class SRC>
+struct Mirrored : SRC {
+    const int* __restrict__ mirror;  // [B]
+    static constexpr bool kMirror = true;
+    __device__ __forceinline__ bool left(int n) const { return mirror[n % SRC::B] != 0; }
+};
+template <class SRC>
+__device__ __forceinline__ bool reads_mirrored(const SRC& geo, int n) {
+    if constexpr (SRC::kMirror)
+        return geo.left(n);
+    else
+        return false;
+}
+
 struct RaggedWin {
     const long long* __restrict__ wins;  // [V][B][NW]
     __device__ __forceinline__ WinGeom window(int n) const {
@@ -147,8 +170,9 @@ constexpr int SEG = BX + 2 * PRE_RMAX;  // row positions a block of pre_rows_ker
 constexpr int COL_ROWS = 8;               // output rows per thread of pre_cols_kernel (sliding window)
 
 // pixel after Sobel and cut-out at image (y, c), packed c0 | c1 << 8 | c2 << 16.  gt: the block's gray tile
-// (rows y-1 .. y+1 at gt[0..2], image column c at gt[.][gi + 1]).
-__device__ __forceinline__ uint32_t pre_packed(const uint8_t* __restrict__ src, int W, int y, int c, const ExtParam& e,
+// (rows y-1 .. y+1 at gt[0..2], image column c at gt[.][gi + 1]).  cs: the column of `src` that holds image column c
+// (c itself, or W - 1 - c when the image is the caller's read mirrored).
+__device__ __forceinline__ uint32_t pre_packed(const uint8_t* __restrict__ src, int W, int y, int c, int cs, const ExtParam& e,
                                                const uint8_t (*gt)[SEG + 2], int gi) {
     int v0, v1, v2;
     if (e.flags & PECLR_AUG_EXT_SOBEL) {
@@ -160,7 +184,7 @@ __device__ __forceinline__ uint32_t pre_packed(const uint8_t* __restrict__ src, 
         const int sy = (g20 + 2 * g21 + g22) - (g00 + 2 * g01 + g02);
         v0 = v1 = v2 = (sx + sy) & 255;
     } else {
-        const uint8_t* s = src + ((size_t)y * W + c) * 3;
+        const uint8_t* s = src + ((size_t)y * W + cs) * 3;
         v0 = s[0], v1 = s[1], v2 = s[2];
     }
     if ((e.flags & PECLR_AUG_EXT_CUT_OUT) && y >= e.r0 && y < e.r1 && c >= e.c0 && c < e.c1) v0 = v1 = v2 = e.fill;
@@ -184,6 +208,7 @@ __global__ __launch_bounds__(BX* BY) void pre_rows_kernel(const uint8_t* __restr
     const int x0 = blockIdx.x * BX, y0 = blockIdx.y * BY, tid = threadIdx.y * BX + threadIdx.x;
     if (SRC::kRagged && (x0 >= W || y0 >= H)) return;  // block-uniform, before any barrier
     const uint8_t* src = images + g.off;
+    const bool left = reads_mirrored(geo, n);  // block-uniform
     const size_t view = geo.view_off(n, g);  // this (view, sample) in srcs / tmp
     const bool blur = (e.flags & PECLR_AUG_EXT_BLUR) && tmp;  // block-uniform
     const int rx = blur ? kx >> 1 : 0;
@@ -194,7 +219,8 @@ __global__ __launch_bounds__(BX* BY) void pre_rows_kernel(const uint8_t* __restr
         const int gw = hi - lo + 2;
         for (int i = tid; i < (BY + 2) * gw; i += BX * BY) {
             const int j = i / gw, c = i - j * gw;
-            gray[j][c] = (uint8_t)gray_at(src, W, reflect101(y0 - 1 + j, H), reflect101(lo - 1 + c, W));
+            const int gy = reflect101(y0 - 1 + j, H), gc = reflect101(lo - 1 + c, W);
+            gray[j][c] = (uint8_t)gray_at(src, W, gy, left ? W - 1 - gc : gc);
         }
         __syncthreads();
     }
@@ -204,7 +230,8 @@ __global__ __launch_bounds__(BX* BY) void pre_rows_kernel(const uint8_t* __restr
         for (int i = threadIdx.x; i < npos; i += BX) {
             const int c = reflect101(x0 - rx + i, W);
             const int gi = min(max(c - lo, 0), hi - lo - 1);  // == c - lo (see above); the clamp only bounds LDS
-            seg[threadIdx.y][i] = pre_packed(src, W, y, c, e, (const uint8_t(*)[SEG + 2])gray[threadIdx.y], gi);
+            seg[threadIdx.y][i] = pre_packed(src, W, y, c, left ? W - 1 - c : c, e,
+                                             (const uint8_t(*)[SEG + 2])gray[threadIdx.y], gi);
         }
     }
     __syncthreads();
@@ -270,6 +297,7 @@ __global__ __launch_bounds__(BX* BY) void pre_cols_kernel(SRC geo, const int* __
 }
 
 // ---- stage 1: rotation (8-bit warpAffine, bilinear, zero border), evaluated on the crop window only
+// (After stage 0 the per-view sources ARE the mirrored images of the left samples: that warp runs on a plain source.)
 template <class SRC, class WIN>
 __global__ __launch_bounds__(BX* BY) void warp_crop_kernel(const uint8_t* __restrict__ images, SRC geo, WIN win,
                                                             const double* __restrict__ params,
@@ -284,14 +312,18 @@ __global__ __launch_bounds__(BX* BY) void warp_crop_kernel(const uint8_t* __rest
     const uint8_t* src = images + g.off;
     uint8_t* dst = crops + wg.off + (size_t)cy * wg.stride + (size_t)cx * 3;
     const int x = v.x0 + cx, y = v.y0 + cy;
+    const bool left = reads_mirrored(geo, n);  // block-uniform
     if (!v.rotate) {
-        const uint8_t* s = src + ((size_t)y * W + x) * 3;
+        const uint8_t* s = src + ((size_t)y * W + (left ? W - 1 - x : x)) * 3;
         dst[0] = s[0], dst[1] = s[1], dst[2] = s[2];
         return;
     }
     // 10-bit fixed-point source coordinates, rounded to 1/32 pixel (warp_u8.hpp)
     int px[3];
-    warp_bilinear_u8(src, H, W, v.minv, x, y, px);
+    if (left)
+        warp_bilinear_u8<true>(src, H, W, v.minv, x, y, px);
+    else
+        warp_bilinear_u8(src, H, W, v.minv, x, y, px);
     dst[0] = (uint8_t)px[0], dst[1] = (uint8_t)px[1], dst[2] = (uint8_t)px[2];
 }
 
@@ -559,12 +591,17 @@ inline bool bad_ksize(int kx, int ky) {
     return kx < 1 || ky < 1 || !(kx & 1) || !(ky & 1) || kx > PECLR_AUG_MAX_BLUR_KSIZE || ky > PECLR_AUG_MAX_BLUR_KSIZE;
 }
 
-// stage 0 over the grid of an ext_h x ext_w image (the batch maximum for a ragged batch)
+// stage 0 over the grid of an ext_h x ext_w image (the batch maximum for a ragged batch); mirror: the left-hand table, or
+// nullptr for the plain source
 template <class SRC>
 int launch_pre(const uint8_t* images, SRC geo, int n_views, int ext_h, int ext_w, const int* ext, const int* coefs,
-               uint8_t* srcs, uint16_t* blur_tmp, hipStream_t s) {
+               const int* mirror, uint8_t* srcs, uint16_t* blur_tmp, hipStream_t s) {
     dim3 grid((ext_w + BX - 1) / BX, (ext_h + BY - 1) / BY, geo.B * n_views);
-    hipLaunchKernelGGL(pre_rows_kernel<SRC>, grid, dim3(BX, BY), 0, s, images, geo, ext, coefs, srcs, blur_tmp);
+    if (mirror)
+        hipLaunchKernelGGL(pre_rows_kernel<Mirrored<SRC>>, grid, dim3(BX, BY), 0, s, images, Mirrored<SRC>{geo, mirror}, ext, coefs,
+                           srcs, blur_tmp);
+    else
+        hipLaunchKernelGGL(pre_rows_kernel<SRC>, grid, dim3(BX, BY), 0, s, images, geo, ext, coefs, srcs, blur_tmp);
     if (blur_tmp) {
         dim3 gcol((ext_w + BX - 1) / BX, (ext_h + BY * COL_ROWS - 1) / (BY * COL_ROWS), geo.B * n_views);
         hipLaunchKernelGGL(pre_cols_kernel<SRC>, gcol, dim3(BX, BY), 0, s, geo, ext, coefs, blur_tmp, srcs);
@@ -574,9 +611,13 @@ int launch_pre(const uint8_t* images, SRC geo, int n_views, int ext_h, int ext_w
 
 template <class SRC, class WIN>
 int launch_warp(const uint8_t* images, SRC geo, WIN win, int n_views, int ext_h, int ext_w, const double* params,
-                uint8_t* crops, hipStream_t s) {
+                const int* mirror, uint8_t* crops, hipStream_t s) {
     dim3 grid((ext_w + BX - 1) / BX, (ext_h + BY - 1) / BY, geo.B * n_views);
-    hipLaunchKernelGGL((warp_crop_kernel<SRC, WIN>), grid, dim3(BX, BY), 0, s, images, geo, win, params, crops);
+    if (mirror)
+        hipLaunchKernelGGL((warp_crop_kernel<Mirrored<SRC>, WIN>), grid, dim3(BX, BY), 0, s, images, Mirrored<SRC>{geo, mirror}, win,
+                           params, crops);
+    else
+        hipLaunchKernelGGL((warp_crop_kernel<SRC, WIN>), grid, dim3(BX, BY), 0, s, images, geo, win, params, crops);
     return launch_status();
 }
 
@@ -609,7 +650,7 @@ extern "C" int peclr_augment_warp_crop_u8(const uint8_t* images, int B, int H, i
                                           uint8_t* crops, peclr_stream_t stream) {
     if (!images || !params || !crops) return PECLR_ERR_NULL;
     if (H <= 0 || W <= 0 || bad_batch(B, n_views)) return PECLR_ERR_SHAPE;
-    return launch_warp(images, UniformSrc{B, H, W, 1, 1}, UniformWin{H, W}, n_views, H, W, params, crops,
+    return launch_warp(images, UniformSrc{B, H, W, 1, 1}, UniformWin{H, W}, n_views, H, W, params, nullptr, crops,
                        static_cast<hipStream_t>(stream));
 }
 
@@ -628,7 +669,7 @@ extern "C" int peclr_augment_pre_u8(const uint8_t* images, int B, int H, int W, 
     if (!images || !ext || !coefs || !srcs) return PECLR_ERR_NULL;
     if (H <= 0 || W <= 0 || bad_batch(B, n_views)) return PECLR_ERR_SHAPE;
     if (bad_ksize(kx, ky)) return PECLR_ERR_SHAPE;
-    return launch_pre(images, UniformSrc{B, H, W, kx, ky}, n_views, H, W, ext, coefs, srcs, blur_tmp,
+    return launch_pre(images, UniformSrc{B, H, W, kx, ky}, n_views, H, W, ext, coefs, nullptr, srcs, blur_tmp,
                       static_cast<hipStream_t>(stream));
 }
 
@@ -654,7 +695,8 @@ extern "C" int peclr_augment_pre_ragged_u8(const uint8_t* images, int B, int n_v
     if (max_h <= 0 || max_w <= 0 || total_bytes <= 0 || bad_batch(B, n_views)) return PECLR_ERR_SHAPE;
     if (bad_ksize(max_kx, max_ky)) return PECLR_ERR_SHAPE;
     const RaggedSrc geo{B, reinterpret_cast<const long long*>(geom), (size_t)total_bytes};
-    return launch_pre(images, geo, n_views, max_h, max_w, ext, coefs, srcs, blur_tmp, static_cast<hipStream_t>(stream));
+    return launch_pre(images, geo, n_views, max_h, max_w, ext, coefs, nullptr, srcs, blur_tmp,
+                      static_cast<hipStream_t>(stream));
 }
 
 extern "C" int peclr_augment_warp_crop_ragged_u8(const uint8_t* images, int B, int n_views, const int64_t* geom,
@@ -664,7 +706,7 @@ extern "C" int peclr_augment_warp_crop_ragged_u8(const uint8_t* images, int B, i
     if (max_cw <= 0 || max_ch <= 0 || bad_batch(B, n_views)) return PECLR_ERR_SHAPE;
     const RaggedSrc geo{B, reinterpret_cast<const long long*>(geom), 0};
     return launch_warp(images, geo, RaggedWin{reinterpret_cast<const long long*>(wins)}, n_views, max_ch, max_cw, params,
-                       crops, static_cast<hipStream_t>(stream));
+                       nullptr, crops, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int peclr_augment_resize_color_norm_ragged(const uint8_t* crops, int B, int n_views, const int64_t* wins,
@@ -688,4 +730,47 @@ extern "C" int peclr_augment_resize_color_norm_ragged_ext(const uint8_t* crops, 
     const PostExt pe{ext, noise_table, n_table, (uint32_t)noise_seed, (uint32_t)(noise_seed >> 32), call};
     return launch_resize(crops, B, n_views, RaggedWin{reinterpret_cast<const long long*>(wins)}, params, out_h, out_w, mean,
                          stdv, channels_last, out, &pe, static_cast<hipStream_t>(stream));
+}
+
+// ---- left hands: stage 0 or stage 1 of a batch in which `mirror` [B] (device, one int per sample, non-zero = left) flags the
+// samples whose image is read mirrored.  Whichever stage reads the caller's images takes the flags -- stage 0 when it runs (the
+// warp then reads the per-view sources through the entry points above), stage 1 otherwise.
+extern "C" int peclr_augment_warp_crop_mirror_u8(const uint8_t* images, int B, int H, int W, int n_views, const double* params,
+                                                 const int* mirror, uint8_t* crops, peclr_stream_t stream) {
+    if (!images || !params || !mirror || !crops) return PECLR_ERR_NULL;
+    if (H <= 0 || W <= 0 || bad_batch(B, n_views)) return PECLR_ERR_SHAPE;
+    return launch_warp(images, UniformSrc{B, H, W, 1, 1}, UniformWin{H, W}, n_views, H, W, params, mirror, crops,
+                       static_cast<hipStream_t>(stream));
+}
+
+extern "C" int peclr_augment_pre_mirror_u8(const uint8_t* images, int B, int H, int W, int n_views, const int* ext,
+                                           const int* coefs, int kx, int ky, const int* mirror, uint8_t* srcs,
+                                           uint16_t* blur_tmp, peclr_stream_t stream) {
+    if (!images || !ext || !coefs || !mirror || !srcs) return PECLR_ERR_NULL;
+    if (H <= 0 || W <= 0 || bad_batch(B, n_views)) return PECLR_ERR_SHAPE;
+    if (bad_ksize(kx, ky)) return PECLR_ERR_SHAPE;
+    return launch_pre(images, UniformSrc{B, H, W, kx, ky}, n_views, H, W, ext, coefs, mirror, srcs, blur_tmp,
+                      static_cast<hipStream_t>(stream));
+}
+
+extern "C" int peclr_augment_pre_ragged_mirror_u8(const uint8_t* images, int B, int n_views, const int64_t* geom,
+                                                  int64_t total_bytes, int max_h, int max_w, const int* ext, const int* coefs,
+                                                  int max_kx, int max_ky, const int* mirror, uint8_t* srcs, uint16_t* blur_tmp,
+                                                  peclr_stream_t stream) {
+    if (!images || !geom || !ext || !coefs || !mirror || !srcs) return PECLR_ERR_NULL;
+    if (max_h <= 0 || max_w <= 0 || total_bytes <= 0 || bad_batch(B, n_views)) return PECLR_ERR_SHAPE;
+    if (bad_ksize(max_kx, max_ky)) return PECLR_ERR_SHAPE;
+    const RaggedSrc geo{B, reinterpret_cast<const long long*>(geom), (size_t)total_bytes};
+    return launch_pre(images, geo, n_views, max_h, max_w, ext, coefs, mirror, srcs, blur_tmp,
+                      static_cast<hipStream_t>(stream));
+}
+
+extern "C" int peclr_augment_warp_crop_ragged_mirror_u8(const uint8_t* images, int B, int n_views, const int64_t* geom,
+                                                        const double* params, const int64_t* wins, int max_cw, int max_ch,
+                                                        const int* mirror, uint8_t* crops, peclr_stream_t stream) {
+    if (!images || !geom || !params || !wins || !mirror || !crops) return PECLR_ERR_NULL;
+    if (max_cw <= 0 || max_ch <= 0 || bad_batch(B, n_views)) return PECLR_ERR_SHAPE;
+    const RaggedSrc geo{B, reinterpret_cast<const long long*>(geom), 0};
+    return launch_warp(images, geo, RaggedWin{reinterpret_cast<const long long*>(wins)}, n_views, max_ch, max_cw, params,
+                       mirror, crops, static_cast<hipStream_t>(stream));
 }

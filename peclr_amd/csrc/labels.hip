@@ -82,12 +82,29 @@ __device__ __forceinline__ void apply_t(const double T[9], double p[3]) {
     p[1] = v;
 }
 
+__device__ __forceinline__ int mirror_width(int) { return 0; }
+__device__ __forceinline__ int mirror_width(int b, const int* __restrict__ mirror_w) { return mirror_w[b]; }
+
+// a joint as the sample has it: with X negated when the sample is a mirrored one (LR: the kernel has the table)
+template <bool LR>
+__device__ __forceinline__ void load3_lr(const float* p, double v[3], bool left) {
+    load3(p, v);
+    if (LR && left) v[0] = -v[0];
+}
+
+// MIRROR: nothing, or `const int*`, the table mirror_w [B] -- a sample whose entry is W > 0 is the LEFT hand of an image of width
+// W, labelled as the right hand of img[:, ::-1]: before anything else K becomes fl32(Kf), Kf = F K M (predict.hip's rule: row 0 <-
+// (W - 1) row 2 - row 0, then column 0 negated; float64 from the float32 K -- the product is exact -- and one rounding), and
+// joints3d / joints_raw get X negated.  Without the table it is the kernel of before, argument list and code.
+template <class... MIRROR>
 __global__ __launch_bounds__(LT) void supervised_labels_kernel(const float* __restrict__ K, const float* __restrict__ j3d,
                                                                const double* __restrict__ T, const float* __restrict__ raw_in,
                                                                int B, int use_palm, float* __restrict__ joints,
                                                                float* __restrict__ k_out, float* __restrict__ scale_out,
                                                                float* __restrict__ j3d_out, float* __restrict__ recreated,
-                                                               float* __restrict__ raw_out, float* __restrict__ t_out) {
+                                                               float* __restrict__ raw_out, float* __restrict__ t_out,
+                                                               MIRROR... mirror_w) {
+    constexpr bool LR = sizeof...(MIRROR) != 0;
     const int lane = threadIdx.x % kWave;
     const int b = blockIdx.x * LS + threadIdx.x / kWave;
     if (b >= B || lane >= LJ) return;
@@ -96,6 +113,15 @@ __global__ __launch_bounds__(LT) void supervised_labels_kernel(const float* __re
     const float* R = raw_in ? raw_in + (size_t)b * LJ * 3 : J;
     double k[9], t[9], tf[9], kp[9];
     load9(K + (size_t)b * 9, k);
+    const int width = mirror_width(b, mirror_w...);
+    const bool left = LR && width > 0;
+    if (LR && left) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) k[c] = (double)(width - 1) * k[6 + c] - k[c];
+        k[0] = -k[0], k[3] = -k[3], k[6] = -k[6];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) k[i] = (double)(float)k[i];
+    }
 #pragma unroll
     for (int i = 0; i < 9; ++i) {
         t[i] = T[(size_t)b * 9 + i];
@@ -109,18 +135,18 @@ __global__ __launch_bounds__(LT) void supervised_labels_kernel(const float* __re
             kp[3 * r + c] = (double)(float)(tf[3 * r] * k[c] + tf[3 * r + 1] * k[3 + c] + tf[3 * r + 2] * k[6 + c]);
 
     double p[3], w[3], c[3], raw[3];
-    load3(J + lane * 3, p);
-    load3(J + kParent * 3, w);
-    load3(J + kChild * 3, c);
-    load3(R + lane * 3, raw);
+    load3_lr<LR>(J + lane * 3, p, left);
+    load3_lr<LR>(J + kParent * 3, w, left);
+    load3_lr<LR>(J + kChild * 3, c, left);
+    load3_lr<LR>(R + lane * 3, raw, left);
 
     // joints of this lane's joint, of the wrist and of the index MCP (the root depth needs the last two), and the scale
     double mine[3], n[3], m[3], s;
     if (use_palm) {
         // move_wrist_to_palm, then convert_to_2_5D on the moved (float32) joints with K'
         double r0[3], r2[3];
-        load3(R + kParent * 3, r0);
-        load3(R + kChild * 3, r2);
+        load3_lr<LR>(R + kParent * 3, r0, left);
+        load3_lr<LR>(R + kChild * 3, r2, left);
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             w[i] = (double)(float)((w[i] + c[i]) / 2.0);
@@ -195,8 +221,20 @@ extern "C" int peclr_supervised_labels(const float* K, const float* joints3d, co
                                        float* joints3d_recreated, float* joints_raw_out, float* t_out, peclr_stream_t stream) {
     if (B <= 0 || !K || !joints3d || !T) return PECLR_ERR_NULL;
     if (!joints || !k_out || !scale || !joints3d_out || !joints3d_recreated || !joints_raw_out || !t_out) return PECLR_ERR_NULL;
-    hipLaunchKernelGGL(supervised_labels_kernel, dim3(grid_of(B)), dim3(LT), 0, static_cast<hipStream_t>(stream), K, joints3d, T,
+    hipLaunchKernelGGL(supervised_labels_kernel<>, dim3(grid_of(B)), dim3(LT), 0, static_cast<hipStream_t>(stream), K, joints3d, T,
                        joints_raw, B, use_palm ? 1 : 0, joints, k_out, scale, joints3d_out, joints3d_recreated, joints_raw_out,
                        t_out);
+    return launch_status();
+}
+
+extern "C" int peclr_supervised_labels_mirror(const float* K, const float* joints3d, const double* T, const float* joints_raw,
+                                              const int* mirror_w, int B, int use_palm, float* joints, float* k_out, float* scale,
+                                              float* joints3d_out, float* joints3d_recreated, float* joints_raw_out, float* t_out,
+                                              peclr_stream_t stream) {
+    if (B <= 0 || !K || !joints3d || !T || !mirror_w) return PECLR_ERR_NULL;
+    if (!joints || !k_out || !scale || !joints3d_out || !joints3d_recreated || !joints_raw_out || !t_out) return PECLR_ERR_NULL;
+    hipLaunchKernelGGL(supervised_labels_kernel<const int*>, dim3(grid_of(B)), dim3(LT), 0, static_cast<hipStream_t>(stream), K, joints3d,
+                       T, joints_raw, B, use_palm ? 1 : 0, joints, k_out, scale, joints3d_out, joints3d_recreated, joints_raw_out,
+                       t_out, mirror_w);
     return launch_status();
 }

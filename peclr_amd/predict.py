@@ -13,7 +13,7 @@ backbone -> head) for
 
 and returns the 3D joints in the sample's camera frame and the 2D keypoints in source-image pixels (what
 `PoseEvaluator.update_2d` scores).  No host round trip between the passes, one status read at the end, one hipGraph
-(`capture` / `replay`).  Kernels: csrc/predict.hip.  The mirrored read exists here only; the augmenters take no `is_left`.
+(`capture` / `replay`).  Kernels: csrc/predict.hip.  The augmenters read left hands the same way (`is_left`; supervised.mirror_camera is `flip_camera`, rounded).
 
 Everything that can be refused is refused on the host before the first device call (`plan`), naming the sample.
 """

@@ -14,6 +14,12 @@ Mirrors `Data_Set.prepare_supervised_sample` (reference src/data_loader/data_set
 The conversions themselves are also here as batched functions of HIP tensors: `joints3d_to_25d` (convert_to_2_5D),
 `joints25d_to_3d` (convert_2_5D_to_3D) and `root_depth` (get_root_depth), one launch each.  Each stage is evaluated in
 float64 from float32 inputs and rounded once (csrc/labels.hip).
+
+Left hands (`is_left`): a left sample is BY DEFINITION the sample (img[:, ::-1], float32(F K M), joints3d with X negated,
+joints_raw with X negated) put through the path above -- the right hand that the mirrored camera sees in the mirrored scene,
+`HandPosePredictor(is_left=...)`'s convention, so that a model trained on such batches and the predictor agree on what a left
+hand looks like.  `mirror_camera` forms those values on the host (the draws read them); on the device the image is read
+mirrored in place and the label kernel forms the same values itself (`peclr_supervised_labels_mirror`).
 """
 from __future__ import annotations
 
@@ -23,7 +29,8 @@ import torch
 from torch import Tensor
 
 from . import _capi
-from .augment import IMAGENET_MEAN, IMAGENET_STD, RaggedImages, TwoViewAugmenter, blur_ksize, convert_to_2_5d
+from .augment import IMAGENET_MEAN, IMAGENET_STD, RaggedImages, TwoViewAugmenter, blur_ksize, check_is_left, convert_to_2_5d, \
+    mirror_table
 
 NUM_JOINTS = 21
 
@@ -45,6 +52,22 @@ def root_depth(joints25d: Tensor, K: Tensor) -> Tensor:
     clamp(min=1e-6).  (The conversion launch with a unit scale: its 3D output is dropped.)"""
     b = _capi._label_batch(joints25d, "root_depth")
     return _capi.joints25d_to_3d(joints25d, torch.ones((b,), device=joints25d.device, dtype=torch.float32), K)[1]
+
+
+def mirror_camera(K, joints3d, width) -> Tuple[Tensor, Tensor]:
+    """The labels of a left hand as the right hand of the mirrored image: K [...,3,3], joints3d [...,21,3] (tensors or arrays,
+    read as float32) and the image width (one integer, or one per leading index) -> (float32(F K M), joints3d with X negated),
+    float32 host tensors.  F: u -> (W - 1) - u, M = diag(-1, 1, 1); by the rule of csrc/predict.hip and csrc/labels.hip: row 0
+    <- (W - 1) row 2 - row 0, then column 0 negated, in float64 (the product is exact: an integer below 2^24 times a 24-bit
+    significand), rounded to float32 once.  Any [...,21,3] tensor (joints_raw) mirrors the same way."""
+    k = torch.as_tensor(K).detach().to("cpu", torch.float32).to(torch.float64)
+    j = torch.as_tensor(joints3d).detach().to("cpu", torch.float32).clone()
+    w1 = torch.as_tensor(width).to("cpu", torch.float64) - 1.0
+    kf = k.clone()
+    kf[..., 0, :] = w1[..., None] * k[..., 2, :] - k[..., 0, :]
+    kf[..., :, 0] = -kf[..., :, 0]
+    j[..., 0] = -j[..., 0]
+    return kf.to(torch.float32), j
 
 
 def transformation_matrix(view: Dict, resize_shape: Sequence[int]) -> List[List[float]]:
@@ -80,13 +103,16 @@ class SupervisedAugmenter:
         self.last_T: Optional[Tensor] = None             # their matrices [B,3,3] float64 (host)
 
     # ---- host
-    def sample_batch(self, K: Tensor, joints3d: Tensor, sizes: Sequence[Tuple[int, int]]):
+    def sample_batch(self, K: Tensor, joints3d: Tensor, sizes: Sequence[Tuple[int, int]], is_left=None):
         """One view per sample, in the order a dataset iterates -> (params [1,B,16] float64, views, T [B,3,3] float64), host.
-        The joints the draws read are the reference's: convert_to_2_5D on the float32 host tensors."""
+        The joints the draws read are the reference's: convert_to_2_5D on the float32 host tensors -- for a left sample on
+        `mirror_camera`'s float32 values, so that its draws are those of the flipped sample."""
         k, j = K.detach().to("cpu", torch.float32), joints3d.detach().to("cpu", torch.float32)
+        left = check_is_left(is_left, len(sizes))
         views = []
         for i, hw in enumerate(sizes):
-            joints25d, _ = convert_to_2_5d(k[i], j[i])
+            ki, ji = mirror_camera(k[i], j[i], int(hw[1])) if left is not None and left[i] else (k[i], j[i])
+            joints25d, _ = convert_to_2_5d(ki, ji)
             views.append(self.views.sample_view(joints25d, (int(hw[0]), int(hw[1])), always_crop=False))
         params = torch.tensor([[self.views.pack(w) for w in views]], dtype=torch.float64)
         T = torch.tensor([transformation_matrix(w, self.params["resize_shape"]) for w in views], dtype=torch.float64)
@@ -94,14 +120,18 @@ class SupervisedAugmenter:
 
     # ---- device
     def __call__(self, images: Union[Tensor, RaggedImages, Sequence], K: Tensor, joints3d: Tensor,
-                 joints_valid: Optional[Tensor] = None, joints_raw: Optional[Tensor] = None) -> Dict[str, Tensor]:
+                 joints_valid: Optional[Tensor] = None, joints_raw: Optional[Tensor] = None, is_left=None) -> Dict[str, Tensor]:
         """images: [B,H,W,3] uint8 on the HIP device, or a `RaggedImages` / a list of HWC uint8 arrays for a batch whose
         images differ in size.  K [B,3,3], joints3d [B,21,3] (and joints_raw [B,21,3], joints_valid [B,21,1]): host tensors
         as a dataset yields them (uploaded here without blocking), or device tensors (the draws then read a host copy,
         which synchronises).  Returns what torch's default collate makes of the reference's per-sample dicts: `image`
         float32 [B,3,S,S], `joints`, `joints3D`, `joints3D_recreated`, `joints_raw` float32 [B,21,3], `K`, `T` float32
         [B,3,3], `scale` float32 [B], `joints_valid` as given or ones [B,21,1] -- all on the device.  One label launch plus
-        the pixel launches; everything that can be refused is refused before the first device call."""
+        the pixel launches; everything that can be refused is refused before the first device call.
+        is_left: None, or B bools (or integers 0 / 1).  A flagged sample is given as STORED (a left hand, its own K and
+        joints) and comes out as the sample (img[:, ::-1], `mirror_camera(K, joints3d, W)`, joints_raw with X negated)
+        comes out without the flag, bit for bit: the image is read mirrored on the device, nothing is flipped on the host.
+        The dict then also holds `is_left` (bool [B]).  None or all false launches exactly what a call without it launches."""
         ragged = not isinstance(images, Tensor)
         if not ragged:
             if images.dim() != 4 or images.shape[3] != 3 or images.dtype != torch.uint8:
@@ -121,7 +151,8 @@ class SupervisedAugmenter:
         if joints_valid is not None and len(joints_valid) != b:
             raise ValueError(f"joints_valid: {len(joints_valid)} entries for {b} images")
         self.views._check_blur_sizes(sizes)
-        params, views, T = self.sample_batch(K, joints3d, sizes)     # raises on an empty crop window
+        left = check_is_left(is_left, b)
+        params, views, T = self.sample_batch(K, joints3d, sizes, left)     # raises on an empty crop window
 
         if ragged and not isinstance(images, RaggedImages):
             dev = next((im.device for im in images if isinstance(im, Tensor) and im.is_cuda), torch.device("cuda"))
@@ -129,18 +160,23 @@ class SupervisedAugmenter:
         dev = images.device
         up = lambda t: t.to(dev, torch.float32, non_blocking=True).contiguous()  # noqa: E731
         params_d = params.to(dev, non_blocking=True)
+        mirror = mirror_table(left, sizes)     # one table for the label kernel (the widths) and the pixel stages (non-zero)
+        lr = {} if mirror is None else {"mirror": mirror.to(dev, non_blocking=True)}  # no left hand: today's calls as they are
         labels = _capi.supervised_labels(up(K), up(joints3d), T.to(dev, non_blocking=True), self.use_palm,
-                                         None if joints_raw is None else up(joints_raw))
-        image = self._pixels(images, sizes, params_d, views)
+                                         None if joints_raw is None else up(joints_raw),
+                                         **({"mirror_w": lr["mirror"]} if lr else {}))
+        image = self._pixels(images, sizes, params_d, views, lr)
         self.last_views, self.last_params, self.last_T = views, params_d, T
         if joints_valid is None:
             joints_valid = torch.ones((b, NUM_JOINTS, 1), device=dev)
         return {"image": image, "joints": labels["joints"], "joints3D": labels["joints3D"], "K": labels["K"],
                 "scale": labels["scale"], "joints3D_recreated": labels["joints3D_recreated"],
-                "joints_valid": joints_valid.to(dev, non_blocking=True), "joints_raw": labels["joints_raw"], "T": labels["T"]}
+                "joints_valid": joints_valid.to(dev, non_blocking=True), "joints_raw": labels["joints_raw"], "T": labels["T"],
+                **({} if left is None else {"is_left": torch.tensor(left, dtype=torch.bool).to(dev, non_blocking=True)})}
 
-    def _pixels(self, images, sizes, params_d: Tensor, views: List[Dict]) -> Tensor:
-        """The existing pixel launches with one view (as `TwoViewAugmenter.__call__` / `_call_ragged` make them)."""
+    def _pixels(self, images, sizes, params_d: Tensor, views: List[Dict], lr: Optional[Dict] = None) -> Tensor:
+        """The existing pixel launches with one view (as `TwoViewAugmenter.__call__` / `_call_ragged` make them).  lr: the
+        `mirror=` keyword of a batch with left hands, or empty."""
         tv = self.views
         rw, rh = self.params["resize_shape"]
         dev = params_d.device
@@ -150,6 +186,7 @@ class SupervisedAugmenter:
         for view in views:
             ops |= tv.ext_flags(view)
         tail = ((rh, rw), IMAGENET_MEAN, IMAGENET_STD, self.channels_last)
+        lr = lr or {}
         if ops:
             ext, coefs = tv.pack_ext([views])
             table, n_table = tv.noise_table()
@@ -158,8 +195,8 @@ class SupervisedAugmenter:
         if isinstance(images, RaggedImages):
             geom, wins = tv.ragged_tables(sizes, images.offsets, [views])
             if not ops:
-                return _capi.augment_views_ragged(images.data, geom, wins, params_d, *tail)[0]
-            return _capi.augment_views_ragged_ext(images.data, geom, wins, params_d, *ext_args, *noise_args, *tail)[0]
+                return _capi.augment_views_ragged(images.data, geom, wins, params_d, *tail, **lr)[0]
+            return _capi.augment_views_ragged_ext(images.data, geom, wins, params_d, *ext_args, *noise_args, *tail, **lr)[0]
         if not ops:
-            return _capi.augment_views(images, params_d, *tail)[0]
-        return _capi.augment_views_ext(images, params_d, *ext_args, blur_ksize(sizes[0]), *noise_args, *tail)[0]
+            return _capi.augment_views(images, params_d, *tail, **lr)[0]
+        return _capi.augment_views_ext(images, params_d, *ext_args, blur_ksize(sizes[0]), *noise_args, *tail, **lr)[0]

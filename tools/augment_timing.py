@@ -7,7 +7,11 @@ With a second file name it also times batches whose images differ in size (`Ragg
 128 x 128 out): five repeats of the uniform 224 x 224 row (their spread is the yardstick), (a) the same images through
 the ragged path, (b) half 224 x 224 and half 480 x 640 through the ragged path, (c) the same mixed images as two
 uniform calls, one per size -- the only way to process them without the ragged path.
-Usage: python tools/augment_timing.py [out.json [ragged_out.json]]"""
+With `--left OUT.txt` it times left hands instead (`is_left`, the mirrored read): B = 128, 128 x 128 out, a dense 224 x 224
+batch and a mixed-size one (64 x 224^2 + 64 x 480 x 640), recipe flags (the warp mirrors) and all ten flags (stage 0 mirrors);
+per case six windows that ALTERNATE the batch without left hands and the same batch with every second sample left, so that the
+window-to-window spread of either arm is the yardstick for the difference between them.
+Usage: python tools/augment_timing.py [out.json [ragged_out.json]] | --left OUT.txt"""
 import json
 import os
 import random
@@ -97,7 +101,47 @@ def ragged_rows():
     return rows
 
 
+def left_rows(path):
+    b, size, windows = 128, 128, 6
+    g = np.random.default_rng(0)
+    small = [g.integers(0, 256, (224, 224, 3), dtype=np.uint8) for _ in range(b)]
+    big = [g.integers(0, 256, (480, 640, 3), dtype=np.uint8) for _ in range(b // 2)]
+    mixed = [im for pair in zip(small[:b // 2], big) for im in pair]
+    half = [i % 4 < 2 for i in range(b)]      # every second PAIR: half of either size in the mixed batch
+    lines = [f"is_left timing: B = {b}, out {size} x {size}, {windows} alternating windows per case (10 batches each after 3 warm-up "
+             "batches); kernel_us = device-event time per batch, summed per launch name", ""]
+    for flags_name, flags in (("recipe", None), ("all ten", ALL_TEN)):
+        for case, images in (("dense 128 x 224^2", torch.from_numpy(np.stack(small)).to(DEV)),
+                             ("mixed 64 x 224^2 + 64 x 480x640", RaggedImages.from_list(mixed, DEV))):
+            sizes = images.sizes if isinstance(images, RaggedImages) else [(224, 224)] * b
+            joints = torch.from_numpy(np.stack([np.concatenate([g.normal((w / 2, h / 2 - 4), min(h, w) / 9, (21, 2)),
+                                                                g.normal(0, 1, (21, 1))], 1) for h, w in sizes])).float()
+            arms = {"no left": [], "half left": []}
+            for win in range(windows):
+                arm = "half left" if win % 2 else "no left"
+                is_left = half if win % 2 else None
+                a = TwoViewAugmenter(flags, params={"resize_shape": [size, size]}, rng=random.Random(1), extended=flags is not None,
+                                     np_rng=np.random.RandomState(1) if flags else None)
+                r = timed(lambda: a(images, joints, is_left=is_left), lambda: a.sample_batch(joints, sizes, is_left))
+                arms[arm].append(r)
+                lines.append(f"{flags_name:8s} {case:34s} window {win} {arm:9s} kernel_us {r['kernel_us']} total {r['kernel_total_us']}"
+                             f" end_to_end_ms {r['end_to_end_ms']} host_param_ms {r['host_param_ms']}")
+                print(lines[-1], flush=True)
+            for name in sorted({k for rs in arms.values() for r in rs for k in r["kernel_us"]}) + ["kernel_total_us"]:
+                get = (lambda r: r["kernel_total_us"]) if name == "kernel_total_us" else (lambda r: r["kernel_us"].get(name, 0.0))
+                no, yes = [get(r) for r in arms["no left"]], [get(r) for r in arms["half left"]]
+                lines.append(f"  {name:32s} no left {min(no):8.1f} .. {max(no):8.1f}   half left {min(yes):8.1f} .. {max(yes):8.1f}   "
+                             f"difference of the means {sum(yes) / len(yes) - sum(no) / len(no):+8.1f} us, spread within an arm "
+                             f"{max(max(no) - min(no), max(yes) - min(yes)):.1f} us")
+                print(lines[-1], flush=True)
+            lines.append("")
+    with open(path, "w") as f:
+        f.write("\n".join(lines))
+
+
 def main():
+    if len(sys.argv) > 2 and sys.argv[1] == "--left":
+        return left_rows(sys.argv[2])
     rows = []
     g = np.random.default_rng(0)
     for b, size, all_ten in ((128, 128, False), (128, 224, False), (512, 128, False), (128, 128, True)):

@@ -80,6 +80,8 @@ def main():
     ap.add_argument("--epochs", type=int, default=EPOCHS)
     ap.add_argument("--lr", type=float, default=LR)
     ap.add_argument("--augment", choices=("full", "plain"), default=AUGMENT)
+    ap.add_argument("--left-frac", type=float, default=0.0,
+                    help="share of the training images marked as left hands (is_left: mirrored read, mirrored-camera labels)")
     ap.add_argument("out", nargs="?")
     opt = ap.parse_args()
     stock, args = opt.stock, [opt.out] if opt.out else []
@@ -100,13 +102,15 @@ def main():
     aug = SupervisedAugmenter(flags, params, rng=random.Random(0))
     val_aug = SupervisedAugmenter({"crop": True, "resize": True}, params, rng=random.Random(2))
     order = random.Random(1)
+    is_left = torch.from_numpy(np.random.default_rng(3).random(n_train) < opt.left_frac)
 
     def batches(epoch):
         idx = list(range(n_train))
         order.shuffle(idx)
         for s in range(0, n_train, BATCH):
             sel = torch.tensor(idx[s:s + BATCH])
-            yield aug(images[sel.to(DEV)], K[sel], j3d[sel])
+            left = {"is_left": is_left[sel]} if opt.left_frac > 0 else {}
+            yield aug(images[sel.to(DEV)], K[sel], j3d[sel], **left)
 
     def val_batches(epoch):
         for s in range(0, N_VAL, BATCH):
@@ -140,7 +144,7 @@ def main():
                                                  if half else ""))
     ratio = round(curve[-1] / curve[0], 3)
     out = {"arm": arm, "precision": opt.precision, "last_over_first_epoch_mean_loss_3d": ratio, "backbone": "rn50", "epochs": epochs,
-           "steps": tr.global_step, "batch": BATCH, "crop": SIZE, "lr": lr, "train_images": n_train, "augment": opt.augment, "seconds": round(dt, 1),
+           "steps": tr.global_step, "batch": BATCH, "crop": SIZE, "lr": lr, "train_images": n_train, "augment": opt.augment, "left_frac": opt.left_frac, "seconds": round(dt, 1),
            "images_per_s_incl_augmentation_validation_and_capture": round(BATCH * tr.global_step / dt),
            "epoch_mean_loss_3d": curve, "epoch_mean_loss_3d_val": val_curve, "evaluate": final}
     print(json.dumps(out))

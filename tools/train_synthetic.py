@@ -3,7 +3,9 @@
 (ResNet-18, crop+rotate alignment) -> NT-Xent -> LARS(Adam), through Trainer.fit with hipGraph replay.
 The "dataset" is a fixed set of structured synthetic images, so instance discrimination is learnable and
 the loss must fall.  --mixed-sizes: every second image is a 240 x 320 one, so that each batch mixes sizes and fit() runs
-from the augmenter's ragged path (`RaggedImages`).  Usage: python tools/train_synthetic.py [--mixed-sizes] [out.json]"""
+from the augmenter's ragged path (`RaggedImages`).  --left-frac F: that share of the images (chosen once, seeded) is marked as
+left hands, so that every batch mixes mirrored and plain reads (`is_left`).
+Usage: python tools/train_synthetic.py [--mixed-sizes] [--left-frac F] [out.json]"""
 import json
 import os
 import random
@@ -44,7 +46,13 @@ def make_dataset(mixed=False):
 def main():
     args = [a for a in sys.argv[1:] if a != "--mixed-sizes"]
     mixed = len(args) != len(sys.argv) - 1
+    left_frac = 0.0
+    if "--left-frac" in args:
+        at = args.index("--left-frac")
+        left_frac = float(args[at + 1])
+        del args[at:at + 2]
     images, joints = make_dataset(mixed)
+    is_left = torch.from_numpy(np.random.default_rng(2).random(N_IMAGES) < left_frac)
     cfg = hybrid2_config(resnet_size="18", projection_head_input_dim=512, augmentation=["crop", "rotate"],
                          batch_size=PAIRS, num_samples=N_IMAGES, warmup_epochs=2, pretrained=False)
     torch.manual_seed(0)
@@ -59,10 +67,11 @@ def main():
         order.shuffle(idx)
         for s in range(0, N_IMAGES, PAIRS):
             sel = torch.tensor(idx[s:s + PAIRS])
+            left = {"is_left": is_left[sel]} if left_frac > 0 else {}
             if mixed:
-                yield aug(RaggedImages.from_list([images[i] for i in sel.tolist()], DEV), joints[sel])
+                yield aug(RaggedImages.from_list([images[i] for i in sel.tolist()], DEV), joints[sel], **left)
             else:
-                yield aug(images[sel.to(DEV)], joints[sel])
+                yield aug(images[sel.to(DEV)], joints[sel], **left)
 
     curve = []
     orig = model.training_epoch_end
@@ -78,7 +87,7 @@ def main():
     tr.fit(model, batches)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    out = {"mixed_sizes": mixed, "epochs": EPOCHS, "steps": tr.global_step, "pairs_per_step": PAIRS, "seconds": round(dt, 1),
+    out = {"mixed_sizes": mixed, "left_frac": left_frac, "left_images": int(is_left.sum()), "epochs": EPOCHS, "steps": tr.global_step, "pairs_per_step": PAIRS, "seconds": round(dt, 1),
            "images_per_s_incl_augmentation_and_capture": round(2 * PAIRS * tr.global_step / dt), "epoch_mean_loss": curve}
     print(json.dumps(out))
     assert curve[-1] < 0.8 * curve[0], "the loss did not fall"
