@@ -526,7 +526,9 @@ int peclr_bn2d_pool_bwd_apply(const void* dy_pool, const void* x, const uint8_t*
  * src/data_loader/sample_augmenter.py:47-129: rotate_sample :218-247 cv2.warpAffine, crop_sample
  * :166-186, resize_sample :188-216 cv2.resize INTER_AREA, color_jitter_sample :267-293 cv2 BGR<->HSV)
  * plus ToTensor + Normalize (src/data_loader/utils.py:283-293).  The parameter side (random draws,
- * crop box, rotation matrix) stays on the host: peclr_amd/augment.py.
+ * crop box, rotation matrix) comes from the host by default, drawn from Python's `random` in the
+ * reference's order (peclr_amd/augment.py), or -- for the recipe flags, TwoViewAugmenter(device_draws=True)
+ * -- from peclr_augment_draw_views below, which writes the same `params` on the device.
  *
  * images : [B][H][W][3] uint8 (the reference's HWC images, one size per batch)
  * params : [n_views][B][PECLR_AUG_PARAM_DOUBLES] doubles per (view, sample):
@@ -661,6 +663,56 @@ int peclr_augment_warp_crop_ragged_mirror_u8(const uint8_t* images, int B, int n
                                              const int64_t* geom, const double* params,
                                              const int64_t* wins, int max_cw, int max_ch,
                                              const int* mirror, uint8_t* crops, peclr_stream_t stream);
+
+/* The PARAMETER side on the device (TwoViewAugmenter(device_draws=True)), csrc/augment_draw.hip: ONE launch computes, for
+ * every (view, sample) of the batch, what TwoViewAugmenter.sample_view computes on the host for the recipe flags (rotate, crop,
+ * random_crop, resize, color_jitter): the uniforms, the angle, the rotation centre, the forward and inverse matrices, the
+ * rotated joints, the crop window with margin and jitter, jitter_x / jitter_y and h / s / a / b -- in sample_view's own
+ * arithmetic (float32 where it works on float32 tensors, float64 where it uses Python floats, no contraction).  The pixel
+ * entry points above then run on the `params` it wrote, unchanged.  No host synchronisation; may be captured into a hipGraph.
+ *
+ * in   joints   : device [B][21][3], joints_dtype PECLR_DTYPE_F32 or PECLR_DTYPE_F64 (rounded to float32 first); x, y are read
+ *      H, W     : the image size of every sample (geom == NULL), >= 1
+ *      geom     : NULL, or the device [B][PECLR_AUG_GEOM_INT64S] table of a mixed-size batch; [1], [2] = H_i, W_i are read
+ *      mirror   : NULL, or device [B] ints, non-zero = a left hand: its x is read as W - x in float32 before anything else
+ *                 (the same table the `_mirror` pixel entry points take)
+ *      flags    : PECLR_AUG_DRAW_* bits; RESIZE is required (PECLR_ERR_UNSUPPORTED without it, or with an unknown bit)
+ *      ranges   : HOST pointer to PECLR_AUG_DRAW_RANGES doubles, passed to the kernel by value:
+ *                   [0] [1]  angle: uniform([0], [1]) // 1 (max_angle, min_angle: the reference's swapped order)
+ *                   [2] [3]  crop_margin_range        [4] crop_margin (random_crop off)
+ *                   [5]      upper end of crop_box_jitter (both axes draw uniform(0, [5]))
+ *                   [6] [7]  hue   [8] [9] saturation   [10] [11] value alpha   [12] [13] value beta
+ *      seed     : the Philox4x32-10 key (low word, high word)
+ *      call     : device uint64, the call counter: read by every workgroup, advanced by one by the last workgroup to finish.
+ *                 Launches that share it must be ordered on one stream.
+ *      counters : device int[2]: [0] += the number of SAMPLES of this launch with an EMPTY crop window in a view (cumulative;
+ *                 the host path raises ValueError for such a sample, the kernel clamps the window to the 1 x 1 window at the
+ *                 nearest pixel inside the image);
+ *                 [1] the ticket counter, zero between launches
+ * out  params   : [n_views][B][PECLR_AUG_PARAM_DOUBLES], the layout above
+ *      scalars  : [n_views][PECLR_AUG_DRAW_SCALARS][B] doubles: angle, crop_margin_scale, h, s, a, b (an entry whose flag is
+ *                 off holds its neutral value: 0, the fixed margin, 1, 1, 1, 0)
+ *      jitter   : [n_views][2][B] int64: jitter_x, jitter_y
+ *      uniforms : NULL, or [n_views][B][PECLR_AUG_DRAW_UNIFORMS] doubles, the raw uniforms in slot order angle, margin,
+ *                 jitter x, jitter y, h, s, a, b
+ * Random numbers: counter (sample i, 4 * view + k, call low word, call high word) for k = 0..3; call k gives slot 2k from the
+ * output words (x, y) and slot 2k + 1 from (z, w): u = ((x >> 5) * 2^26 + (y >> 6)) / 2^53 (Python's random()), and
+ * uniform(a, b) = a + (b - a) * u.  A slot whose flag is off is not used, so the draws of (view, sample) depend on nothing but
+ * (seed, call, view, sample).  1 <= B <= 32767 and n_views 1 or 2, else PECLR_ERR_SHAPE; null pointers PECLR_ERR_NULL. */
+#define PECLR_AUG_DRAW_ROTATE 1
+#define PECLR_AUG_DRAW_CROP 2
+#define PECLR_AUG_DRAW_RANDOM_CROP 4
+#define PECLR_AUG_DRAW_RESIZE 8
+#define PECLR_AUG_DRAW_COLOR_JITTER 16
+#define PECLR_AUG_DRAW_ALL 31
+#define PECLR_AUG_DRAW_RANGES 14
+#define PECLR_AUG_DRAW_SCALARS 6
+#define PECLR_AUG_DRAW_UNIFORMS 8
+int peclr_augment_draw_views(const void* joints, int joints_dtype, int B, int n_views, int H, int W,
+                             const int64_t* geom, const int* mirror, int flags, const double* ranges,
+                             uint64_t seed, uint64_t* call, int* counters, double* params,
+                             double* scalars, int64_t* jitter, double* uniforms,
+                             peclr_stream_t stream);
 
 /* ---- 16-bit convolutions of the residual blocks (bf16 / fp16 autocast: BASELINE configs C3 / C5 and the reference's own
  * `precision: 16`, training_config.json:9, peclr_training.py:78-79), csrc/conv_h.hip.  They replace MIOpen's 16-bit

@@ -90,6 +90,8 @@ SIGNATURES = {
     "peclr_augment_warp_crop_ragged_mirror_u8": (c_int, [_P, c_int, c_int, _P, _P, _P, c_int, c_int, _P, _P, _P]),
     "peclr_augment_resize_color_norm_ragged_ext": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, c_int, c_uint64, c_uint32,
                                                            c_int, c_int, _P, _P, c_int, _P, _P]),
+    "peclr_augment_draw_views": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, c_uint64, _P, _P, _P, _P, _P,
+                                         _P, _P]),
     "peclr_gemm_x6_f32": (c_int, [c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P]),
     "peclr_gemm_x6_tn_slabs": (c_int, [c_int, c_int, c_int]),
     "peclr_gemm_x6_tn_f32": (c_int, [c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, _P]),
@@ -1678,6 +1680,54 @@ def augment_views_ragged_ext(packed: torch.Tensor, geom: torch.Tensor, wins: tor
     aug = _AugExt(v, b, ext, coefs, noise_table, n_table, noise_seed, call, ops)
     return (*_augment_ragged(packed, geom, wins, params, b, v, scratch, aug, out_hw, mean, std, channels_last,
                              _aug_mirror(mirror, b)), wins)
+
+
+# ---- the parameter side on the device (include/peclr_hip.h: peclr_augment_draw_views)
+AUG_DRAW_ROTATE, AUG_DRAW_CROP, AUG_DRAW_RANDOM_CROP, AUG_DRAW_RESIZE, AUG_DRAW_COLOR_JITTER = 1, 2, 4, 8, 16
+AUG_DRAW_RANGES, AUG_DRAW_SCALARS, AUG_DRAW_UNIFORMS = 14, 6, 8
+
+
+def augment_draw_state(device):
+    """The device state of one stream of draws: (call, counters) -- call int64 [1] (the uint64 call counter's storage), counters
+    int32 [2] (cumulative empty windows, ticket).  Both zero; two fill launches, so allocate it OUTSIDE a graph capture."""
+    return torch.zeros(1, device=device, dtype=torch.int64), torch.zeros(2, device=device, dtype=torch.int32)
+
+
+def augment_draw_views(joints: torch.Tensor, image_hw, geom: Optional[torch.Tensor], mirror: Optional[torch.Tensor], flags: int,
+                       ranges, seed: int, call: torch.Tensor, counters: torch.Tensor, n_views: int = 2,
+                       return_uniforms: bool = False):
+    """joints [B,21,3] float32 / float64 (HIP); image_hw = (H, W) of every sample, or None with geom, the DEVICE [B,5] int64 table
+    of a mixed-size batch; mirror: None or int32 [B] (HIP), non-zero = a left hand; flags: AUG_DRAW_* bits; ranges: the 14
+    doubles of include/peclr_hip.h; seed: the Philox key; call / counters: `augment_draw_state`, advanced by the launch.
+    ONE launch, no host synchronisation.  Returns (params [V,B,16] float64, scalars [V,6,B] float64 -- angle, crop margin, h, s,
+    a, b --, jitter [V,2,B] int64, uniforms [V,B,8] float64 or None)."""
+    if (not isinstance(joints, torch.Tensor) or joints.dim() != 3 or tuple(joints.shape[1:]) != (21, 3)
+            or joints.dtype not in (torch.float32, torch.float64)):
+        raise PeclrHipError("augment_draw: joints must be a [B,21,3] float32 or float64 HIP tensor")
+    b, dev = joints.shape[0], joints.device
+    joints_ptr = _ptr(joints, joints.dtype, "augment_draw: joints")
+    if geom is None:
+        h, w = (int(x) for x in image_hw)
+        geom_ptr = None
+    else:
+        if tuple(geom.shape) != (b, AUG_GEOM_INT64S):
+            raise PeclrHipError(f"augment_draw: geom must be a device [{b},{AUG_GEOM_INT64S}] int64 tensor")
+        h, w, geom_ptr = 0, 0, _ptr(geom, torch.int64, "augment_draw: geom")
+    if len(ranges) != AUG_DRAW_RANGES:
+        raise PeclrHipError(f"augment_draw: ranges must hold {AUG_DRAW_RANGES} numbers")
+    if tuple(call.shape) != (1,) or tuple(counters.shape) != (2,):
+        raise PeclrHipError("augment_draw: call must be int64 [1] and counters int32 [2] (augment_draw_state)")
+    ranges_arr = (c_double * AUG_DRAW_RANGES)(*(float(x) for x in ranges))
+    params = torch.empty((n_views, b, AUG_PARAM_DOUBLES), device=dev, dtype=torch.float64)
+    scalars = torch.empty((n_views, AUG_DRAW_SCALARS, b), device=dev, dtype=torch.float64)
+    jitter = torch.empty((n_views, 2, b), device=dev, dtype=torch.int64)
+    uniforms = torch.empty((n_views, b, AUG_DRAW_UNIFORMS), device=dev, dtype=torch.float64) if return_uniforms else None
+    _launch("augment_draw", "peclr_augment_draw_views", joints_ptr, DTYPE_F32 if joints.dtype == torch.float32 else DTYPE_F64, b,
+            n_views, h, w, geom_ptr, _aug_mirror(mirror, b), int(flags), ctypes.cast(ranges_arr, c_void_p), int(seed) & (2 ** 64 - 1),
+            _ptr(call, torch.int64, "augment_draw: call"), _ptr(counters, torch.int32, "augment_draw: counters"), params.data_ptr(),
+            scalars.data_ptr(), jitter.data_ptr(), None if uniforms is None else uniforms.data_ptr(), _stream(),
+            nbytes=n_views * b * 8 * (AUG_PARAM_DOUBLES + AUG_DRAW_SCALARS + 2) + b * 63 * joints.element_size())
+    return params, scalars, jitter, uniforms
 
 
 # ------------------------------------------------------------------ 2.5D hand-pose model at evaluation time (peclr_amd/pose.py)

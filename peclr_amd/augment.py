@@ -12,6 +12,10 @@ Mirrors `Data_Set.prepare_hybrid2_sample` (reference src/data_loader/data_set.py
          reference's for the same seed (pinned by tests/golden/g9_augment_params.json).
   device the PIXEL side for the whole batch and both views: csrc/augment.hip (two launches).
 
+With `TwoViewAugmenter(..., device_draws=True)` the parameter side of these recipe flags runs on the device as well: one
+launch (csrc/augment_draw.hip) computes the same function of Philox uniforms for the whole batch, the two pixel launches follow
+on the `params` it wrote, and a call with device inputs neither synchronises with the host nor reads it (see `__init__`).
+
 The emitted dict is what torch's default collate makes of the reference's per-sample dicts:
 `transformed_image{1,2}` float32 [B,3,S,S]; `jitter_{x,y}_{1,2}` int64 [B]; `angle_{1,2}` float64 [B]
 (only with rotate); `h/s/a/b_{1,2}` float64 [B] (only with colour jitter); `crop_margin_scale_{1,2}`
@@ -243,7 +247,8 @@ class RaggedImages:
 
 class TwoViewAugmenter:
     def __init__(self, flags: Optional[Dict[str, bool]] = None, params: Optional[Dict] = None, rng=None,
-                 channels_last: bool = True, extended: bool = False, np_rng=None, noise_seed: Optional[int] = None):
+                 channels_last: bool = True, extended: bool = False, np_rng=None, noise_seed: Optional[int] = None,
+                 device_draws: bool = False, draw_seed: Optional[int] = None):
         """flags / params: the reference's `augmentation_flags` / `augmentation_params` (missing flags
         are off, missing params take training_config.json's values).  rng: object with `.uniform`
         and `.getrandbits` (default: Python's global `random`, the generator the reference draws from).
@@ -260,10 +265,33 @@ class TwoViewAugmenter:
             nothing from `rng` or `np_rng`.
           * sobel_filter: the reference stores the float64 Sobel sum into uint8, which follows x86 NumPy's
             float-to-uint8 conversion (the value modulo 256); that is what is done here.
-        Blur's 8-bit fixed-point path is a restatement of OpenCV's (see `gaussian_kernel_q8`)."""
+        Blur's 8-bit fixed-point path is a restatement of OpenCV's (see `gaussian_kernel_q8`).
+
+        device_draws=True moves the parameter side of the recipe flags to the device: ONE launch (csrc/augment_draw.hip) computes
+        for every (view, sample) what `sample_view` computes -- the same function, in the same float32 / float64 arithmetic, of
+        uniforms that come from Philox4x32-10 keyed by `draw_seed` (default: torch.initial_seed()) instead of from `rng`; the
+        stream is NOT Python's, so a seeded host run and a device run draw different numbers of the same distribution.  The
+        call counter lives on the device and advances with every launch, also when a hipGraph replays it.  A dense call with
+        device images, device joints and `is_left` None or a device tensor then makes no host synchronisation and can be
+        captured with torch.cuda.graph (call once, or `draw_state(device)`, before the capture: the state is allocated on first
+        use).  The five `extended` flags and a caller's `rng` / `np_rng` are refused with it; an empty crop window, for which
+        the host path raises, is clamped to one pixel and counted (`bad_windows`)."""
         self.flags = dict(RECIPE_FLAGS if flags is None else flags)
         self.params = dict(DEFAULT_PARAMS, **(params or {}))
         self.extended = extended
+        self.device_draws = bool(device_draws)
+        if device_draws:
+            for k in _UNSUPPORTED:
+                if self.flags.get(k):
+                    raise NotImplementedError(f"augmentation '{k}' is drawn on the host only: device draws cover the recipe "
+                                              "flags (rotate, crop, random_crop, resize, color_jitter)")
+            if rng is not None or np_rng is not None:
+                raise ValueError("device_draws=True draws from Philox keyed by draw_seed: rng / np_rng would be ignored")
+        elif draw_seed is not None:
+            raise ValueError("draw_seed is the key of the device draws: pass device_draws=True with it")
+        self.draw_seed = (torch.initial_seed() if draw_seed is None else int(draw_seed)) & (2 ** 64 - 1)
+        self._draw_state: Dict = {}  # device -> (call, counters), _capi.augment_draw_state
+        self._blur_false: Dict = {}  # (device, B) -> the all-false blur_flag entry
         if not extended:
             for k in _UNSUPPORTED:
                 if self.flags.get(k):
@@ -512,15 +540,157 @@ class TwoViewAugmenter:
             batch["is_left"] = torch.tensor(left, dtype=torch.bool).to(dev, non_blocking=True)
         return batch
 
+    # ---- device: the parameter side (device_draws=True)
+    def draw_flags(self) -> int:
+        """The recipe flags as include/peclr_hip.h's PECLR_AUG_DRAW_* bits."""
+        f = self.flags
+        return ((_capi.AUG_DRAW_ROTATE if f.get("rotate") else 0) | (_capi.AUG_DRAW_CROP if f.get("crop") else 0)
+                | (_capi.AUG_DRAW_RANDOM_CROP if f.get("random_crop") else 0) | (_capi.AUG_DRAW_RESIZE if f.get("resize") else 0)
+                | (_capi.AUG_DRAW_COLOR_JITTER if f.get("color_jitter") else 0))
+
+    def draw_ranges(self) -> List[float]:
+        """include/peclr_hip.h's `ranges`: the arguments of `sample_view`'s uniform(a, b) calls, in its order."""
+        p = self.params
+        return [float(x) for x in (p["max_angle"], p["min_angle"], *p["crop_margin_range"][:2], p["crop_margin"],
+                                   p["crop_box_jitter"][1], *p["hue_factor_range"][:2], *p["sat_factor_range"][:2],
+                                   *p["value_factor_alpha_range"][:2], *p["value_factor_beta_range"][:2])]
+
+    def draw_state(self, device) -> Tuple[Tensor, Tensor]:
+        """(call, counters) of `device`: the int64 [1] call counter and the int32 [2] (empty windows, ticket) the draw launch
+        advances.  Allocated and zeroed on first use, which must not happen inside a graph capture."""
+        device = torch.device(device)
+        if device.index is None:
+            device = torch.device(device.type, torch.cuda.current_device())
+        if device not in self._draw_state:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("TwoViewAugmenter: the device draw state is allocated on first use; call the augmenter (or "
+                                   "draw_state(device)) once before capturing it into a graph")
+            self._draw_state[device] = _capi.augment_draw_state(device)
+        return self._draw_state[device]
+
+    def bad_windows(self) -> int:
+        """How many samples of all device-drawn batches so far had an EMPTY crop window in one of their views (the host path
+        raises ValueError for such a sample; the device clamps the window to one pixel inside the image).  This is the one
+        call here that SYNCHRONISES with the device: ask at the end of an epoch, not every step."""
+        return sum(int(counters[0].item()) for _, counters in self._draw_state.values())
+
+    def draw_batch(self, joints: Tensor, image_hw=None, geom: Optional[Tensor] = None, mirror: Optional[Tensor] = None,
+                   return_uniforms: bool = False):
+        """The ONE launch of the device draws, for both views of a batch: joints [B,21,3] float32 / float64 on the device;
+        image_hw = (H, W) of every sample, or geom, the DEVICE [B,5] int64 table of a mixed-size batch; mirror: None or the
+        device int32 [B] left-hand table.  Advances this device's call counter.  No host synchronisation.
+        -> `_capi.augment_draw_views`'s (params [2,B,16], scalars [2,6,B], jitter [2,2,B], uniforms [2,B,8] or None)."""
+        call, counters = self.draw_state(joints.device)
+        return _capi.augment_draw_views(joints, image_hw, geom, mirror, self.draw_flags(), self.draw_ranges(), self.draw_seed,
+                                        call, counters, 2, return_uniforms)
+
+    @staticmethod
+    def _check_device_left(is_left, b: int):
+        """is_left of a device-drawn batch, checked on the host: a device tensor (never read here) by shape and dtype, anything
+        else by `check_is_left`.  -> (the device tensor or None, the list of bools or None)."""
+        if isinstance(is_left, Tensor) and is_left.is_cuda:
+            if is_left.dim() != 1 or is_left.shape[0] != b:
+                raise ValueError(f"is_left: expected {b} entries, one per sample, got shape {tuple(is_left.shape)}")
+            if is_left.dtype.is_floating_point or is_left.dtype.is_complex:
+                raise TypeError(f"is_left: expected bools or integers 0 / 1, got {is_left.dtype}")
+            return is_left, None
+        return None, check_is_left(is_left, b)
+
+    @staticmethod
+    def _device_left(on_device: Optional[Tensor], left: Optional[List[bool]], sizes: Sequence[Tuple[int, int]], dev):
+        """`_check_device_left`'s result -> (mirror int32 [B] on the device or None, the dict's bool [B] entry or None)."""
+        if on_device is not None:
+            flag = on_device if on_device.dtype == torch.bool else on_device != 0
+            return flag.to(torch.int32), flag
+        if left is None:
+            return None, None
+        mirror = mirror_table(left, sizes)
+        return (None if mirror is None else mirror.to(dev, non_blocking=True),
+                torch.tensor(left, dtype=torch.bool).to(dev, non_blocking=True))
+
+    def _call_device(self, images, joints25d, is_left, return_uniforms: bool) -> Dict[str, Tensor]:
+        """`__call__` with the draws on the device.  Everything that can be refused is refused before the first device call."""
+        ragged = not isinstance(images, Tensor)
+        if ragged:
+            sizes = images.sizes if isinstance(images, RaggedImages) else RaggedImages.check(images)
+            b = len(sizes)
+        else:
+            if not images.is_cuda or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+                raise _capi.PeclrHipError(f"augment: images must be a [B,H,W,3] uint8 HIP tensor, got {images.dtype} "
+                                          f"{tuple(images.shape)} on {images.device} (peclr_amd has no CPU path)")
+            b, h, w, _ = images.shape
+            sizes = [(h, w)] * b
+        joints = joints25d if isinstance(joints25d, Tensor) else torch.as_tensor(np.asarray(joints25d))
+        if joints.dim() != 3 or tuple(joints.shape[1:]) != (21, 3) or joints.shape[0] != b:
+            raise ValueError(f"joints25d: expected [{b},21,3] for {b} images, got {tuple(joints.shape)}")
+        if joints.dtype not in (torch.float32, torch.float64):
+            joints = joints.to(torch.float32)
+        left_checked = self._check_device_left(is_left, b)
+        if ragged and not isinstance(images, RaggedImages):
+            dev = next((im.device for im in images if isinstance(im, Tensor) and im.is_cuda), torch.device("cuda"))
+            images = RaggedImages.from_list(images, dev)
+        dev = images.device
+        self.draw_state(dev)
+        mirror, left = self._device_left(*left_checked, sizes, dev)
+        lr = {} if mirror is None else {"mirror": mirror}
+        joints = joints.detach().to(dev, non_blocking=True).contiguous()
+        rw, rh = self.params["resize_shape"]
+        if not ragged:
+            params, scalars, jitter, uniforms = self.draw_batch(joints, (h, w), None, mirror, return_uniforms)
+            out, _ = _capi.augment_views(images, params, (rh, rw), IMAGENET_MEAN, IMAGENET_STD, self.channels_last, **lr)
+        else:
+            geom, wins = self.ragged_slot_tables(sizes, images.offsets, int(images.data.numel()))
+            params, scalars, jitter, uniforms = self.draw_batch(joints, None, geom.to(dev, non_blocking=True), mirror,
+                                                                return_uniforms)
+            out = _capi.augment_views_ragged(images.data, geom, wins, params, (rh, rw), IMAGENET_MEAN, IMAGENET_STD,
+                                             self.channels_last, **lr)[0]
+        batch = {"transformed_images": out, "transformed_image1": out[:b], "transformed_image2": out[b:]}
+        if (dev, b) not in self._blur_false:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("TwoViewAugmenter: call once with this batch size before capturing it into a graph")
+            self._blur_false[(dev, b)] = torch.zeros(b, device=dev, dtype=torch.bool)
+        f = self.flags
+        for v in (0, 1):
+            entries = {"angle": scalars[v, 0] if f.get("rotate") else None, "jitter_x": jitter[v, 0], "jitter_y": jitter[v, 1]}
+            if f.get("color_jitter"):
+                entries.update(h=scalars[v, 2], s=scalars[v, 3], a=scalars[v, 4], b=scalars[v, 5])
+            entries.update(blur_flag=self._blur_false[(dev, b)], crop_margin_scale=scalars[v, 1])
+            batch.update({f"{k}_{v + 1}": t for k, t in entries.items() if t is not None})  # `collate` drops them too
+        if left is not None:
+            batch["is_left"] = left
+        if uniforms is not None:  # what makes the draws checkable: the uniforms and the records the pixel stages read
+            batch["params"], batch["uniforms"] = params, uniforms
+        return batch
+
+    @staticmethod
+    def ragged_slot_tables(sizes: Sequence[Tuple[int, int]], offsets: Tensor, total: int) -> Tuple[Tensor, Tensor]:
+        """`ragged_tables` when the windows are not known on the host (device draws): view v of sample i gets a slot the size
+        of its whole image at byte v * total + offset_i, row stride W_i -- so the tables depend on the sizes alone and the
+        window, wherever the draw puts it, fits.  The scratch is V * total bytes, the warp's grid the largest image's."""
+        geom = torch.tensor([[off, h, w, *blur_ksize((h, w))] for off, (h, w) in zip(offsets.tolist(), sizes)],
+                            dtype=torch.int64)
+        wins = torch.tensor([[[v * total + off, w, w, h] for off, (h, w) in zip(offsets.tolist(), sizes)] for v in (0, 1)],
+                            dtype=torch.int64)
+        return geom, wins
+
     # ---- device: the batch
-    def __call__(self, images: Union[Tensor, RaggedImages, Sequence], joints25d: Tensor, is_left=None) -> Dict[str, Tensor]:
+    def __call__(self, images: Union[Tensor, RaggedImages, Sequence], joints25d: Tensor, is_left=None,
+                 return_uniforms: bool = False) -> Dict[str, Tensor]:
         """images: [B,H,W,3] uint8 on the HIP device (the reference's RGB HWC arrays, one size per
         batch), or -- for a batch whose images differ in size -- a `RaggedImages`, or a list / tuple of HWC uint8
         arrays (packed and copied here); joints25d: [B,21,3] (any device; the parameter logic runs on the host).
         is_left: None, or B bools (or integers 0 / 1): a flagged sample comes out as the reference loader's
         (cv2.flip(img, 1), x <- W - x) would -- its image as stored, read mirrored on the device, its joints in the stored
         image's coordinates (`sample_batch` has the rule).  The dict then also holds `is_left` (bool [B], device).  None or
-        all false launches exactly what a call without it launches."""
+        all false launches exactly what a call without it launches.
+        With device_draws=True the joints are read on the device (a CPU tensor is uploaded), `is_left` may be a device bool /
+        integer [B] tensor, which is then never read on the host; with return_uniforms=True the dict also holds `uniforms`
+        (float64 [2,B,8]: angle, margin, jitter x, jitter y, h, s, a, b) and `params` (float64 [2,B,16], the records the
+        pixel stages read)."""
+        if self.device_draws:
+            return self._call_device(images, joints25d, is_left, return_uniforms)
+        if return_uniforms:
+            raise ValueError("return_uniforms needs device_draws=True: the host draws come from rng")
         if not isinstance(images, Tensor):
             return self._call_ragged(images, joints25d, is_left)
         b, h, w, _ = images.shape

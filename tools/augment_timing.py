@@ -11,7 +11,13 @@ With `--left OUT.txt` it times left hands instead (`is_left`, the mirrored read)
 batch and a mixed-size one (64 x 224^2 + 64 x 480 x 640), recipe flags (the warp mirrors) and all ten flags (stage 0 mirrors);
 per case six windows that ALTERNATE the batch without left hands and the same batch with every second sample left, so that the
 window-to-window spread of either arm is the yardstick for the difference between them.
-Usage: python tools/augment_timing.py [out.json [ragged_out.json]] | --left OUT.txt"""
+With `--device-draws OUT.txt` it times the parameter side on the device (TwoViewAugmenter(device_draws=True)) against the host
+draws: B = 128, 128 x 128 out, the dense 224 x 224 batch and the mixed-size one, recipe flags, six windows per case that ALTERNATE
+the two arms.  host_param_ms is what the host spends on the parameters of one batch: `sample_batch` in the host arm, issuing the
+one draw launch (joints already on the device) in the device arm.  In the mixed-size case the device arm's windows sit in
+whole-image slots under a grid of the largest image, the host arm's are packed: the rows of the two pixel launches show what
+that costs.
+Usage: python tools/augment_timing.py [out.json [ragged_out.json]] | --left OUT.txt | --device-draws OUT.txt"""
 import json
 import os
 import random
@@ -139,9 +145,58 @@ def left_rows(path):
         f.write("\n".join(lines))
 
 
+def device_draw_rows(path):
+    b, size, windows = 128, 128, 6
+    g = np.random.default_rng(0)
+    small = [g.integers(0, 256, (224, 224, 3), dtype=np.uint8) for _ in range(b)]
+    big = [g.integers(0, 256, (480, 640, 3), dtype=np.uint8) for _ in range(b // 2)]
+    mixed = [im for pair in zip(small[:b // 2], big) for im in pair]
+    lines = [f"device draws timing: B = {b}, out {size} x {size}, recipe flags, {windows} alternating windows per case (10 batches each "
+             "after 3 warm-up batches); kernel_us = device-event time per batch, summed per launch name", ""]
+    for case, images in (("dense 128 x 224^2", torch.from_numpy(np.stack(small)).to(DEV)),
+                         ("mixed 64 x 224^2 + 64 x 480x640", RaggedImages.from_list(mixed, DEV))):
+        ragged = isinstance(images, RaggedImages)
+        sizes = images.sizes if ragged else [(224, 224)] * b
+        joints = torch.from_numpy(np.stack([np.concatenate([g.normal((w / 2, h / 2 - 4), min(h, w) / 9, (21, 2)),
+                                                            g.normal(0, 1, (21, 1))], 1) for h, w in sizes])).float()
+        joints_dev = joints.to(DEV)
+        geom_dev = TwoViewAugmenter.ragged_slot_tables(sizes, images.offsets, images.data.numel())[0].to(DEV) if ragged else None
+        arms = {"host draws": [], "device draws": []}
+        for win in range(windows):
+            if win % 2:
+                arm, a = "device draws", TwoViewAugmenter(params={"resize_shape": [size, size]}, device_draws=True, draw_seed=1)
+                r = timed(lambda: a(images, joints_dev), lambda: a.draw_batch(joints_dev, None if ragged else (224, 224), geom_dev))
+                assert a.bad_windows() == 0
+            else:
+                arm, a = "host draws", TwoViewAugmenter(params={"resize_shape": [size, size]}, rng=random.Random(1))
+                r = timed(lambda: a(images, joints), lambda: a.sample_batch(joints, sizes))
+            arms[arm].append(r)
+            lines.append(f"{case:34s} window {win} {arm:12s} kernel_us {r['kernel_us']} total {r['kernel_total_us']}"
+                         f" end_to_end_ms {r['end_to_end_ms']} host_param_ms {r['host_param_ms']}")
+            print(lines[-1], flush=True)
+        names = sorted({k for rs in arms.values() for r in rs for k in r["kernel_us"]})
+        for name in names + ["kernel_total_us", "host_param_ms", "end_to_end_ms"]:
+            get = (lambda r: r["kernel_us"].get(name, 0.0)) if name in names else (lambda r: r[name])
+            host, devc = [get(r) for r in arms["host draws"]], [get(r) for r in arms["device draws"]]
+            unit = "ms" if name.endswith("_ms") else "us"
+            lines.append(f"  {name:28s} host draws {min(host):9.2f} .. {max(host):9.2f}   device draws {min(devc):9.2f} .. {max(devc):9.2f}   "
+                         f"difference of the means {sum(devc) / len(devc) - sum(host) / len(host):+9.2f} {unit}, spread within an arm "
+                         f"{max(max(host) - min(host), max(devc) - min(devc)):.2f} {unit}")
+            print(lines[-1], flush=True)
+        e_host, e_dev = (sum(r["end_to_end_ms"] for r in arms[k]) / len(arms[k]) for k in ("host draws", "device draws"))
+        lines.append(f"  end_to_end_ms, host draws / device draws: {e_host / e_dev:.1f} x   ({2 * b / e_host * 1e3:.0f} -> "
+                     f"{2 * b / e_dev * 1e3:.0f} images/s per process)")
+        print(lines[-1], flush=True)
+        lines.append("")
+    with open(path, "w") as f:
+        f.write("\n".join(lines))
+
+
 def main():
     if len(sys.argv) > 2 and sys.argv[1] == "--left":
         return left_rows(sys.argv[2])
+    if len(sys.argv) > 2 and sys.argv[1] == "--device-draws":
+        return device_draw_rows(sys.argv[2])
     rows = []
     g = np.random.default_rng(0)
     for b, size, all_ten in ((128, 128, False), (128, 224, False), (512, 128, False), (128, 128, True)):

@@ -4,8 +4,9 @@
 The "dataset" is a fixed set of structured synthetic images, so instance discrimination is learnable and
 the loss must fall.  --mixed-sizes: every second image is a 240 x 320 one, so that each batch mixes sizes and fit() runs
 from the augmenter's ragged path (`RaggedImages`).  --left-frac F: that share of the images (chosen once, seeded) is marked as
-left hands, so that every batch mixes mirrored and plain reads (`is_left`).
-Usage: python tools/train_synthetic.py [--mixed-sizes] [--left-frac F] [out.json]"""
+left hands, so that every batch mixes mirrored and plain reads (`is_left`).  --device-draws: the augmentation parameters are drawn
+on the device (TwoViewAugmenter(device_draws=True)); joints and `is_left` then live there too and no batch reads them on the host.
+Usage: python tools/train_synthetic.py [--mixed-sizes] [--left-frac F] [--device-draws] [out.json]"""
 import json
 import os
 import random
@@ -44,8 +45,8 @@ def make_dataset(mixed=False):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a != "--mixed-sizes"]
-    mixed = len(args) != len(sys.argv) - 1
+    args = [a for a in sys.argv[1:] if a not in ("--mixed-sizes", "--device-draws")]
+    mixed, device_draws = "--mixed-sizes" in sys.argv[1:], "--device-draws" in sys.argv[1:]
     left_frac = 0.0
     if "--left-frac" in args:
         at = args.index("--left-frac")
@@ -59,7 +60,11 @@ def main():
     model = Hybrid2Model(cfg).to(DEV).train()
     model.encoder = model.encoder.to(memory_format=torch.channels_last)
     enable_hip_batchnorm(model.encoder)
-    aug = TwoViewAugmenter(params={"resize_shape": [SIZE, SIZE]}, rng=random.Random(0))
+    if device_draws:
+        aug = TwoViewAugmenter(params={"resize_shape": [SIZE, SIZE]}, device_draws=True, draw_seed=0)
+        joints, is_left = joints.to(DEV), is_left.to(DEV)
+    else:
+        aug = TwoViewAugmenter(params={"resize_shape": [SIZE, SIZE]}, rng=random.Random(0))
     order = random.Random(1)
 
     def batches(epoch):
@@ -67,11 +72,12 @@ def main():
         order.shuffle(idx)
         for s in range(0, N_IMAGES, PAIRS):
             sel = torch.tensor(idx[s:s + PAIRS])
-            left = {"is_left": is_left[sel]} if left_frac > 0 else {}
+            rows = sel.to(DEV) if device_draws else sel
+            left = {"is_left": is_left[rows]} if left_frac > 0 else {}
             if mixed:
-                yield aug(RaggedImages.from_list([images[i] for i in sel.tolist()], DEV), joints[sel], **left)
+                yield aug(RaggedImages.from_list([images[i] for i in sel.tolist()], DEV), joints[rows], **left)
             else:
-                yield aug(images[sel.to(DEV)], joints[sel], **left)
+                yield aug(images[sel.to(DEV)], joints[rows], **left)
 
     curve = []
     orig = model.training_epoch_end
@@ -87,7 +93,8 @@ def main():
     tr.fit(model, batches)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    out = {"mixed_sizes": mixed, "left_frac": left_frac, "left_images": int(is_left.sum()), "epochs": EPOCHS, "steps": tr.global_step, "pairs_per_step": PAIRS, "seconds": round(dt, 1),
+    out = {"device_draws": device_draws, "empty_windows": aug.bad_windows() if device_draws else 0,
+           "last_over_first_epoch_mean_loss": round(curve[-1] / curve[0], 3), "mixed_sizes": mixed, "left_frac": left_frac, "left_images": int(is_left.sum()), "epochs": EPOCHS, "steps": tr.global_step, "pairs_per_step": PAIRS, "seconds": round(dt, 1),
            "images_per_s_incl_augmentation_and_capture": round(2 * PAIRS * tr.global_step / dt), "epoch_mean_loss": curve}
     print(json.dumps(out))
     assert curve[-1] < 0.8 * curve[0], "the loss did not fall"
